@@ -1,9 +1,16 @@
 #!/usr/bin/env python
 """Benchmark of the MoBGS render hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step, ...).
+--full adds everything else the line can carry: the secondary legs, `repeat`, the roofline (incl. the rocprofv3 child
+runs), the CPU baselines, and at N > 1 the one-GPU anchor and the scaling diagnostics.  Their options (--deblur-steps,
+--dynamic-steps, --flow-steps, --train-steps, --small-steps, --repeat-steps, --cpu-reps, --pmc) need --full: a plain
+run refuses a non-zero value.
+--dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy (see dump_outputs()).
 
 Metric (BASELINE.json): train-step renders/sec (fwd+bwd, 1352x1014, 300k Gaussians) at 1/2/4/8 GPU.
 
@@ -23,7 +30,7 @@ N > 1   one step = one training iteration's blurry-view part (train.py:430-541) 
         Gaussian leaves, decoder, BLCE parameters, mid-frame densification statistics) completes the step.
         `value` = 18 renders x steps / time = whole-job renders/s; total work per step is fixed: "scaling": "strong".
 
-Inputs are resident in HBM before the timed region.  Prints ONE JSON line on rank 0 (see the task contract) with
+Inputs are resident in HBM before the timed region.  Prints ONE JSON line on rank 0 with, under --full,
   roofline     -- the dominant kernel (raster_bwd): algorithmic bytes / HIP-event time vs the 8 TB/s HBM peak, plus
                   pixel-splat pairs/s, fp32 FLOP/s against the 157.3 TFLOP/s vector peak
   cpu_baseline -- oracle/gsplat_cpu.c (OpenMP port of upstream's kernels) at the full workload and the north-star
@@ -534,6 +541,32 @@ def scaling_diagnostics(wl, shard, args, dev, world, dist, steps=3):
                     "and show up as busy time"}
 
 
+DUMP_ROWS = 65536          # --dump-outputs: per-row arrays longer than this are written as a fixed, seeded row sample
+DUMP_LIMIT = 64 * 2 ** 20  # ... and all the files of one dump together stay below this many bytes
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """--dump-outputs: write `arrays` ([(name, tensor, per_row)]) as <out_dir>/<name>.npy, float32 (float64 stays
+    float64).  A per_row array (one row per Gaussian / buffer element) with more than DUMP_ROWS rows is written as the
+    rows of a sorted random sample drawn from a generator seeded with seed + its row count: the same rows every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    picks, total = {}, 0
+    for name, t, per_row in arrays:
+        a = t.detach()
+        n = a.shape[0] if a.dim() else 1
+        if per_row and n > DUMP_ROWS:
+            if n not in picks:
+                g = torch.Generator().manual_seed(seed + n)
+                picks[n] = torch.randperm(n, generator=g)[:DUMP_ROWS].sort().values
+            a = a[picks[n].to(a.device)]
+        a = (a.double() if a.dtype == torch.float64 else a.float()).cpu().numpy()
+        total += a.nbytes
+        assert total <= DUMP_LIMIT, f"--dump-outputs: more than {DUMP_LIMIT} bytes"
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
+
+
 def freeze_python_heap():
     gc.collect()
     gc.freeze()
@@ -596,6 +629,11 @@ def stall_counters(since=None):
     return now if since is None else {k: now[k] - since[k] for k in now}
 
 
+# the options of what only a --full run measures, with their defaults there (a plain run refuses a non-zero value)
+FULL_LEGS = {"deblur_steps": 10, "dynamic_steps": 20, "flow_steps": 4, "train_steps": 10, "small_steps": 20,
+             "repeat_steps": 100, "cpu_reps": 2}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -606,24 +644,43 @@ def main():
     ap.add_argument("--width", type=int, default=1352)
     ap.add_argument("--height", type=int, default=1014)
     ap.add_argument("--views", type=int, default=2, help="views per training iteration in the deblur step")
-    ap.add_argument("--deblur-steps", type=int, default=10, help="N=1: steps of the secondary deblur leg (0: skip)")
-    ap.add_argument("--dynamic-steps", type=int, default=20, help="N=1: steps of the secondary config #3 leg (0: skip)")
-    ap.add_argument("--flow-steps", type=int, default=4, help="N=1: steps of the secondary get_flow leg (0: skip)")
+    ap.add_argument("--deblur-steps", type=int, default=None, help="N=1: steps of the secondary deblur leg (0: skip)")
+    ap.add_argument("--dynamic-steps", type=int, default=None, help="N=1: steps of the secondary config #3 leg (0: skip)")
+    ap.add_argument("--flow-steps", type=int, default=None, help="N=1: steps of the secondary get_flow leg (0: skip)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-cpu-torch", action="store_true", help="skip the PyTorch-CPU config #1 render (tens of s)")
-    ap.add_argument("--cpu-reps", type=int, default=2)
+    ap.add_argument("--cpu-reps", type=int, default=None)
     ap.add_argument("--prewarm", type=int, default=40, help="untimed set-up steps before the W warm-up steps (arena sizing)")
-    ap.add_argument("--train-steps", type=int, default=10, help="N=1: whole training iterations timed (0: skip)")
-    ap.add_argument("--small-steps", type=int, default=20,
+    ap.add_argument("--train-steps", type=int, default=None, help="N=1: whole training iterations timed (0: skip)")
+    ap.add_argument("--small-steps", type=int, default=None,
                     help="N=1: whole iterations at the reference's own 512x288 / 30 k operating point, eager and graphed (0: skip)")
-    ap.add_argument("--repeat-steps", type=int, default=100,
+    ap.add_argument("--repeat-steps", type=int, default=None,
                     help="N=1: further lean steps after the K timed ones; their HIP-event median is reported as `repeat`")
     ap.add_argument("--no-kernel-breakdown", action="store_true",
                     help="skip the rocprofv3 child run behind roofline.streaming")
     ap.add_argument("--pmc", action="store_true",
                     help="re-collect roofline.traffic / roofline.valu (three rocprofv3 --pmc child runs) first")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary legs, repeat, roofline, CPU baselines and (N > 1) the anchor and "
+                         "scaling diagnostics; a plain run does only what the headline figure needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy")
     ap.add_argument("--breakdown-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if not args.full:
+        # a plain run: set-up, warm-up, the K timed steps, the outputs, the line -- every other leg is --full's, and
+        # asking for one of them without --full is an error rather than a line that silently lacks it
+        asked = [f"--{k.replace('_', '-')}" for k in FULL_LEGS if getattr(args, k) not in (None, 0)]
+        asked += ["--pmc"] if args.pmc else []
+        if asked:
+            raise SystemExit(f"{' '.join(asked)}: measured only by a --full run (add --full)")
+        for k in FULL_LEGS:
+            setattr(args, k, 0)
+        args.no_cpu_baseline = args.no_kernel_breakdown = True
+    else:
+        for k, v in FULL_LEGS.items():
+            if getattr(args, k) is None:
+                setattr(args, k, v)
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -698,10 +755,23 @@ def main():
         freeze_python_heap()            # (see timed(): here, so that the set-up steps below re-heat the device after it)
         for _ in range(args.prewarm):
             lean_step()
-        profiler.enable(True)
+        profiler.enable(args.full)      # (HIP events around the compositors: the roofline's raster_bwd time)
         dt, med_ms = timed(lean_step, args.steps, args.warmup, world, dist, freeze=False)
-        prof = profiler.summary()
+        prof = profiler.summary() if args.full else {}
         profiler.enable(False)
+        if args.dump_outputs:
+            # what a caller of the timed path receives from its last step: the images and per-splat outputs of render()
+            # and the gradients backward() left on the leaves, the decoder weights and the camera pose
+            out = last["out"]
+            arrays = [("render", out["render"], False), ("depth", out["depth"], False),
+                      ("radii", out["radii"], True), ("viewspace_points", out["viewspace_points"].squeeze(0), True)]
+            for tag, d in (("stat", stat.trainable_tensors(False)), ("dyn", dyn.trainable_tensors(True))):
+                arrays += [(f"grad_{tag}_{k.lstrip('_')}", t.grad, True) for k, t in d.items() if t.grad is not None]
+            arrays += [(f"grad_decoder_{k}", p.grad, False) for k, p in dyn.rgbdecoder.named_parameters()
+                       if p.grad is not None]
+            if cam_lean.world_view_transform.grad is not None:
+                arrays.append(("grad_world_view_transform", cam_lean.world_view_transform.grad, False))
+            dump_outputs(args.dump_outputs, arrays)
         if args.repeat_steps > 0:  # the driver's K may be small: a longer run next to it (not `value`)
             rdt, rmed = timed(lean_step, args.repeat_steps, 0, world, dist, freeze=False)
             repeat = {"steps": args.repeat_steps, "ms_per_step": round(rdt / args.repeat_steps * 1e3, 4),
@@ -871,23 +941,35 @@ def main():
         freeze_python_heap()
         for _ in range(min(args.prewarm, 8)):   # set-up: arena sizing of this rank's batches (see the N = 1 branch)
             wl.step()
-        profiler.enable(True)
-        dt, med_ms = timed(wl.step, args.steps, args.warmup, world, dist, freeze=False)
-        prof = profiler.summary()
+
+        def deblur_step():
+            last["pred"] = wl.step()
+        profiler.enable(args.full)
+        dt, med_ms = timed(deblur_step, args.steps, args.warmup, world, dist, freeze=False)
+        prof = profiler.summary() if args.full else {}
         profiler.enable(False)
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
         renders = n_units * args.steps
-        # the anchor of the scaling curve, measured in THIS run: the same 18-unit iteration with all units on one GPU (no
-        # collective), every rank on its own device, outside the timed region; efficiency(N) = value / (N x scale_anchor)
-        awl = DeblurWorkload(dev, stat, dyn, scam, args.width, args.height, SubframeShard(1, 0), args.views)
-        adt, _ = timed(awl.step, max(args.steps // 2, 3), 3, world, dist, freeze=False)
-        t = torch.tensor([adt], device=dev, dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        anchor = n_units * max(args.steps // 2, 3) / float(t.item())
-        del awl
-        scale_diag = scaling_diagnostics(wl, shard, args, dev, world, dist)
+        if args.dump_outputs and rank == 0:
+            # the all-reduced blurry predictions (the same on every rank) and the flat gradient buffers
+            pred = last["pred"]
+            arrays = [("pred", torch.stack(list(pred)) if isinstance(pred, (list, tuple)) else pred, False)]
+            buckets = wl.view_buckets if wl.view_buckets is not None else [wl.bucket]
+            arrays += [(f"grad_flat{i}", b.flat, True) for i, b in enumerate(buckets)]
+            dump_outputs(args.dump_outputs, arrays)
+        if args.full:
+            # the anchor of the scaling curve, measured in THIS run: the same 18-unit iteration with all units on one GPU
+            # (no collective), every rank on its own device, outside the timed region; efficiency(N) = value / (N x
+            # scale_anchor)
+            awl = DeblurWorkload(dev, stat, dyn, scam, args.width, args.height, SubframeShard(1, 0), args.views)
+            adt, _ = timed(awl.step, max(args.steps // 2, 3), 3, world, dist, freeze=False)
+            t = torch.tensor([adt], device=dev, dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            anchor = n_units * max(args.steps // 2, 3) / float(t.item())
+            del awl
+            scale_diag = scaling_diagnostics(wl, shard, args, dev, world, dist)
         last["out"] = next(iter(wl.mids.values())) if wl.mids else render(cam, stat, dyn, None, bg)
         from mobgs_amd import rendering
         I = rendering.last_stats.get("n_isects", 0)
@@ -930,10 +1012,10 @@ def main():
     # What the driver's 1 -> N curve must be anchored on: `value` at N = 1 is ONE lean render() per step (BASELINE's
     # metric), `value` at N > 1 counts the 18 renders of a sharded deblur iteration -- unlike quantities.  scale_anchor is
     # the N > 1 workload run on ONE GPU (renders/s): efficiency(N) = value(N) / (N x scale_anchor).
-    if world == 1:
+    if args.full and world == 1:
         result["scale_anchor"] = deblur["renders_per_s"] if deblur is not None else None
         result["scale_anchor_field"] = "deblur.renders_per_s (this line); compare value of the N > 1 lines with it, not with `value`"
-    else:
+    elif args.full:
         result["scale_anchor"] = round(anchor, 2)
         result["scale_anchor_field"] = ("the same 18-unit iteration with every unit on one GPU, timed in this run on every "
                                         "rank (slowest rank): efficiency = value / (n_gpus x scale_anchor)")
@@ -952,7 +1034,7 @@ def main():
     if small_scene is not None:
         result["reference_operating_point"] = small_scene
     if rank == 0:
-        rb = prof.get("raster_bwd")
+        rb = prof.get("raster_bwd")   # (profiled under --full only)
         if rb:
             # algorithmic bytes of raster_bwd per launch (DESIGN.md "Kernels"): per intersection 4 (id) + 64 (splat
             # record) gathered + 64 (gradient record) written; per pixel 40 (v_render) + 4 (v_alpha) + 4 (alpha)

@@ -20,8 +20,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.dirname(HERE))
 
 import ref_harness as RH  # noqa: E402
+from helpers import save_npz  # noqa: E402
 
 from mobgs_amd.camera import PinholeCamera  # noqa: E402
 from mobgs_amd.synth import SynthCamera, dynamic_extras, gaussian_cloud  # noqa: E402
@@ -94,8 +96,8 @@ def np_(t):
 def save(name, **arrays):
     arrays = {k: v for k, v in arrays.items() if v is not None}
     path = os.path.join(HERE, name + ".npz")
-    np.savez_compressed(path, **arrays)
-    print(f"wrote {path}  ({os.path.getsize(path) / 1024:.0f} KiB, {len(arrays)} arrays)")
+    files = save_npz(path, arrays)
+    print(f"wrote {', '.join(files)}  ({sum(os.path.getsize(f) for f in files) / 1024:.0f} KiB, {len(arrays)} arrays)")
 
 
 def inputs_dict(stat, dyn, cam, w2c, spc, dpc, bg):
@@ -660,6 +662,52 @@ def gen_normals(name):
                               Meta.principal_point_y, Meta.skew], dtype=np.float32))
 
 
+def gen_render_nograd(name, ns=500, nd=300, W=72, H=56, seed=21, delta=-0.2):
+    """render() under no_grad with both auxiliary sets, an exposure offset and the flow outputs: every key of the
+    result, with the names of the keys that are None."""
+    gr = RH.ref_import("gaussian_renderer")
+    scam = SynthCamera().scaled(W, H)
+    w2c = small_w2c()
+    cam = PinholeCamera(W, H, scam.K, w2c, time=0.3, max_time=scam.max_time)
+    stat, dyn = scene_params(ns, nd, scam, seed)
+    spc, dpc = ref_models(stat, dyn, seed)
+    bg = torch.zeros(9)
+    with RH.CudaToCpu(), torch.no_grad():
+        out = gr.render(cam, spc, dpc, None, bg, get_static=True, get_dynamic=True, delta_exposure=torch.tensor(delta),
+                        get_flow=True)
+    arrays = inputs_dict(stat, dyn, cam, w2c, spc, dpc, bg)
+    arrays["opt"] = np.array([1, 1, 1, delta, 1, 0], dtype=np.float64)
+    for k, v in out.items():
+        if isinstance(v, torch.Tensor):
+            arrays["out_" + k] = np_(v)
+    arrays["none_keys"] = np.array(sorted(k for k, v in out.items() if v is None), dtype=np.str_)
+    save(name, **arrays)
+
+
+def gen_init_geometry(name, B=2, H=24, W=32):
+    """scene.deformation.points_from_DRTK / inverse_warp_rt1_rt2 (train.py:101,113 import them) on random depths,
+    images and two sets of small camera motions."""
+    dm = RH.ref_import("scene.deformation")
+    g = torch.Generator().manual_seed(0)
+    depth = 1.0 + 3.0 * torch.rand(B, 1, H, W, generator=g)
+    img = torch.rand(B, 3, H, W, generator=g)
+    K = torch.tensor([[30.0, 0, W / 2], [0, 30.0, H / 2], [0, 0, 1]]).expand(B, 3, 3).contiguous()
+
+    def pose(seed):
+        q = torch.randn(B, 3, generator=torch.Generator().manual_seed(seed)) * 0.05
+        R = torch.matrix_exp(torch.stack([torch.stack([torch.zeros(()), -v[2], v[1], v[2], torch.zeros(()), -v[0], -v[1],
+                                                       v[0], torch.zeros(())]).reshape(3, 3) for v in q]))
+        t = torch.randn(B, 3, 1, generator=torch.Generator().manual_seed(seed + 1)) * 0.1
+        return torch.cat([R, t], dim=2)
+
+    w1, w2 = pose(1), pose(5)
+    with RH.CudaToCpu():
+        pts = dm.points_from_DRTK(depth, w1, K)
+        warped, grid = dm.inverse_warp_rt1_rt2(img, depth, w1, w2, K, torch.inverse(K), ret_grid=True)
+    save(name, in_depth=np_(depth), in_img=np_(img), in_K=np_(K), in_w1=np_(w1), in_w2=np_(w2), out_pts=np_(pts),
+         out_img=np_(warped), out_grid=np_(grid))
+
+
 def main():
     RH.install()
     gen_hermite("hermite")
@@ -676,6 +724,8 @@ def main():
     gen_losses("losses")
     gen_densify("densify")
     gen_normals("normals")
+    gen_render_nograd("render_nograd")
+    gen_init_geometry("init_geometry")
 
 
 if __name__ == "__main__":

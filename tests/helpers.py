@@ -14,8 +14,65 @@ STAT_KEYS = ["xyz", "scaling", "rotation", "opacity", "features_dc", "features_t
 DYN_KEYS = ["omega", "trbf_center", "control_xyz", "current_control_num"]
 
 
+PART_BYTES = 900 * 1024  # raw array bytes per fixture file: every stored file stays below 1 MiB
+
+
+def save_npz(path, arrays):
+    """np.savez_compressed(path, **arrays) split over `path` and <path without .npz>.<i>.npz, each holding at most
+    PART_BYTES of raw array data.  An array larger than that is stored flat in pieces "<key>@<j>" next to its shape
+    "<key>@shape".  -> the files written (stale higher-numbered parts are removed)."""
+    pieces = {}
+    for k, a in arrays.items():
+        a = np.asarray(a)
+        if a.nbytes <= PART_BYTES:
+            pieces[k] = a
+            continue
+        flat, step = a.reshape(-1), max(1, PART_BYTES // a.itemsize)
+        for j in range(0, flat.size, step):
+            pieces[f"{k}@{j // step}"] = flat[j:j + step]
+        pieces[k + "@shape"] = np.array(a.shape, dtype=np.int64)
+    parts, size = [{}], 0
+    for k, a in pieces.items():
+        if parts[-1] and size + a.nbytes > PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][k] = a
+        size += a.nbytes
+    base = path[:-len(".npz")]
+    files = [path] + [f"{base}.{i}.npz" for i in range(1, len(parts))]
+    for f, p in zip(files, parts):
+        np.savez_compressed(f, **p)
+    i = len(parts)
+    while os.path.exists(f"{base}.{i}.npz"):
+        os.remove(f"{base}.{i}.npz")
+        i += 1
+    return files
+
+
+def load_npz(path):
+    """What save_npz stored, as {key: array} in the original key order."""
+    base = path[:-len(".npz")]
+    stored = dict(np.load(path))
+    i = 1
+    while os.path.exists(f"{base}.{i}.npz"):
+        stored.update(np.load(f"{base}.{i}.npz"))
+        i += 1
+    out = {}
+    for k, a in stored.items():
+        if "@" not in k:
+            out[k] = a
+        elif k.endswith("@0"):
+            name = k[:-2]
+            chunks, j = [], 0
+            while f"{name}@{j}" in stored:
+                chunks.append(stored[f"{name}@{j}"])
+                j += 1
+            out[name] = np.concatenate(chunks).reshape(tuple(stored[name + "@shape"]))
+    return out
+
+
 def load(name):
-    return dict(np.load(os.path.join(GOLDEN, name + ".npz")))
+    return load_npz(os.path.join(GOLDEN, name + ".npz"))
 
 
 def scene_from_fixture(fx, device="cpu", requires_grad=True):

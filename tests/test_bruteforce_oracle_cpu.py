@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import close, close_image_with_blend_flips
+from helpers import close, close_image_with_blend_flips, load_npz, save_npz
 from mobgs_amd.synth import SynthCamera, splat_inputs
 
 NAMES = ["means", "quats", "scales", "opacities", "colors"]
@@ -46,12 +46,12 @@ _META = ("radii", "means2d", "conics", "depths")
 
 def save_reference(ref, path=REF_FILE):
     img, a, meta, g = ref
-    np.savez_compressed(path, img=img.numpy(), alpha=a.numpy(), **{"meta_" + k: meta[k].detach().numpy() for k in _META},
-                        **{"grad_" + k: v.numpy() for k, v in g.items()})
+    save_npz(path, dict(img=img.numpy(), alpha=a.numpy(), **{"meta_" + k: meta[k].detach().numpy() for k in _META},
+                        **{"grad_" + k: v.numpy() for k, v in g.items()}))
 
 
 def load_reference(path=REF_FILE):
-    z = np.load(path)
+    z = load_npz(path)
     meta = {k: torch.from_numpy(z["meta_" + k]) for k in _META}
     return (torch.from_numpy(z["img"]), torch.from_numpy(z["alpha"]), meta,
             {k: torch.from_numpy(z["grad_" + k]) for k in NAMES})

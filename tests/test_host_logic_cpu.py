@@ -108,33 +108,15 @@ def test_ply_reader_handles_ascii_and_mixed_property_types(tmp_path):
     assert names == ["x", "n", "c"] and np.allclose(rows, [[0.5, -3, 9], [2.0, 4, 250]])
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/scene"), reason="reference tree not present")
 def test_init_geometry_helpers_match_reference_live():
-    """points_from_DRTK / inverse_warp_rt1_rt2 (train.py:101,113 import them from scene.deformation) against the
-    reference's own functions, run in place."""
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
-    import ref_harness as RH
+    """points_from_DRTK / inverse_warp_rt1_rt2 (train.py:101,113 import them from scene.deformation) against what the
+    reference's own functions return on the same inputs (tests/golden/init_geometry.npz, make_golden.py:gen_init_geometry)."""
     import torch
+    from helpers import load
     from mobgs_amd import deformation as D
-    dm = RH.ref_import("scene.deformation")
-    g = torch.Generator().manual_seed(0)
-    B, H, W = 2, 24, 32
-    depth = 1.0 + 3.0 * torch.rand(B, 1, H, W, generator=g)
-    img = torch.rand(B, 3, H, W, generator=g)
-    K = torch.tensor([[30.0, 0, W / 2], [0, 30.0, H / 2], [0, 0, 1]]).expand(B, 3, 3).contiguous()
-
-    def pose(seed):
-        q = torch.randn(B, 3, generator=torch.Generator().manual_seed(seed)) * 0.05
-        R = torch.matrix_exp(torch.stack([torch.stack([torch.zeros(()), -v[2], v[1], v[2], torch.zeros(()), -v[0], -v[1],
-                                                       v[0], torch.zeros(())]).reshape(3, 3) for v in q]))
-        t = torch.randn(B, 3, 1, generator=torch.Generator().manual_seed(seed + 1)) * 0.1
-        return torch.cat([R, t], dim=2)
-
-    w1, w2 = pose(1), pose(5)
-    with RH.CudaToCpu():
-        ref_pts = dm.points_from_DRTK(depth, w1, K)
-        ref_img, ref_grid = dm.inverse_warp_rt1_rt2(img, depth, w1, w2, K, torch.inverse(K), ret_grid=True)
+    fx = load("init_geometry")
+    depth, img, K, w1, w2 = (torch.from_numpy(fx["in_" + k]) for k in ("depth", "img", "K", "w1", "w2"))
+    ref_pts, ref_img, ref_grid = (torch.from_numpy(fx["out_" + k]) for k in ("pts", "img", "grid"))
     assert torch.allclose(D.points_from_DRTK(depth, w1, K), ref_pts, atol=1e-5)
     out, grid = D.inverse_warp_rt1_rt2(img, depth, w1, w2, K, torch.inverse(K), ret_grid=True)
     assert torch.allclose(grid, ref_grid, atol=1e-5) and torch.allclose(out, ref_img, atol=1e-5)
@@ -252,3 +234,15 @@ def test_hints_are_kept_per_scene_and_per_thread():
         assert R._workload_key(dev, 1, 300000, 1352, 1014) == k1    # the other thread's scope did not leak into this one
     assert k1[0] == t1 and seen["k2"][0] == t2 and seen["outside"][0] == 0 and k1[1:] == seen["k2"][1:]
     assert R._workload_key(dev, 1, 300000, 1352, 1014)[0] == 0      # outside any scope: the operator API's shared entry
+
+
+def test_bench_refuses_full_only_options_without_full():
+    """A plain bench.py run measures the headline alone: an option of what only --full measures (a secondary leg's
+    step count, --cpu-reps, --pmc) is refused before any work instead of yielding a line that silently lacks it;
+    zero counts and the --no-* switches are fine."""
+    import subprocess
+    import sys
+    bench = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py")
+    for extra in (["--deblur-steps", "10"], ["--flow-steps", "6"], ["--cpu-reps", "3"], ["--pmc"]):
+        r = subprocess.run([sys.executable, bench, "--steps", "2", *extra], capture_output=True, text=True, timeout=300)
+        assert r.returncode != 0 and "--full" in r.stderr and extra[0] in r.stderr, (extra, r.stderr[-500:])

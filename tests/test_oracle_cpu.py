@@ -265,26 +265,17 @@ def test_get_flow_gradients_of_the_restatement_match_reference_fixture():
                      lambda a, b, c, s, d, bg: R.get_flow_static(a, b, c, s), "cpu", 1e-4, 1e-5)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/gaussian_renderer"), reason="reference tree not present")
 def test_render_restatement_matches_reference_live():
-    """When /root/reference is present (build container), run its render() directly on a fresh scene."""
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
-    import ref_harness as RH
-    from make_golden import ref_models, scene_params, small_w2c
-    from mobgs_amd.camera import PinholeCamera
-    gr = RH.ref_import("gaussian_renderer")
-    W, H = 72, 56
-    scam = SynthCamera().scaled(W, H)
-    cam = PinholeCamera(W, H, scam.K, small_w2c(), time=0.3, max_time=scam.max_time)
-    stat_p, dyn_p = scene_params(500, 300, scam, 21)
-    spc, dpc = ref_models(stat_p, dyn_p, 21)
-    bg = torch.zeros(9)
-    with RH.CudaToCpu(), torch.no_grad():
-        ref = gr.render(cam, spc, dpc, None, bg, get_static=True, get_dynamic=True,
-                        delta_exposure=torch.tensor(-0.2), get_flow=True)
-        mine = R.render(cam, spc, dpc, bg, get_static=True, get_dynamic=True, delta_exposure=torch.tensor(-0.2),
+    """The reference's own render() under no_grad on a fresh scene (both auxiliary sets, an exposure offset, the flow
+    outputs: tests/golden/render_nograd.npz, make_golden.py:gen_render_nograd) against the restatement: every key."""
+    fx = load("render_nograd")
+    cam, stat, dyn, bg, _ = scene_from_fixture(fx)
+    _, _, _, delta, _, _ = fx["opt"]
+    with torch.no_grad():
+        mine = R.render(cam, stat, dyn, bg, get_static=True, get_dynamic=True, delta_exposure=torch.tensor(float(delta)),
                         get_flow=True)
+    ref = {k[4:]: torch.from_numpy(v) for k, v in fx.items() if k.startswith("out_")}
+    ref.update({str(k): None for k in fx["none_keys"]})
     assert set(ref.keys()) == set(mine.keys())
     for k, v in ref.items():
         if isinstance(v, torch.Tensor):
