@@ -1989,8 +1989,10 @@ int mobgs_raster_channels_supported(int D) {
 int mobgs_raster_path(int total_channels, int class_filter, int n_tiles, const MobgsTuning* tuning) {
     const int D = total_channels;
     int bwd = 0;
-    if (!class_filter && tuning_bwd_block_walk(tuning) && D >= 7 && D <= 10) {
-        bwd = 3;
+    // a plain pass under bwd_block_walk never takes the matrix pipe: counts without a block-walk build run the quadrant
+    // kernel (raster_bwd_impl skips raster_bwd_mfma_launch whenever bwd_block_walk is set)
+    if (!class_filter && tuning_bwd_block_walk(tuning)) {
+        if (D >= 7 && D <= 10) bwd = 3;
     } else if (tuning_bwd_mfma(tuning, n_tiles)) {
         const bool has = class_filter ? (D == 1 || D == 10) : (D == 1 || D == 3 || D == 4 || D == 9 || D == 10);
         if (has) bwd = tuning_bwd_mfma(tuning, n_tiles);

@@ -995,6 +995,7 @@ class _RasterizeClassAlpha(torch.autograd.Function):
                   "mobgs_raster_class_fwd")
             if tl.defer or not tl.resolve():
                 break
+        _log_path("fwd", 1, tl, class_filter=True, decode=False)
         ctx.save_for_backward(records, radii, alphas, last, reach, bg)
         ctx.tl, ctx.arena = tl, tl.flatten_arena
         ctx.gate = _zero_gate[0]
@@ -1023,6 +1024,7 @@ class _RasterizeClassAlpha(torch.autograd.Function):
             v_render, v_a = _zero_image(C, height, width, dev), f32c(v_alphas)
         else:            # ... to the 1-channel render output (background folded in by the kernel)
             v_render, v_a = f32c(v_alphas).reshape(C, height, width, 1), None
+        _log_path("bwd", 1, tl, class_filter=True, tn=tn)
         check(lib.mobgs_raster_class_bwd(C, N, Ns, class_sel, 1, width, height, ptr(records), ptr(bg), ptr(radii),
                                          ptr(tl.cum_tiles), ptr(tl.keep_scan), ptr(tl.tile_offsets),
                                          ptr(tl.tile_order), ptr(tl.flatten_ids), ptr(alphas), ptr(last),
