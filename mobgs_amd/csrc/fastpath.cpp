@@ -37,7 +37,6 @@ struct Api {
     decltype(&mobgs_raster_bwd) raster_bwd = nullptr;
     decltype(&mobgs_raster_bwd_decode) raster_bwd_decode = nullptr;
     decltype(&mobgs_raster_bwd_decode_scratch_floats) raster_bwd_decode_scratch_floats = nullptr;
-    decltype(&mobgs_raster_bwd_decode_finish) raster_bwd_decode_finish = nullptr;
     decltype(&mobgs_raster_bwd_reduce_decode) raster_bwd_reduce_decode = nullptr;
     decltype(&mobgs_raster_bwd_reduce) raster_bwd_reduce = nullptr;
     decltype(&mobgs_decoder_fwd_channels) decoder_fwd = nullptr;
@@ -83,7 +82,6 @@ void bind(const std::unordered_map<std::string, uint64_t>& m) {
     take(m, "mobgs_raster_bwd", api.raster_bwd);
     take(m, "mobgs_raster_bwd_decode", api.raster_bwd_decode);
     take(m, "mobgs_raster_bwd_decode_scratch_floats", api.raster_bwd_decode_scratch_floats);
-    take(m, "mobgs_raster_bwd_decode_finish", api.raster_bwd_decode_finish);
     take(m, "mobgs_raster_bwd_reduce_decode", api.raster_bwd_reduce_decode);
     take(m, "mobgs_raster_bwd_reduce", api.raster_bwd_reduce);
     take(m, "mobgs_decoder_fwd_channels", api.decoder_fwd);
@@ -310,24 +308,6 @@ raster_bwd_decode(int64_t C, int64_t N, int64_t width, int64_t height, int64_t n
                                 fpw(partial), tp(tuning), sp(stream)),
           "mobgs_raster_bwd_decode");
     return {slots, partial};
-}
-
-// ... and the fixed-order sum of its partial rows (mobgs_raster_bwd_decode_finish): -> (g_c2w | None, g_w1, g_w2);
-// g_w1 / g_w2: a sink's buffers (accumulate as given) or None -> allocated here and overwritten.
-std::tuple<OptT, Tensor, Tensor>
-raster_bwd_decode_finish(int64_t C, int64_t width, int64_t height, const Tensor& partial, const Tensor& c2w, const Tensor& w1,
-                         const Tensor& w2, bool c2w_needs_grad, const OptT& g_w1_in, const OptT& g_w2_in, int64_t accumulate,
-                         int64_t stream) {
-    const bool sunk = g_w1_in.has_value() && g_w1_in->defined();
-    Tensor g_w1 = sunk ? *g_w1_in : at::empty_like(w1);
-    Tensor g_w2 = sunk ? *g_w2_in : at::empty_like(w2);
-    OptT g_c2w = c2w_needs_grad ? OptT(at::empty_like(c2w)) : OptT();
-    const int64_t c2w_stride = (C > 1 && c2w.dim() == 3) ? c2w.numel() / C : 0;
-    check(api.raster_bwd_decode_finish((int)C, (int)width, (int)height, fpw(partial), (int)c2w_stride, fpw(g_w1), fpw(g_w2),
-                                       fpw(g_c2w), g_c2w.has_value() ? (int)(g_c2w->numel() / (c2w_stride ? C : 1)) : 0,
-                                       sunk ? (int)accumulate : 0, sp(stream)),
-          "mobgs_raster_bwd_decode_finish");
-    return {g_c2w, g_w1, g_w2};
 }
 
 // raster_bwd_reduce + raster_bwd_decode_finish in one launch (mobgs_raster_bwd_reduce_decode):
@@ -620,7 +600,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("raster_fwd", &raster_fwd);
     m.def("raster_bwd", &raster_bwd);
     m.def("raster_bwd_decode", &raster_bwd_decode);
-    m.def("raster_bwd_decode_finish", &raster_bwd_decode_finish);
     m.def("raster_bwd_reduce_decode", &raster_bwd_reduce_decode);
     m.def("raster_bwd_reduce", &raster_bwd_reduce);
     m.def("decoder_fwd", &decoder_fwd);

@@ -177,59 +177,68 @@ class PrepSplats(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, v_means, v_quats, v_scales, v_opac, v_colors):
-        lib = _lib.load()
-        times, d_ncp, d_trbf, scales, opac = ctx.saved_tensors
-        Ns, Nd = ctx.sizes
-        dev = times.device
+        return prep_backward(ctx.saved_tensors, ctx.sizes, ctx.leaf_inputs, ctx.half, ctx.attr_dtypes, v_means, v_quats,
+                             v_scales, v_opac, v_colors)
 
-        sink = _active_sink
-        use_sink = sink is not None and getattr(ctx, "leaf_inputs", None) is not None and sink.accepts(ctx.leaf_inputs)
-        # attribute gradients: fp32 in the sink's accumulation buffers (cast once when the context exits), otherwise
-        # the dtype of the leaves (half leaves need half .grad tensors: written as such by the kernel)
-        g_half = ctx.half and not use_sink
 
-        def E(*shape, attr=False):
-            return torch.empty(*shape, dtype=torch.float16 if (attr and g_half) else torch.float32, device=dev)
+def prep_backward(saved, sizes, leaf_inputs, half, attr_dtypes, v_means, v_quats, v_scales, v_opac, v_colors):
+    """PrepSplats.backward on explicit state (rendering._PrepProjectAndBin runs it on its own): saved = (times, d_ncp,
+    d_trbf, scales, opac); sizes = (Ns, Nd); leaf_inputs: the caller's 13 leaf tensor objects (for a LeafGradSink) or None;
+    half: the attribute leaves are float16; attr_dtypes: the 11 attribute leaves' dtypes, gradients are cast back to the
+    ones that are not float32 (() = none).  -> the 16 input gradients of PrepSplats.forward."""
+    lib = _lib.load()
+    times, d_ncp, d_trbf, scales, opac = saved
+    Ns, Nd = sizes
+    dev = times.device
 
-        accumulate = 0
-        F = _fast.get()
-        if F is not None:
-            have = use_sink and sink.buffers is not None
-            out = F.prep_bwd(Ns, Nd, times, d_ncp, d_trbf, scales, opac, v_means, v_quats, v_scales, v_opac, v_colors,
-                             [sink.buffers[n_] for n_ in _LEAF_NAMES] if have else [], g_half, 1 if have else 0,
-                             stream_int())
-            g = sink.buffers if have else dict(zip(_LEAF_NAMES, out))
-            if use_sink:
-                sink.buffers = g
-        elif use_sink and sink.buffers is not None:
-            g, accumulate = sink.buffers, 1
-        else:
-            g = {"s_xyz": E(Ns, 3), "s_scaling": E(Ns, 3, attr=True), "s_rotation": E(Ns, 4, attr=True),
-                 "s_opacity": E(Ns, 1, attr=True), "s_fdc": E(Ns, 6, attr=True), "s_ft": E(Ns, 3, attr=True),
-                 "d_control": E(Nd, 12, 3), "d_scaling": E(Nd, 3, attr=True), "d_rotation": E(Nd, 4, attr=True),
-                 "d_omega": E(Nd, 4, attr=True), "d_opacity": E(Nd, 1, attr=True), "d_fdc": E(Nd, 6, attr=True),
-                 "d_ft": E(Nd, 3, attr=True)}
-            if use_sink:
-                sink.buffers = g
-        if F is None:
-            c = [f32c(v) if v is not None else None for v in (v_means, v_quats, v_scales, v_opac, v_colors)]
-            bwd = lib.mobgs_prep_bwd_many_f16 if g_half else lib.mobgs_prep_bwd_many
-            check(bwd(times.shape[0] if times.dim() == 2 else 1, Ns, Nd, ptr(times), ptr(d_ncp), ptr(d_trbf), ptr(scales), ptr(opac), ptr(c[0]), ptr(c[1]),
-                      ptr(c[2]), ptr(c[3]), ptr(c[4]), ptr(g["s_xyz"]), ptr(g["s_scaling"]), ptr(g["s_rotation"]),
-                      ptr(g["s_opacity"]), ptr(g["s_fdc"]), ptr(g["s_ft"]), ptr(g["d_control"]), ptr(g["d_scaling"]),
-                      ptr(g["d_rotation"]), ptr(g["d_omega"]), ptr(g["d_opacity"]), ptr(g["d_fdc"]), ptr(g["d_ft"]),
-                      accumulate, stream()), "mobgs_prep_bwd")
-        if not use_sink and not g_half:  # mixed / other dtypes: autograd wants the leaf's dtype back
-            names = ("s_scaling", "s_rotation", "s_opacity", "s_fdc", "s_ft", "d_scaling", "d_rotation", "d_omega",
-                     "d_opacity", "d_fdc", "d_ft")
-            for n_, dt in zip(names, ctx.attr_dtypes):
-                if dt != torch.float32:
-                    g[n_] = g[n_].to(dt)
+    sink = _active_sink
+    use_sink = sink is not None and leaf_inputs is not None and sink.accepts(leaf_inputs)
+    # attribute gradients: fp32 in the sink's accumulation buffers (cast once when the context exits), otherwise
+    # the dtype of the leaves (half leaves need half .grad tensors: written as such by the kernel)
+    g_half = half and not use_sink
+
+    def E(*shape, attr=False):
+        return torch.empty(*shape, dtype=torch.float16 if (attr and g_half) else torch.float32, device=dev)
+
+    accumulate = 0
+    F = _fast.get()
+    if F is not None:
+        have = use_sink and sink.buffers is not None
+        out = F.prep_bwd(Ns, Nd, times, d_ncp, d_trbf, scales, opac, v_means, v_quats, v_scales, v_opac, v_colors,
+                         [sink.buffers[n_] for n_ in _LEAF_NAMES] if have else [], g_half, 1 if have else 0,
+                         stream_int())
+        g = sink.buffers if have else dict(zip(_LEAF_NAMES, out))
         if use_sink:
-            return (None,) * 16
-        return (None, g["s_xyz"], g["s_scaling"], g["s_rotation"], g["s_opacity"], g["s_fdc"], g["s_ft"],
-                g["d_control"], None, g["d_scaling"], g["d_rotation"], g["d_omega"], g["d_opacity"], g["d_fdc"],
-                g["d_ft"], None)
+            sink.buffers = g
+    elif use_sink and sink.buffers is not None:
+        g, accumulate = sink.buffers, 1
+    else:
+        g = {"s_xyz": E(Ns, 3), "s_scaling": E(Ns, 3, attr=True), "s_rotation": E(Ns, 4, attr=True),
+             "s_opacity": E(Ns, 1, attr=True), "s_fdc": E(Ns, 6, attr=True), "s_ft": E(Ns, 3, attr=True),
+             "d_control": E(Nd, 12, 3), "d_scaling": E(Nd, 3, attr=True), "d_rotation": E(Nd, 4, attr=True),
+             "d_omega": E(Nd, 4, attr=True), "d_opacity": E(Nd, 1, attr=True), "d_fdc": E(Nd, 6, attr=True),
+             "d_ft": E(Nd, 3, attr=True)}
+        if use_sink:
+            sink.buffers = g
+    if F is None:
+        c = [f32c(v) if v is not None else None for v in (v_means, v_quats, v_scales, v_opac, v_colors)]
+        bwd = lib.mobgs_prep_bwd_many_f16 if g_half else lib.mobgs_prep_bwd_many
+        check(bwd(times.shape[0] if times.dim() == 2 else 1, Ns, Nd, ptr(times), ptr(d_ncp), ptr(d_trbf), ptr(scales), ptr(opac), ptr(c[0]), ptr(c[1]),
+                  ptr(c[2]), ptr(c[3]), ptr(c[4]), ptr(g["s_xyz"]), ptr(g["s_scaling"]), ptr(g["s_rotation"]),
+                  ptr(g["s_opacity"]), ptr(g["s_fdc"]), ptr(g["s_ft"]), ptr(g["d_control"]), ptr(g["d_scaling"]),
+                  ptr(g["d_rotation"]), ptr(g["d_omega"]), ptr(g["d_opacity"]), ptr(g["d_fdc"]), ptr(g["d_ft"]),
+                  accumulate, stream()), "mobgs_prep_bwd")
+    if not use_sink and not g_half:  # mixed / other dtypes: autograd wants the leaf's dtype back
+        names = ("s_scaling", "s_rotation", "s_opacity", "s_fdc", "s_ft", "d_scaling", "d_rotation", "d_omega",
+                 "d_opacity", "d_fdc", "d_ft")
+        for n_, dt in zip(names, attr_dtypes):
+            if dt != torch.float32:
+                g[n_] = g[n_].to(dt)
+    if use_sink:
+        return (None,) * 16
+    return (None, g["s_xyz"], g["s_scaling"], g["s_rotation"], g["s_opacity"], g["s_fdc"], g["s_ft"],
+            g["d_control"], None, g["d_scaling"], g["d_rotation"], g["d_omega"], g["d_opacity"], g["d_fdc"],
+            g["d_ft"], None)
 
 
 def _decoder_strides(C, P, rays, intr, c2w):
@@ -298,50 +307,58 @@ class Decode(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, v_rgb, v_depth, _v_chan=None, _chan_c0=0):
-        """_v_chan / _chan_c0 (DecodeWithChannels, host fast path): the cotangent of the channels handed out by forward;
-        the kernel writes it into those channels of the image's gradient."""
-        lib = _lib.load()
-        feat_hw, alphas, rays, intr, c2w, w1, w2 = ctx.saved_tensors
-        if v_rgb is None and v_depth is None:
-            return (None,) * 10
-        H, W, CF = feat_hw.shape[-3:]
-        P = H * W
-        dev = feat_hw.device
-        has_depth = ctx.has_depth
-        sunk = _active_sink.decoder_buffers(*ctx.w_inputs) if _active_sink is not None else None
-        F = _fast.get()
-        if F is not None:
-            v_feat, v_alphas, v_rays, g_c2w, g_w1, g_w2 = F.decoder_bwd(
-                H, W, CF, bool(has_depth), feat_hw, alphas, rays, intr, c2w, w1, w2, v_rgb, v_depth,
-                list(ctx.feat_shape), bool(ctx.rays_need_grad), bool(ctx.c2w_needs_grad),
-                sunk[0] if sunk is not None else None, sunk[1] if sunk is not None else None,
-                sunk[2] if sunk is not None else 0, stream_int(), _v_chan, int(_chan_c0))
-            if sunk is not None:
-                return v_feat, v_alphas, v_rays, None, g_c2w, None, None, None, None, None
-            return v_feat, v_alphas, v_rays, None, g_c2w, g_w1, g_w2, None, None, None
-        C = feat_hw.numel() // (P * CF)
-        v_rgb = f32c(v_rgb) if v_rgb is not None else torch.zeros(C, 3, H, W, dtype=torch.float32, device=dev)
-        v_depth = f32c(v_depth) if (has_depth and v_depth is not None) else None
-        v_feat = torch.empty(ctx.feat_shape, dtype=torch.float32, device=dev)
-        v_alphas = torch.empty(alphas.shape, dtype=torch.float32, device=dev) if has_depth else None
-        v_rays = torch.empty_like(rays) if ctx.rays_need_grad else None
-        g_c2w = torch.empty_like(c2w) if ctx.c2w_needs_grad else None  # [3,4] or [4,4] (per image) like the input
-        nb = lib.mobgs_decoder_bwd_blocks(P)
-        partial = torch.empty(C * nb, 102, dtype=torch.float32, device=dev)
-        if sunk is not None:
-            g_w1, g_w2, accumulate = sunk
-        else:
-            g_w1, g_w2, accumulate = torch.empty_like(w1), torch.empty_like(w2), 0
-        rs, is_, cs = _decoder_strides(C, P, rays, intr, c2w)
-        check(lib.mobgs_decoder_bwd_many(C, P, CF, int(has_depth), W, ptr(feat_hw), ptr(alphas), ptr(rays), rs,
-                                         ptr(intr), is_, ptr(c2w), cs, ptr(w1), ptr(w2), ptr(v_rgb), ptr(v_depth),
-                                         ptr(v_feat), ptr(v_alphas), ptr(v_rays), ptr(partial), ptr(g_w1), ptr(g_w2),
-                                         ptr(g_c2w), (g_c2w.numel() // (C if cs else 1)) if g_c2w is not None else 0,
-                                         accumulate, stream()),
-              "mobgs_decoder_bwd")
+        return decode_backward(ctx.saved_tensors, ctx.has_depth, ctx.w_inputs, ctx.feat_shape, ctx.rays_need_grad,
+                               ctx.c2w_needs_grad, v_rgb, v_depth, _v_chan, _chan_c0)
+
+
+def decode_backward(saved, has_depth, w_inputs, feat_shape, rays_need_grad, c2w_needs_grad, v_rgb, v_depth, v_chan=None,
+                    chan_c0=0):
+    """Decode.backward on explicit state (rendering._Rasterize runs it on the decoder inputs IT saved): saved = (feat_hw,
+    alphas, rays, intr, c2w, w1, w2) as Decode.forward saves them; w_inputs: the caller's weight tensor objects (for a
+    LeafGradSink).  v_chan / chan_c0 (DecodeWithChannels, host fast path): the cotangent of the channels handed out by
+    forward; the kernel writes it into those channels of the image's gradient.  -> the 10 input gradients of
+    Decode.forward."""
+    lib = _lib.load()
+    feat_hw, alphas, rays, intr, c2w, w1, w2 = saved
+    if v_rgb is None and v_depth is None:
+        return (None,) * 10
+    H, W, CF = feat_hw.shape[-3:]
+    P = H * W
+    dev = feat_hw.device
+    sunk = _active_sink.decoder_buffers(*w_inputs) if _active_sink is not None else None
+    F = _fast.get()
+    if F is not None:
+        v_feat, v_alphas, v_rays, g_c2w, g_w1, g_w2 = F.decoder_bwd(
+            H, W, CF, bool(has_depth), feat_hw, alphas, rays, intr, c2w, w1, w2, v_rgb, v_depth,
+            list(feat_shape), bool(rays_need_grad), bool(c2w_needs_grad),
+            sunk[0] if sunk is not None else None, sunk[1] if sunk is not None else None,
+            sunk[2] if sunk is not None else 0, stream_int(), v_chan, int(chan_c0))
         if sunk is not None:
             return v_feat, v_alphas, v_rays, None, g_c2w, None, None, None, None, None
         return v_feat, v_alphas, v_rays, None, g_c2w, g_w1, g_w2, None, None, None
+    C = feat_hw.numel() // (P * CF)
+    v_rgb = f32c(v_rgb) if v_rgb is not None else torch.zeros(C, 3, H, W, dtype=torch.float32, device=dev)
+    v_depth = f32c(v_depth) if (has_depth and v_depth is not None) else None
+    v_feat = torch.empty(feat_shape, dtype=torch.float32, device=dev)
+    v_alphas = torch.empty(alphas.shape, dtype=torch.float32, device=dev) if has_depth else None
+    v_rays = torch.empty_like(rays) if rays_need_grad else None
+    g_c2w = torch.empty_like(c2w) if c2w_needs_grad else None  # [3,4] or [4,4] (per image) like the input
+    nb = lib.mobgs_decoder_bwd_blocks(P)
+    partial = torch.empty(C * nb, 102, dtype=torch.float32, device=dev)
+    if sunk is not None:
+        g_w1, g_w2, accumulate = sunk
+    else:
+        g_w1, g_w2, accumulate = torch.empty_like(w1), torch.empty_like(w2), 0
+    rs, is_, cs = _decoder_strides(C, P, rays, intr, c2w)
+    check(lib.mobgs_decoder_bwd_many(C, P, CF, int(has_depth), W, ptr(feat_hw), ptr(alphas), ptr(rays), rs,
+                                     ptr(intr), is_, ptr(c2w), cs, ptr(w1), ptr(w2), ptr(v_rgb), ptr(v_depth),
+                                     ptr(v_feat), ptr(v_alphas), ptr(v_rays), ptr(partial), ptr(g_w1), ptr(g_w2),
+                                     ptr(g_c2w), (g_c2w.numel() // (C if cs else 1)) if g_c2w is not None else 0,
+                                     accumulate, stream()),
+          "mobgs_decoder_bwd")
+    if sunk is not None:
+        return v_feat, v_alphas, v_rays, None, g_c2w, None, None, None, None, None
+    return v_feat, v_alphas, v_rays, None, g_c2w, g_w1, g_w2, None, None, None
 
 
 class DecodeWithChannels(torch.autograd.Function):

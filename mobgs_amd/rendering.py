@@ -17,7 +17,7 @@ from typing import Dict, Optional, Tuple
 import torch
 from torch import Tensor
 
-from . import _fast, _lib, profiler
+from . import _fast, _lib, ops, profiler
 from ._lib import DerivedCache, check, f32c, ptr, stream, stream_int
 
 TILE = 16
@@ -55,30 +55,35 @@ class _Project(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, _v_radii, v_means2d, v_depths, v_conics, _v_tpg):
-        lib = _lib_()
-        means, quats, scales, viewmats, Ks, radii, conics = ctx.saved_tensors
-        width, height, eps2d = ctx.dims
-        F = _fast.get()
-        if F is not None:  # the same body in C++ (csrc/fastpath.cpp)
-            v_means, v_quats, v_scales, v_viewmats = F.project_bwd(width, height, eps2d, means, quats, scales,
-                                                                   viewmats, Ks, radii, conics, v_means2d, v_depths,
-                                                                   v_conics, stream_int())
-            return v_means, v_quats, v_scales, v_viewmats, None, None, None, None, None, None, None
-        C, N = viewmats.shape[0], means.shape[-2]
-        dev = means.device
-        v_means = torch.empty_like(means)
-        v_quats = torch.empty_like(quats)
-        v_scales = torch.empty_like(scales)
-        v_viewmats = torch.empty_like(viewmats)
-        partial = torch.empty(lib.mobgs_project_bwd_scratch_floats(C, N), dtype=torch.float32, device=dev)
-        g2 = f32c(v_means2d) if v_means2d is not None else None
-        gd = f32c(v_depths) if v_depths is not None else None
-        gc = f32c(v_conics) if v_conics is not None else None
-        check(lib.mobgs_project_bwd_ex(C, N, 1 if means.dim() == 3 else 0, ptr(means), ptr(quats), ptr(scales),
-                                       ptr(viewmats), ptr(Ks), width, height, eps2d, ptr(radii), ptr(conics), ptr(g2),
-                                       ptr(gd), ptr(gc), ptr(v_means), ptr(v_quats), ptr(v_scales), ptr(v_viewmats),
-                                       ptr(partial), stream()), "mobgs_project_bwd")
-        return v_means, v_quats, v_scales, v_viewmats, None, None, None, None, None, None, None
+        return (*_project_bwd(ctx.saved_tensors, ctx.dims, v_means2d, v_depths, v_conics), None, None, None, None, None, None,
+                None)
+
+
+def _project_bwd(saved, dims, v_means2d, v_depths, v_conics):
+    """The projection's backward pass on what _Project.forward (and the binning nodes' forwards) save: saved = (means, quats,
+    scales, viewmats, Ks, radii, conics), dims = (width, height, eps2d).  -> (v_means, v_quats, v_scales, v_viewmats)."""
+    lib = _lib_()
+    means, quats, scales, viewmats, Ks, radii, conics = saved
+    width, height, eps2d = dims
+    F = _fast.get()
+    if F is not None:  # the same body in C++ (csrc/fastpath.cpp)
+        return F.project_bwd(width, height, eps2d, means, quats, scales, viewmats, Ks, radii, conics, v_means2d, v_depths,
+                             v_conics, stream_int())
+    C, N = viewmats.shape[0], means.shape[-2]
+    dev = means.device
+    v_means = torch.empty_like(means)
+    v_quats = torch.empty_like(quats)
+    v_scales = torch.empty_like(scales)
+    v_viewmats = torch.empty_like(viewmats)
+    partial = torch.empty(lib.mobgs_project_bwd_scratch_floats(C, N), dtype=torch.float32, device=dev)
+    g2 = f32c(v_means2d) if v_means2d is not None else None
+    gd = f32c(v_depths) if v_depths is not None else None
+    gc = f32c(v_conics) if v_conics is not None else None
+    check(lib.mobgs_project_bwd_ex(C, N, 1 if means.dim() == 3 else 0, ptr(means), ptr(quats), ptr(scales),
+                                   ptr(viewmats), ptr(Ks), width, height, eps2d, ptr(radii), ptr(conics), ptr(g2),
+                                   ptr(gd), ptr(gc), ptr(v_means), ptr(v_quats), ptr(v_scales), ptr(v_viewmats),
+                                   ptr(partial), stream()), "mobgs_project_bwd")
+    return v_means, v_quats, v_scales, v_viewmats
 
 
 def fully_fused_projection(
@@ -668,8 +673,248 @@ def _pad_channels(D: int) -> int:
     raise NotImplementedError(f"mobgs_amd: {D} colour channels exceed the compiled maximum ({_SUPPORTED[-1]})")
 
 
+_const_cache = {}
+
+
+def _const(make, *shape, dev):
+    """A float32 constant (make = torch.ones | torch.zeros) that kernels only read: built once per shape and device."""
+    key = (make, shape, str(dev))
+    t = _const_cache.get(key)
+    if t is None:
+        if len(_const_cache) > 16:
+            _const_cache.clear()
+        t = _const_cache[key] = make(*shape, dtype=torch.float32, device=dev)
+    return t
+
+
+def _ptr3(tensors):
+    return (ctypes.c_void_p * 3)(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+# -- one host body per launch: the fast-path arm (csrc/fastpath.cpp, where it has one) and the ctypes arm side by side --------
+def _pack_records(C, N, channels, means2d, conics, colors, opacities, extra, radii):
+    """mobgs_pack_records: the compositor's per-splat records of these (float32, contiguous) inputs -> [C*N, stride]."""
+    lib = _lib_()
+    D = channels + (1 if extra is not None else 0)
+    records = torch.empty(C * N, lib.mobgs_record_stride(D), dtype=torch.float32, device=means2d.device)
+    check(lib.mobgs_pack_records(C, N, channels, ptr(means2d), ptr(conics), ptr(colors), 1 if colors.dim() == 3 else 0,
+                                 ptr(opacities), 1 if opacities.dim() == 2 else 0, ptr(extra), ptr(radii), ptr(records),
+                                 stream()), "mobgs_pack_records")
+    return records
+
+
+def _new_reach(tl, dev):
+    """Per list entry: the quadrants of its tile the splat can reach -- computed by the forward kernels anyway, kept for the
+    backward pass over the same lists."""
+    return torch.empty(max(tl.flatten_arena.numel(), 1), dtype=torch.uint8, device=dev)
+
+
+def _composite_until_resolved(tl, launch, honour_defer, reach=None):
+    """Run `launch(reach) -> reach` (one forward compositing launch over tl's lists) until the lists it read are final:
+    speculative lists whose arena was too small get rebuilt by tl.resolve(), then `reach` is regrown to the new arena and the
+    launch issued again.  -> the reach buffer of the last launch (None for a kernel that keeps none).
+    honour_defer: a caller that wants to enqueue more work before waiting for the counts sets tl.defer and resolves and
+    re-issues by itself.  render() sets `defer` only around composite_decode, which composites through _Rasterize, so
+    _Rasterize and _RasterizeClassAlpha (the nodes of the main image and its coverage) pass True; _RasterizeLayers and
+    _RasterizeClasses have always resolved on the spot and pass False."""
+    while True:
+        if reach is not None and reach.numel() < tl.flatten_arena.numel():  # lists rebuilt into a larger arena
+            reach = torch.empty(tl.flatten_arena.numel(), dtype=torch.uint8, device=reach.device)
+        reach = launch(reach)
+        if (honour_defer and tl.defer) or not tl.resolve():
+            return reach
+
+
+def _new_slots(tl, stride, dev, cover=False):
+    """Gradient slots of one backward pass: a row per list entry + one extra row whose first word is the any_record flag of
+    include/mobgs_hip.h (zeroed by the same fill; + the gate word of a gated pass).  cover (MobgsTuning.cover_slots): the
+    kernel writes every slot -- no fill."""
+    return (torch.empty if cover else torch.zeros)(max(tl.n_isects, 1) + 1, stride, dtype=torch.float32, device=dev)
+
+
+def _slot_flag(tl, slots, source, fast):
+    """The `any_record` word of a backward launch (include/mobgs_hip.h), from one of its three sources: "row" -- the first
+    word of the slot buffer's extra last row (_new_slots), which stage 1 sets; "total" -- the lists' total
+    (_lists_total_addr), wherever stage 1 sets none (cover_slots, the 10-channel class passes); None -- no flag.
+    fast: as the C++ host bodies take it (-1 = the extra row, an address, 0 = none), else as ctypes does (c_void_p | None)."""
+    if source == "row":
+        return -1 if fast else ctypes.c_void_p(slots.data_ptr() + 4 * (slots.shape[0] - 1) * slots.shape[1])
+    if source == "total":
+        return _lists_total_addr(tl) if fast else ctypes.c_void_p(_lists_total_addr(tl))
+    return 0 if fast else None
+
+
+def _raster_bwd(tl, records, bg, radii, means2d, alphas, last_ids, v_render, v_alphas, reach, dims, tn, cover):
+    """Stage 1 of the backward pass (mobgs_raster_bwd): per-entry gradient records -> slots.
+    dims = (C, N, channels, has_extra, width, height)."""
+    C, N, channels, has_extra, width, height = dims
+    F = _fast.get()
+    if F is not None:  # the same body in C++ (csrc/fastpath.cpp)
+        with profiler.region("raster_bwd"):
+            return F.raster_bwd(C, N, channels, int(has_extra), width, height, tl.n_isects, records, bg, radii, means2d,
+                                tl.cum_tiles, tl.keep_scan, tl.tile_offsets, tl.tile_order, tl.flatten_ids, alphas,
+                                last_ids, v_render, v_alphas, reach, tn.address(), stream_int(), cover)
+    v_render = f32c(v_render)
+    v_alphas = f32c(v_alphas) if v_alphas is not None else None
+    slots = _new_slots(tl, records.shape[1], records.device, cover)
+    flag = _slot_flag(tl, slots, None if cover else "row", False)
+    lib = _lib_()
+    with profiler.region("raster_bwd"):
+        check(lib.mobgs_raster_bwd(C, N, channels, int(has_extra), width, height, ptr(records), ptr(bg), ptr(radii),
+                                   ptr(means2d), ptr(tl.cum_tiles), ptr(tl.keep_scan), ptr(tl.tile_offsets),
+                                   ptr(tl.tile_order), ptr(tl.flatten_ids), ptr(alphas), ptr(last_ids), ptr(v_render),
+                                   ptr(v_alphas), ptr(slots), ptr(reach), flag, tn.ref(), stream()), "mobgs_raster_bwd")
+    return slots
+
+
+def _raster_bwd_decode(tl, records, bg, radii, render, alphas, last_ids, v_rgb, v_depth, v_alphas, dec, reach, dims, tn,
+                       cover):
+    """Stage 1 with the decoder's backward pass as the kernel's prologue (mobgs_raster_bwd_decode; dec = (intr, c2w, w1, w2)
+    as the forward saved them) -> (slots, partial rows of the decoder's weight / pose gradient sums).
+    dims = (C, N, width, height)."""
+    C, N, width, height = dims
+    intr, c2w, w1, w2 = dec
+    va = v_alphas.reshape(C, height, width) if v_alphas is not None else None
+    F = _fast.get()
+    with profiler.region("raster_bwd"):
+        if F is not None:
+            return F.raster_bwd_decode(C, N, width, height, tl.n_isects, records, bg, radii, tl.cum_tiles, tl.keep_scan,
+                                       tl.tile_offsets, tl.tile_order, tl.flatten_ids, render, alphas, last_ids, v_rgb,
+                                       v_depth, va, intr, c2w, w1, w2, reach, tn.address(), stream_int(), cover)
+        lib = _lib_()
+        dev = records.device
+        v_rgb = f32c(v_rgb) if v_rgb is not None else torch.zeros(C, 3, height, width, dtype=torch.float32, device=dev)
+        v_depth = f32c(v_depth) if v_depth is not None else None
+        va = f32c(va) if va is not None else None
+        slots = _new_slots(tl, records.shape[1], dev, cover)
+        partial = torch.empty(lib.mobgs_raster_bwd_decode_scratch_floats(C, width, height), dtype=torch.float32, device=dev)
+        check(lib.mobgs_raster_bwd_decode(
+            C, N, width, height, ptr(records), ptr(bg), ptr(radii), ptr(tl.cum_tiles), ptr(tl.keep_scan),
+            ptr(tl.tile_offsets), ptr(tl.tile_order), ptr(tl.flatten_ids), ptr(render), ptr(alphas), ptr(last_ids),
+            ptr(v_rgb), ptr(v_depth), ptr(va), ptr(intr), 4 if (C > 1 and intr.numel() == 4 * C) else 0, ptr(c2w),
+            (c2w.numel() // C) if (C > 1 and c2w.dim() == 3) else 0, ptr(w1), ptr(w2), ptr(slots), ptr(reach),
+            _slot_flag(tl, slots, None if cover else "row", False), ptr(partial), tn.ref(), stream()),
+            "mobgs_raster_bwd_decode")
+    return slots, partial
+
+
+def _reduce_slots(tl, records, slots, flag_source, C, N, channels, has_extra):
+    """Stage 2 (mobgs_raster_bwd_reduce): the slots of every splat summed
+    -> (v_means2d [C,N,2], v_conics [C,N,3], v_opac [C,N], v_colors [C,N,channels], v_extra [C,N] | None)."""
+    F = _fast.get()
+    if F is not None:
+        return F.raster_bwd_reduce(C, N, channels, int(has_extra), records, tl.cum_tiles, tl.keep_scan, slots, stream_int(),
+                                   tl.tiles_per_gauss, _slot_flag(tl, slots, flag_source, True))
+    dev = records.device
+    v_means2d = torch.empty(C, N, 2, dtype=torch.float32, device=dev)
+    v_conics = torch.empty(C, N, 3, dtype=torch.float32, device=dev)
+    v_opac = torch.empty(C, N, dtype=torch.float32, device=dev)
+    v_colors = torch.empty(C, N, channels, dtype=torch.float32, device=dev)
+    v_extra = torch.empty(C, N, dtype=torch.float32, device=dev) if has_extra else None
+    lib = _lib_()
+    check(lib.mobgs_raster_bwd_reduce(C, N, channels, int(has_extra), ptr(records), ptr(tl.cum_tiles), ptr(tl.keep_scan),
+                                      ptr(slots), _slot_flag(tl, slots, flag_source, False), ptr(v_means2d), ptr(v_conics),
+                                      ptr(v_opac), ptr(v_colors), ptr(v_extra), ptr(tl.tiles_per_gauss), stream()),
+          "mobgs_raster_bwd_reduce")
+    return v_means2d, v_conics, v_opac, v_colors, v_extra
+
+
+def _reduce_slots_decode(tl, records, slots, flag_source, C, N, channels, width, height, partial, c2w, w1, w2,
+                         c2w_needs_grad, sunk):
+    """Stage 2 after _raster_bwd_decode: the slot reduction + the decoder's weight / pose gradient sums over `partial`, which
+    ride in the reduction's launch (mobgs_raster_bwd_reduce_decode) or, WGRAD_IN_REDUCE = False, take a launch of their own
+    first (mobgs_raster_bwd_decode_finish, then the usual reduction).  sunk: LeafGradSink.decoder_buffers() or None.
+    -> (*the five of _reduce_slots, g_c2w | None, g_w1, g_w2)."""
+    F = _fast.get()
+    if WGRAD_IN_REDUCE and F is not None:
+        return F.raster_bwd_reduce_decode(
+            C, N, width, height, records, tl.cum_tiles, tl.keep_scan, slots, tl.tiles_per_gauss,
+            _slot_flag(tl, slots, flag_source, True), partial, c2w, w1, w2, bool(c2w_needs_grad),
+            sunk[0] if sunk is not None else None, sunk[1] if sunk is not None else None,
+            sunk[2] if sunk is not None else 0, stream_int())
+    lib = _lib_()
+    if sunk is not None:
+        g_w1, g_w2, accumulate = sunk
+    else:
+        g_w1, g_w2, accumulate = torch.empty_like(w1), torch.empty_like(w2), 0
+    g_c2w = torch.empty_like(c2w) if c2w_needs_grad else None
+    cstr = (c2w.numel() // C) if (C > 1 and c2w.dim() == 3) else 0
+    sums = (ptr(partial), cstr, ptr(g_w1), ptr(g_w2), ptr(g_c2w),
+            (g_c2w.numel() // (C if cstr else 1)) if g_c2w is not None else 0, accumulate, stream())
+    if not WGRAD_IN_REDUCE:
+        check(lib.mobgs_raster_bwd_decode_finish(C, width, height, *sums), "mobgs_raster_bwd_decode_finish")
+        return (*_reduce_slots(tl, records, slots, flag_source, C, N, channels, True), g_c2w, g_w1, g_w2)
+    dev = records.device
+    v_means2d = torch.empty(C, N, 2, dtype=torch.float32, device=dev)
+    v_conics = torch.empty(C, N, 3, dtype=torch.float32, device=dev)
+    v_opac = torch.empty(C, N, dtype=torch.float32, device=dev)
+    v_colors = torch.empty(C, N, channels, dtype=torch.float32, device=dev)
+    v_extra = torch.empty(C, N, dtype=torch.float32, device=dev)
+    check(lib.mobgs_raster_bwd_reduce_decode(
+        C, N, ptr(records), ptr(tl.cum_tiles), ptr(tl.keep_scan), ptr(slots), _slot_flag(tl, slots, flag_source, False),
+        ptr(v_means2d), ptr(v_conics), ptr(v_opac), ptr(v_colors), ptr(v_extra), ptr(tl.tiles_per_gauss), width, height,
+        *sums), "mobgs_raster_bwd_reduce_decode")
+    return v_means2d, v_conics, v_opac, v_colors, v_extra, g_c2w, g_w1, g_w2
+
+
+def _fold_cameras(v, per_camera, C):
+    """A per-camera gradient [C,N,...] as its input takes it: as it is when every camera had its own rows, else summed over
+    the cameras."""
+    if per_camera:
+        return v
+    return v.sum(0) if C > 1 else v[0]
+
+
+def _class_fwd(tl, records, bg, reach, C, N, Ns, cls, D, width, height, honour_defer):
+    """One class-restricted forward pass (mobgs_raster_class_fwd) over the lists of the whole set: class `cls` = 1, the first
+    Ns splats, or 2, the rest.  -> (render [C,H,W,D], alphas [C,H,W], last ids, reach)."""
+    lib = _lib_()
+    dev = records.device
+    render = torch.empty(C, height, width, D, dtype=torch.float32, device=dev)
+    alphas = torch.empty(C, height, width, dtype=torch.float32, device=dev)
+    last = torch.empty(C, height, width, dtype=torch.int32, device=dev)
+
+    def launch(reach):
+        check(lib.mobgs_raster_class_fwd(C, N, Ns, cls, D, width, height, ptr(records), ptr(bg), ptr(tl.tile_offsets),
+                                         ptr(tl.tile_order), ptr(tl.flatten_arena), ptr(render), ptr(alphas), ptr(last),
+                                         ptr(reach), tuning.ref(), stream()), "mobgs_raster_class_fwd")
+        return reach
+
+    reach = _composite_until_resolved(tl, launch, honour_defer, reach)
+    return render, alphas, last, reach
+
+
+def _class_bwd(tl, records, bg, radii, alphas, last, v_render, v_alpha, slots, reach, flag_source, tn, C, N, Ns, cls, D,
+               width, height):
+    """Stage 1 of a class-restricted backward pass (mobgs_raster_class_bwd) into `slots`: the classes of one set own
+    disjoint slots, so their passes may share one buffer and one reduction."""
+    lib = _lib_()
+    check(lib.mobgs_raster_class_bwd(C, N, Ns, cls, D, width, height, ptr(records), ptr(bg), ptr(radii), ptr(tl.cum_tiles),
+                                     ptr(tl.keep_scan), ptr(tl.tile_offsets), ptr(tl.tile_order), ptr(tl.flatten_ids),
+                                     ptr(alphas), ptr(last), ptr(v_render), ptr(v_alpha), ptr(slots), ptr(reach),
+                                     _slot_flag(tl, slots, flag_source, False), tn.ref(), stream()),
+          "mobgs_raster_class_bwd")
+
+
+# True: render() lets the forward compositor decode its own image (SharedProjection.composite_decode); False: a separate
+# decoder launch, as before round 5 (A/B; results are bit-identical)
+FUSE_DECODER = os.environ.get("MOBGS_FUSE_DECODER", "1") != "0"
+# True (round 6): the backward half too -- rgb / depth are outputs of the compositing node itself and the decoder's backward
+# pass is the prologue of the backward compositor (mobgs_raster_bwd_decode); False: ops.Decode owns it (a launch of its
+# own + a 55-MB cotangent image).  Splat gradients are bit-identical either way, weight / pose gradients to summation order.
+FUSE_DECODER_BWD = os.environ.get("MOBGS_FUSE_DECODER_BWD", "1") != "0"
+# True: the decoder's weight / pose gradient sums run as extra workgroups of the gradient-slot reduction (no launch of their
+# own); False: mobgs_raster_bwd_decode_finish (A/B; same sums to summation order)
+WGRAD_IN_REDUCE = os.environ.get("MOBGS_WGRAD_IN_REDUCE", "1") != "0"
+# True: static-only / dynamic-only images (without the combined one) come from two class-restricted passes of the
+# single-set compositor over the combined lists (every splat belongs to exactly one class, so together they do the
+# work of ONE pass and share one gradient-slot buffer); False: from the generic 3-layer kernel
+CLASS_PASSES = True
+
+
 class _Rasterize(torch.autograd.Function):
-    """rasterize_to_pixels: (means2d, conics, colors, opacities[, extra channel], backgrounds) -> image, alpha."""
+    """rasterize_to_pixels: (means2d, conics, colors, opacities[, extra channel], backgrounds) -> image, alpha
+    [, rgb, depth of the Sandwich decoder run as the compositor's epilogue]."""
 
     @staticmethod
     def forward(ctx, means2d, conics, colors, opacities, extra, backgrounds, radii, tl: TileLists, width, height,
@@ -677,10 +922,11 @@ class _Rasterize(torch.autograd.Function):
         """dec = (intr, c2w, w1, w2) (detached, float32, contiguous): the Sandwich decoder runs as the kernel's epilogue
         (mobgs_raster_fwd_decode) and the node returns (render, alphas, rgb, depth) -- rgb / depth non-differentiable here:
         ops.Decode takes them as its precomputed outputs and owns their backward pass.
-        dec_c2w / dec_w1 / dec_w2 (round 6, FUSE_DECODER_BWD): the caller's pose and weight TENSORS -- rgb / depth are then
-        differentiable outputs of THIS node and its backward pass runs the decoder's backward as the prologue of the backward
-        compositor (mobgs_raster_bwd_decode: no decoder launch, no cotangent image in memory) whenever only rgb / depth
-        carry cotangents and the quadrant kernel is the selection; else decoder_bwd runs as a launch of its own.
+        dec_c2w / dec_w1 / dec_w2 (FUSE_DECODER_BWD): the caller's pose and weight TENSORS -- rgb / depth are then
+        differentiable outputs of THIS node, whose backward pass runs the decoder's backward as the prologue of the backward
+        compositor (_raster_bwd_decode: no decoder launch, no cotangent image in memory) whenever only rgb / depth (and
+        alpha) carry cotangents and the ungated quadrant kernel is the selection; else as a launch of its own
+        (_decoder_bwd_separately).
         static_rows = S > 0: the first S splats are the reference's STATIC set (include/mobgs_hip.h
         MobgsTuning.static_rows: colour channels 6.. structurally zero, their gradient multiplied by 0.0 downstream) --
         the backward compositor takes the short blend body for their entries and returns zeros for those channels."""
@@ -706,7 +952,17 @@ class _Rasterize(torch.autograd.Function):
         rgb = dec_depth = None
         if dec is not None and not (D == 10 and extra is not None and tuning.block_walk != 0):
             raise NotImplementedError("decoder epilogue: 9 feature channels + depth through the block-walk kernel only")
-        if F is None:
+        if F is not None:  # allocations + the launch in C++ (csrc/fastpath.cpp); buffers are reused on a redo
+            d4 = dec if dec is not None else (None, None, None, None)
+
+            def launch(reach):
+                nonlocal records, render, alphas, last_ids, rgb, dec_depth
+                records, render, alphas, last_ids, reach, rgb, dec_depth = F.raster_fwd(
+                    C, N, channels, width, height, means2d, conics, colors_arg, colors_per_camera, opacities,
+                    opac_per_camera, extra, bg, radii, tl.tile_offsets, tl.tile_order, tl.flatten_arena, records,
+                    reach, tuning.address(), stream_int(), *d4)
+                return reach
+        else:
             if records is None:
                 records = torch.empty(C * N, stride, dtype=torch.float32, device=dev)
             if dec is not None:
@@ -715,36 +971,24 @@ class _Rasterize(torch.autograd.Function):
             render = torch.empty(C, height, width, D, dtype=torch.float32, device=dev)
             alphas = torch.empty(C, height, width, dtype=torch.float32, device=dev)
             last_ids = torch.empty(C, height, width, dtype=torch.int32, device=dev)
-            # per list entry: the quadrants of its tile the splat can reach -- computed by the forward kernel anyway,
-            # kept for the backward pass over the same lists
-            reach = torch.empty(max(tl.flatten_arena.numel(), 1), dtype=torch.uint8, device=dev)
-        with profiler.region("raster_fwd"):
-            while True:
-                if F is not None:  # allocations + the launch in C++ (csrc/fastpath.cpp); buffers are reused on a redo
-                    d4 = dec if dec is not None else (None, None, None, None)
-                    records, render, alphas, last_ids, reach, rgb, dec_depth = F.raster_fwd(
-                        C, N, channels, width, height, means2d, conics, colors_arg, colors_per_camera, opacities,
-                        opac_per_camera, extra, bg, radii, tl.tile_offsets, tl.tile_order, tl.flatten_arena, records,
-                        reach, tuning.address(), stream_int(), *d4)
+            reach = _new_reach(tl, dev)
+
+            def launch(reach):
+                head = (C, N, channels, width, height, ptr(means2d), ptr(conics), ptr(colors_arg), colors_per_camera,
+                        ptr(opacities), opac_per_camera, ptr(extra), ptr(bg), ptr(radii), ptr(tl.tile_offsets),
+                        ptr(tl.tile_order), ptr(tl.flatten_arena), ptr(records), ptr(render), ptr(alphas),
+                        ptr(last_ids), ptr(reach))
+                if dec is not None:
+                    intr, c2w, w1, w2 = dec
+                    check(lib.mobgs_raster_fwd_decode(*head, ptr(intr), 4 if (C > 1 and intr.numel() == 4 * C) else 0,
+                                                      ptr(c2w), (c2w.numel() // C) if (C > 1 and c2w.dim() == 3) else 0,
+                                                      ptr(w1), ptr(w2), ptr(rgb), ptr(dec_depth), tuning.ref(),
+                                                      stream()), "mobgs_raster_fwd_decode")
                 else:
-                    if reach.numel() < tl.flatten_arena.numel():  # lists rebuilt into a larger arena
-                        reach = torch.empty(tl.flatten_arena.numel(), dtype=torch.uint8, device=dev)
-                    head = (C, N, channels, width, height, ptr(means2d), ptr(conics), ptr(colors_arg), colors_per_camera,
-                            ptr(opacities), opac_per_camera, ptr(extra), ptr(bg), ptr(radii), ptr(tl.tile_offsets),
-                            ptr(tl.tile_order), ptr(tl.flatten_arena), ptr(records), ptr(render), ptr(alphas),
-                            ptr(last_ids), ptr(reach))
-                    if dec is not None:
-                        intr, c2w, w1, w2 = dec
-                        check(lib.mobgs_raster_fwd_decode(*head, ptr(intr), 4 if (C > 1 and intr.numel() == 4 * C) else 0,
-                                                          ptr(c2w), (c2w.numel() // C) if (C > 1 and c2w.dim() == 3) else 0,
-                                                          ptr(w1), ptr(w2), ptr(rgb), ptr(dec_depth), tuning.ref(),
-                                                          stream()), "mobgs_raster_fwd_decode")
-                    else:
-                        check(lib.mobgs_raster_fwd(*head, tuning.ref(), stream()), "mobgs_raster_fwd")
-                # speculative lists whose arena was too small get rebuilt by resolve(): composite again.  A caller that
-                # wants to enqueue more work before waiting for the counts sets tl.defer and does this itself.
-                if tl.defer or not tl.resolve():
-                    break
+                    check(lib.mobgs_raster_fwd(*head, tuning.ref(), stream()), "mobgs_raster_fwd")
+                return reach
+        with profiler.region("raster_fwd"):
+            reach = _composite_until_resolved(tl, launch, True, reach)
         _log_path("fwd", D, tl, decode=dec is not None)
         dec_fused = dec is not None and dec_w1 is not None
         if dec_fused:   # (+ the decoder's inputs: the composited image -- an output, saved the way outputs are -- and weights)
@@ -771,193 +1015,74 @@ class _Rasterize(torch.autograd.Function):
 
     @staticmethod
     def _decoder_bwd_separately(ctx, alphas, v_rgb, v_depth):
-        """decoder_bwd as a launch of its own (ops.Decode's backward on this node's saved state) -> (v_feat [C,H,W,10],
-        v_alphas [C,H,W], g_c2w | None, g_w1 | None, g_w2 | None)."""
-        from types import SimpleNamespace
-        from . import ops
+        """decoder_bwd as a launch of its own (ops.decode_backward on this node's saved state) -> (v_feat [C,H,W,10],
+        v_alphas [C,H,W,1], g_c2w | None, g_w1 | None, g_w2 | None)."""
         render, intr, c2w, w1, w2 = ctx.saved_tensors[7:12]
         C, H, W = alphas.shape
         lead = (C,) if C > 1 else ()
         feat = render.reshape(*lead, H, W, 10)
         c2w_d = c2w if (C > 1 or c2w.dim() == 2) else c2w.reshape(c2w.shape[-2:])
-        fake = SimpleNamespace(saved_tensors=(feat, alphas.reshape(*lead, H, W), None, intr.reshape(-1) if C == 1 else intr,
-                                              c2w_d, w1, w2),
-                               has_depth=True, w_inputs=ctx.dec_w_inputs, feat_shape=feat.shape, rays_need_grad=False,
-                               c2w_needs_grad=ctx.dec_c2w_needs_grad)
         if v_rgb is not None:
             v_rgb = v_rgb.reshape(*lead, 3, H, W)
         if v_depth is not None:
             v_depth = v_depth.reshape(*lead, H, W)
-        g = ops.Decode.backward(fake, v_rgb, v_depth)
+        g = ops.decode_backward((feat, alphas.reshape(*lead, H, W), None, intr.reshape(-1) if C == 1 else intr, c2w_d, w1, w2),
+                                True, ctx.dec_w_inputs, feat.shape, False, ctx.dec_c2w_needs_grad, v_rgb, v_depth)
         g_c2w = g[4].reshape(ctx.dec_c2w_shape) if g[4] is not None else None
-        return g[0].reshape(C, H, W, 10), g[1].reshape(C, H, W), g_c2w, g[5], g[6]
+        return g[0].reshape(C, H, W, 10), g[1].reshape(C, H, W, 1), g_c2w, g[5], g[6]
 
     @staticmethod
     def backward(ctx, v_render, v_alphas, v_rgb=None, v_depth=None):
-        lib = _lib_()
         records, bg, radii, means2d, alphas, last_ids, reach = ctx.saved_tensors[:7]
         tl = ctx.tl
         if tl.flatten_arena is not ctx.arena:  # lists rebuilt after this forward ran (deferred resolve): recompute
             reach = None
         C, N, channels, has_extra, width, height, colors_per_camera, opac_per_camera = ctx.meta
-        dev = records.device
         D = channels + (1 if has_extra else 0)
-        stride = records.shape[1]
         if not ctx.dec_fused:
             v_rgb = v_depth = None
         if v_render is None and v_alphas is None and v_rgb is None and v_depth is None:
             return (None,) * 16
-        F = _fast.get()
+        # plan: which kernel, with which tuning, and where the decoder's backward pass runs
         gated = bool(ctx.gate) and tuning.bwd_block_walk != 1
         nt = tl.C * tl.tile_w * tl.tile_h
         quadrant = tuning.bwd_block_walk != 1 and (_raster_path_bits(D, nt) & 3) == 0
         cover = COVER_SLOTS and quadrant and not gated   # the kernel writes every slot: no zero fill, no flag
         tn = _tuning_variant(gated, ctx.static_rows, cover)
+        flag_source = "total" if cover else "row"
+        decoder = v_rgb is not None or v_depth is not None
+        fuse = decoder and v_render is None and not ctx.bg_needs_grad and not gated and quadrant
         g_c2w = g_w1 = g_w2 = None
-        slots, reduced = None, False
-        if v_rgb is not None or v_depth is not None:
-            fuse = v_render is None and not ctx.bg_needs_grad and not gated and quadrant
-            if fuse:   # the decoder's backward pass inside the backward compositor
-                from . import ops
-                render, intr, c2w, w1, w2 = ctx.saved_tensors[7:12]
-                sunk = ops._active_sink.decoder_buffers(*ctx.dec_w_inputs) if ops._active_sink is not None else None
-                _log_path("bwd", D, tl, tn=tn, static_rows=tn.static_rows, decode_bwd=True)
-                va = v_alphas.reshape(C, height, width) if v_alphas is not None else None
-                istr = 4 if (C > 1 and intr.numel() == 4 * C) else 0
-                cstr = (c2w.numel() // C) if (C > 1 and c2w.dim() == 3) else 0
-                with profiler.region("raster_bwd"):
-                    if F is not None:
-                        slots, partial = F.raster_bwd_decode(
-                            C, N, width, height, tl.n_isects, records, bg, radii, tl.cum_tiles, tl.keep_scan,
-                            tl.tile_offsets, tl.tile_order, tl.flatten_ids, render, alphas, last_ids, v_rgb, v_depth, va,
-                            intr, c2w, w1, w2, reach, tn.address(), stream_int(), cover)
-                    else:
-                        v_rgb_c = f32c(v_rgb) if v_rgb is not None else torch.zeros(C, 3, height, width, dtype=torch.float32,
-                                                                                    device=dev)
-                        v_depth_c = f32c(v_depth) if v_depth is not None else None
-                        va = f32c(va) if va is not None else None
-                        rows = max(tl.n_isects, 1)
-                        slots = (torch.empty if cover else torch.zeros)(rows + 1, stride, dtype=torch.float32, device=dev)
-                        flag = None if cover else ctypes.c_void_p(slots.data_ptr() + 4 * rows * stride)
-                        partial = torch.empty(lib.mobgs_raster_bwd_decode_scratch_floats(C, width, height),
-                                              dtype=torch.float32, device=dev)
-                        check(lib.mobgs_raster_bwd_decode(
-                            C, N, width, height, ptr(records), ptr(bg), ptr(radii), ptr(tl.cum_tiles), ptr(tl.keep_scan),
-                            ptr(tl.tile_offsets), ptr(tl.tile_order), ptr(tl.flatten_ids), ptr(render), ptr(alphas),
-                            ptr(last_ids), ptr(v_rgb_c), ptr(v_depth_c), ptr(va), ptr(intr), istr, ptr(c2w), cstr, ptr(w1),
-                            ptr(w2), ptr(slots), ptr(reach), flag, ptr(partial), tn.ref(), stream()),
-                            "mobgs_raster_bwd_decode")
-                # the weight / pose gradient sums ride in the slot reduction's launch (mobgs_raster_bwd_reduce_decode);
-                # WGRAD_IN_REDUCE = False: a launch of their own (mobgs_raster_bwd_decode_finish), then the usual reduction
-                if not WGRAD_IN_REDUCE:
-                    if sunk is not None:
-                        g_w1, g_w2, accumulate = sunk
-                    else:
-                        g_w1, g_w2, accumulate = torch.empty_like(w1), torch.empty_like(w2), 0
-                    g_c2w = torch.empty_like(c2w) if ctx.dec_c2w_needs_grad else None
-                    check(lib.mobgs_raster_bwd_decode_finish(
-                        C, width, height, ptr(partial), cstr, ptr(g_w1), ptr(g_w2), ptr(g_c2w),
-                        (g_c2w.numel() // (C if cstr else 1)) if g_c2w is not None else 0, accumulate, stream()),
-                        "mobgs_raster_bwd_decode_finish")
-                elif F is not None:
-                    v_means2d, v_conics, v_opac, v_colors, v_extra, g_c2w, g_w1, g_w2 = F.raster_bwd_reduce_decode(
-                        C, N, width, height, records, tl.cum_tiles, tl.keep_scan, slots, tl.tiles_per_gauss,
-                        _lists_total_addr(tl) if cover else -1, partial, c2w, w1, w2, bool(ctx.dec_c2w_needs_grad), sunk[0] if sunk is not None else None,
-                        sunk[1] if sunk is not None else None, sunk[2] if sunk is not None else 0, stream_int())
-                else:
-                    if sunk is not None:
-                        g_w1, g_w2, accumulate = sunk
-                    else:
-                        g_w1, g_w2, accumulate = torch.empty_like(w1), torch.empty_like(w2), 0
-                    g_c2w = torch.empty_like(c2w) if ctx.dec_c2w_needs_grad else None
-                    v_means2d = torch.empty(C, N, 2, dtype=torch.float32, device=dev)
-                    v_conics = torch.empty(C, N, 3, dtype=torch.float32, device=dev)
-                    v_opac = torch.empty(C, N, dtype=torch.float32, device=dev)
-                    v_colors = torch.empty(C, N, channels, dtype=torch.float32, device=dev)
-                    v_extra = torch.empty(C, N, dtype=torch.float32, device=dev)
-                    flag2 = ctypes.c_void_p(_lists_total_addr(tl) if cover else slots.data_ptr() + 4 * max(tl.n_isects, 1) * stride)
-                    check(lib.mobgs_raster_bwd_reduce_decode(
-                        C, N, ptr(records), ptr(tl.cum_tiles), ptr(tl.keep_scan), ptr(slots), flag2, ptr(v_means2d),
-                        ptr(v_conics), ptr(v_opac), ptr(v_colors), ptr(v_extra), ptr(tl.tiles_per_gauss), width, height,
-                        ptr(partial), cstr, ptr(g_w1), ptr(g_w2), ptr(g_c2w),
-                        (g_c2w.numel() // (C if cstr else 1)) if g_c2w is not None else 0, accumulate, stream()),
-                        "mobgs_raster_bwd_reduce_decode")
-                reduced = WGRAD_IN_REDUCE
-                if g_c2w is not None:
-                    g_c2w = g_c2w.reshape(ctx.dec_c2w_shape)
-                if sunk is not None:
-                    g_w1 = g_w2 = None
-            else:      # some other output carries a cotangent too (or another kernel is selected): decoder_bwd by itself
-                v_feat, v_a_dec, g_c2w, g_w1, g_w2 = _Rasterize._decoder_bwd_separately(ctx, alphas, v_rgb, v_depth)
-                v_render = v_feat if v_render is None else v_render + v_feat
-                v_a_dec = v_a_dec.reshape(C, height, width, 1)
-                v_alphas = v_a_dec if v_alphas is None else v_alphas + v_a_dec
-        if slots is None and v_render is None:  # only the alpha output was used
-            v_render = torch.zeros(C, height, width, D, dtype=torch.float32, device=dev)
-        if slots is None:
-            _log_path("bwd", D, tl, tn=tn, static_rows=tn.static_rows)
-        if slots is not None and not reduced:
-            st = stream_int()
-            if F is not None:
-                v_means2d, v_conics, v_opac, v_colors, v_extra = F.raster_bwd_reduce(
-                    C, N, channels, int(has_extra), records, tl.cum_tiles, tl.keep_scan, slots, st, tl.tiles_per_gauss,
-                    _lists_total_addr(tl) if cover else -1)
-            else:
-                rows = max(tl.n_isects, 1)
-                flag = ctypes.c_void_p(_lists_total_addr(tl) if cover else slots.data_ptr() + 4 * rows * stride)
-                v_means2d = torch.empty(C, N, 2, dtype=torch.float32, device=dev)
-                v_conics = torch.empty(C, N, 3, dtype=torch.float32, device=dev)
-                v_opac = torch.empty(C, N, dtype=torch.float32, device=dev)
-                v_colors = torch.empty(C, N, channels, dtype=torch.float32, device=dev)
-                v_extra = torch.empty(C, N, dtype=torch.float32, device=dev) if has_extra else None
-                check(lib.mobgs_raster_bwd_reduce(C, N, channels, int(has_extra), ptr(records), ptr(tl.cum_tiles),
-                                                  ptr(tl.keep_scan), ptr(slots), flag, ptr(v_means2d), ptr(v_conics),
-                                                  ptr(v_opac), ptr(v_colors), ptr(v_extra), ptr(tl.tiles_per_gauss),
-                                                  stream()), "mobgs_raster_bwd_reduce")
-        elif reduced:
-            pass
-        elif F is not None:  # the same body in C++ (csrc/fastpath.cpp)
-            st = stream_int()
-            with profiler.region("raster_bwd"):
-                slots = F.raster_bwd(C, N, channels, int(has_extra), width, height, tl.n_isects, records, bg, radii,
-                                     means2d, tl.cum_tiles, tl.keep_scan, tl.tile_offsets, tl.tile_order,
-                                     tl.flatten_ids, alphas, last_ids, v_render, v_alphas, reach, tn.address(), st, cover)
-            v_means2d, v_conics, v_opac, v_colors, v_extra = F.raster_bwd_reduce(
-                C, N, channels, int(has_extra), records, tl.cum_tiles, tl.keep_scan, slots, st, tl.tiles_per_gauss,
-                _lists_total_addr(tl) if cover else -1)
+        if decoder and not fuse:  # some other output carries a cotangent too (or another kernel is selected)
+            v_feat, v_a_dec, g_c2w, g_w1, g_w2 = _Rasterize._decoder_bwd_separately(ctx, alphas, v_rgb, v_depth)
+            v_render = v_feat if v_render is None else v_render + v_feat
+            v_alphas = v_a_dec if v_alphas is None else v_alphas + v_a_dec
+        if fuse:   # the decoder's backward pass inside the backward compositor
+            render, intr, c2w, w1, w2 = ctx.saved_tensors[7:12]
+            sunk = ops._active_sink.decoder_buffers(*ctx.dec_w_inputs) if ops._active_sink is not None else None
+            _log_path("bwd", D, tl, tn=tn, static_rows=tn.static_rows, decode_bwd=True)
+            slots, partial = _raster_bwd_decode(tl, records, bg, radii, render, alphas, last_ids, v_rgb, v_depth, v_alphas,
+                                                (intr, c2w, w1, w2), reach, (C, N, width, height), tn, cover)
+            v_means2d, v_conics, v_opac, v_colors, v_extra, g_c2w, g_w1, g_w2 = _reduce_slots_decode(
+                tl, records, slots, flag_source, C, N, channels, width, height, partial, c2w, w1, w2,
+                ctx.dec_c2w_needs_grad, sunk)
+            if g_c2w is not None:
+                g_c2w = g_c2w.reshape(ctx.dec_c2w_shape)
+            if sunk is not None:
+                g_w1 = g_w2 = None
         else:
-            v_render = f32c(v_render)
-            v_alphas = f32c(v_alphas) if v_alphas is not None else None
-            # one extra row: its first word is the any_record flag of include/mobgs_hip.h (zeroed by the same fill)
-            rows = max(tl.n_isects, 1)
-            slots = (torch.empty if cover else torch.zeros)(rows + 1, stride, dtype=torch.float32, device=dev)
-            flag = None if cover else ctypes.c_void_p(slots.data_ptr() + 4 * rows * stride)
-            v_means2d = torch.empty(C, N, 2, dtype=torch.float32, device=dev)
-            v_conics = torch.empty(C, N, 3, dtype=torch.float32, device=dev)
-            v_opac = torch.empty(C, N, dtype=torch.float32, device=dev)
-            v_colors = torch.empty(C, N, channels, dtype=torch.float32, device=dev)
-            v_extra = torch.empty(C, N, dtype=torch.float32, device=dev) if has_extra else None
-            with profiler.region("raster_bwd"):
-                check(lib.mobgs_raster_bwd(C, N, channels, int(has_extra), width, height, ptr(records), ptr(bg),
-                                           ptr(radii), ptr(means2d), ptr(tl.cum_tiles), ptr(tl.keep_scan),
-                                           ptr(tl.tile_offsets), ptr(tl.tile_order), ptr(tl.flatten_ids), ptr(alphas),
-                                           ptr(last_ids), ptr(v_render), ptr(v_alphas), ptr(slots), ptr(reach),
-                                           flag, tn.ref(), stream()), "mobgs_raster_bwd")
-            check(lib.mobgs_raster_bwd_reduce(C, N, channels, int(has_extra), ptr(records), ptr(tl.cum_tiles),
-                                              ptr(tl.keep_scan), ptr(slots),
-                                              ctypes.c_void_p(_lists_total_addr(tl)) if cover else flag, ptr(v_means2d),
-                                              ptr(v_conics), ptr(v_opac),
-                                              ptr(v_colors), ptr(v_extra), ptr(tl.tiles_per_gauss), stream()),
-                  "mobgs_raster_bwd_reduce")
-        if not colors_per_camera:
-            v_colors = v_colors.sum(0) if C > 1 else v_colors[0]
-        if not opac_per_camera:
-            v_opac = v_opac.sum(0) if C > 1 else v_opac[0]
+            if v_render is None:  # only the alpha output was used
+                v_render = torch.zeros(C, height, width, D, dtype=torch.float32, device=records.device)
+            _log_path("bwd", D, tl, tn=tn, static_rows=tn.static_rows)
+            slots = _raster_bwd(tl, records, bg, radii, means2d, alphas, last_ids, v_render, v_alphas, reach,
+                                (C, N, channels, has_extra, width, height), tn, cover)
+            v_means2d, v_conics, v_opac, v_colors, v_extra = _reduce_slots(tl, records, slots, flag_source, C, N, channels,
+                                                                           has_extra)
         v_bg = None
         if ctx.bg_needs_grad:
             v_bg = (v_render * (1.0 - alphas).unsqueeze(-1)).sum(dim=(1, 2))
-        return (v_means2d, v_conics, v_colors, v_opac, v_extra, v_bg, None, None, None, None, None, None, None,
-                g_c2w, g_w1, g_w2)
+        return (v_means2d, v_conics, _fold_cameras(v_colors, colors_per_camera, C), _fold_cameras(v_opac, opac_per_camera, C),
+                v_extra, v_bg, None, None, None, None, None, None, None, g_c2w, g_w1, g_w2)
 
 
 class _RasterizeClassAlpha(torch.autograd.Function):
@@ -965,36 +1090,19 @@ class _RasterizeClassAlpha(torch.autograd.Function):
     or the rest (2) -- over the tile lists of the WHOLE set: what a rasterization of that subset alone with a ones
     colour returns as alpha, without projecting, binning and sorting the subset a second time
     (/root/reference/gaussian_renderer/__init__.py:477-490 does exactly that for the dynamic splats in get_flow()).
-    mobgs_raster_class_fwd/bwd with one channel; -> alphas [C,H,W]."""
+    A one-channel class pass (_class_fwd / _class_bwd); -> alphas [C,H,W]."""
 
     @staticmethod
     def forward(ctx, means2d, conics, opacities, radii, tl: TileLists, width, height, Ns, class_sel, background=None):
-        lib = _lib_()
         C, N = radii.shape
         dev = means2d.device
         means2d, conics, opacities = map(f32c, (means2d, conics, opacities))
-        ones = _ones_colors(N, dev)
-        stride = lib.mobgs_record_stride(1)
-        records = torch.empty(C * N, stride, dtype=torch.float32, device=dev)
-        check(lib.mobgs_pack_records(C, N, 1, ptr(means2d), ptr(conics), ptr(ones), 0, ptr(opacities),
-                                     1 if opacities.dim() == 2 else 0, None, ptr(radii), ptr(records), stream()),
-              "mobgs_pack_records")
+        records = _pack_records(C, N, 1, means2d, conics, _const(torch.ones, N, 1, dev=dev), opacities, None, radii)
         # background [C,1] (optional): the ones-colour render (1 - T) + T * bg -- what get_flow() calls latent_alpha,
         # /root/reference/gaussian_renderer/__init__.py:477-490 -- leaves the kernel directly (no rsub / mul / add glue)
         bg = f32c(background).reshape(C, 1) if background is not None else None
-        render = torch.empty(C, height, width, 1, dtype=torch.float32, device=dev)
-        alphas = torch.empty(C, height, width, dtype=torch.float32, device=dev)
-        last = torch.empty(C, height, width, dtype=torch.int32, device=dev)
-        reach = torch.empty(max(tl.flatten_arena.numel(), 1), dtype=torch.uint8, device=dev)
-        while True:
-            if reach.numel() < tl.flatten_arena.numel():  # lists rebuilt into a larger arena
-                reach = torch.empty(tl.flatten_arena.numel(), dtype=torch.uint8, device=dev)
-            check(lib.mobgs_raster_class_fwd(C, N, Ns, class_sel, 1, width, height, ptr(records), ptr(bg),
-                                             ptr(tl.tile_offsets), ptr(tl.tile_order), ptr(tl.flatten_arena),
-                                             ptr(render), ptr(alphas), ptr(last), ptr(reach), tuning.ref(), stream()),
-                  "mobgs_raster_class_fwd")
-            if tl.defer or not tl.resolve():
-                break
+        render, alphas, last, reach = _class_fwd(tl, records, bg, _new_reach(tl, dev), C, N, Ns, class_sel, 1, width,
+                                                 height, True)
         _log_path("fwd", 1, tl, class_filter=True, decode=False)
         ctx.save_for_backward(records, radii, alphas, last, reach, bg)
         ctx.tl, ctx.arena = tl, tl.flatten_arena
@@ -1004,7 +1112,6 @@ class _RasterizeClassAlpha(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, v_alphas):
-        lib = _lib_()
         C, N, width, height, opac_per_camera, Ns, class_sel = ctx.meta
         records, radii, alphas, last, reach, bg = ctx.saved_tensors
         tl = ctx.tl
@@ -1013,62 +1120,17 @@ class _RasterizeClassAlpha(torch.autograd.Function):
             return (None,) * 10
         if tl.flatten_arena is not ctx.arena:  # lists rebuilt after this forward ran: recompute the masks
             reach = None
-        stride = records.shape[1]
-        rows = max(tl.n_isects, 1)
-        gated = bool(ctx.gate)
-        tn = _tuning_gated() if gated else tuning
-        # last row: the any_record flag (+ the gate word of a gated pass)
-        slots = torch.zeros(rows + 1, stride, dtype=torch.float32, device=dev)
-        flag = ctypes.c_void_p(slots.data_ptr() + 4 * rows * stride)
+        tn = _tuning_gated() if ctx.gate else tuning
+        slots = _new_slots(tl, records.shape[1], dev)
         if bg is None:   # the cotangent belongs to the alpha output
-            v_render, v_a = _zero_image(C, height, width, dev), f32c(v_alphas)
+            v_render, v_a = _const(torch.zeros, C, height, width, 1, dev=dev), f32c(v_alphas)
         else:            # ... to the 1-channel render output (background folded in by the kernel)
             v_render, v_a = f32c(v_alphas).reshape(C, height, width, 1), None
         _log_path("bwd", 1, tl, class_filter=True, tn=tn)
-        check(lib.mobgs_raster_class_bwd(C, N, Ns, class_sel, 1, width, height, ptr(records), ptr(bg), ptr(radii),
-                                         ptr(tl.cum_tiles), ptr(tl.keep_scan), ptr(tl.tile_offsets),
-                                         ptr(tl.tile_order), ptr(tl.flatten_ids), ptr(alphas), ptr(last),
-                                         ptr(v_render), ptr(v_a), ptr(slots), ptr(reach), flag,
-                                         tn.ref(), stream()), "mobgs_raster_class_bwd")
-        v_means2d = torch.empty(C, N, 2, dtype=torch.float32, device=dev)
-        v_conics = torch.empty(C, N, 3, dtype=torch.float32, device=dev)
-        v_opac = torch.empty(C, N, dtype=torch.float32, device=dev)
-        v_colors = torch.empty(C, N, 1, dtype=torch.float32, device=dev)
-        check(lib.mobgs_raster_bwd_reduce(C, N, 1, 0, ptr(records), ptr(tl.cum_tiles), ptr(tl.keep_scan), ptr(slots), flag,
-                                          ptr(v_means2d), ptr(v_conics), ptr(v_opac), ptr(v_colors), None,
-                                          ptr(tl.tiles_per_gauss), stream()),
-              "mobgs_raster_bwd_reduce")
-        if not opac_per_camera:
-            v_opac = v_opac.sum(0) if C > 1 else v_opac[0]
-        return v_means2d, v_conics, v_opac, None, None, None, None, None, None, None
-
-
-_const_cache = {}
-
-
-def _ones_colors(n, dev):
-    key = ("ones", n, str(dev))
-    t = _const_cache.get(key)
-    if t is None:
-        if len(_const_cache) > 16:
-            _const_cache.clear()
-        t = _const_cache[key] = torch.ones(n, 1, dtype=torch.float32, device=dev)
-    return t
-
-
-def _zero_image(C, h, w, dev):
-    key = ("zeros", C, h, w, str(dev))
-    t = _const_cache.get(key)
-    if t is None:
-        if len(_const_cache) > 16:
-            _const_cache.clear()
-        t = _const_cache[key] = torch.zeros(C, h, w, 1, dtype=torch.float32, device=dev)
-    return t
-
-
-def _ptr3(tensors):
-    import ctypes
-    return (ctypes.c_void_p * 3)(*[None if t is None else t.data_ptr() for t in tensors])
+        _class_bwd(tl, records, bg, radii, alphas, last, v_render, v_a, slots, reach, "row", tn, C, N, Ns, class_sel, 1,
+                   width, height)
+        v_means2d, v_conics, v_opac, _, _ = _reduce_slots(tl, records, slots, "row", C, N, 1, False)
+        return v_means2d, v_conics, _fold_cameras(v_opac, opac_per_camera, C), None, None, None, None, None, None, None
 
 
 class _RasterizeLayers(torch.autograd.Function):
@@ -1092,25 +1154,22 @@ class _RasterizeLayers(torch.autograd.Function):
             raise NotImplementedError("layered compositing is built for 9 feature channels + depth")
         _refuse_token(colors, None, "_RasterizeLayers")
         bg = f32c(backgrounds) if backgrounds is not None else None
-        stride = lib.mobgs_record_stride(D)
-        records = torch.empty(C * N, stride, dtype=torch.float32, device=dev)
-        check(lib.mobgs_pack_records(C, N, channels, ptr(means2d), ptr(conics), ptr(colors),
-                                     1 if colors.dim() == 3 else 0, ptr(opacities), 1 if opacities.dim() == 2 else 0,
-                                     ptr(extra), ptr(radii), ptr(records), stream()), "mobgs_pack_records")
+        records = _pack_records(C, N, channels, means2d, conics, colors, opacities, extra, radii)
         renders, alphas, lasts = [], [], []
         for layer in range(3):
             on = (mask >> layer) & 1
             renders.append(torch.empty(C, height, width, D, dtype=torch.float32, device=dev) if on else None)
             alphas.append(torch.empty(C, height, width, dtype=torch.float32, device=dev) if on else None)
             lasts.append(torch.empty(C, height, width, dtype=torch.int32, device=dev) if on else None)
+
+        def launch(_):   # (this kernel keeps no reach masks)
+            check(lib.mobgs_raster_layers_fwd(C, N, Ns, mask, D, width, height, ptr(records), ptr(bg),
+                                              ptr(tl.tile_offsets), ptr(tl.tile_order), ptr(tl.flatten_arena),
+                                              _ptr3(renders), _ptr3(alphas), _ptr3(lasts), stream()),
+                  "mobgs_raster_layers_fwd")
+
         with profiler.region("raster_layers_fwd"):
-            while True:
-                check(lib.mobgs_raster_layers_fwd(C, N, Ns, mask, D, width, height, ptr(records), ptr(bg),
-                                                  ptr(tl.tile_offsets), ptr(tl.tile_order), ptr(tl.flatten_arena),
-                                                  _ptr3(renders), _ptr3(alphas), _ptr3(lasts), stream()),
-                      "mobgs_raster_layers_fwd")
-                if not tl.resolve():
-                    break
+            _composite_until_resolved(tl, launch, False)
         ctx.save_for_backward(records, bg, radii, *[t for t in alphas + lasts if t is not None])
         ctx.tl = tl
         ctx.meta = (C, N, channels, width, height, colors.dim() == 3, opacities.dim() == 2, Ns, mask)
@@ -1155,34 +1214,14 @@ class _RasterizeLayers(torch.autograd.Function):
                                               _ptr3(v_alphas), ptr(slots), ptr(slots_xy0), ptr(v_means2d_l0),
                                               ptr(v_means2d), ptr(v_conics), ptr(v_opac), ptr(v_colors), ptr(v_extra),
                                               ptr(tl.tiles_per_gauss), stream()), "mobgs_raster_layers_bwd")
-        if not colors_per_camera:
-            v_colors = v_colors.sum(0) if C > 1 else v_colors[0]
-        if not opac_per_camera:
-            v_opac = v_opac.sum(0) if C > 1 else v_opac[0]
-        return (v_means2d - v_means2d_l0, v_means2d_l0, v_conics, v_colors, v_opac, v_extra, None, None, None, None,
-                None, None, None)
-
-
-# True: render() lets the forward compositor decode its own image (SharedProjection.composite_decode); False: a separate
-# decoder launch, as before round 5 (A/B; results are bit-identical)
-FUSE_DECODER = os.environ.get("MOBGS_FUSE_DECODER", "1") != "0"
-# True (round 6): the backward half too -- rgb / depth are outputs of the compositing node itself and the decoder's backward
-# pass is the prologue of the backward compositor (mobgs_raster_bwd_decode); False: ops.Decode owns it (a launch of its
-# own + a 55-MB cotangent image).  Splat gradients are bit-identical either way, weight / pose gradients to summation order.
-FUSE_DECODER_BWD = os.environ.get("MOBGS_FUSE_DECODER_BWD", "1") != "0"
-# True: the decoder's weight / pose gradient sums run as extra workgroups of the gradient-slot reduction (no launch of their
-# own); False: mobgs_raster_bwd_decode_finish (A/B; same sums to summation order)
-WGRAD_IN_REDUCE = os.environ.get("MOBGS_WGRAD_IN_REDUCE", "1") != "0"
-# True: static-only / dynamic-only images (without the combined one) come from two class-restricted passes of the
-# single-set compositor over the combined lists (every splat belongs to exactly one class, so together they do the
-# work of ONE pass and share one gradient-slot buffer); False: from the generic 3-layer kernel
-CLASS_PASSES = True
+        return (v_means2d - v_means2d_l0, v_means2d_l0, v_conics, _fold_cameras(v_colors, colors_per_camera, C),
+                _fold_cameras(v_opac, opac_per_camera, C), v_extra, None, None, None, None, None, None, None)
 
 
 class _RasterizeClasses(torch.autograd.Function):
-    """Static-only and/or dynamic-only "RGB+D" renders over the lists of the whole set: mobgs_raster_class_fwd/bwd
-    (csrc/raster.hip with a class filter).  Returns (render_static, alpha_static, render_dynamic, alpha_dynamic);
-    classes not in `mask` (bit 1 = static, bit 2 = dynamic) are empty tensors."""
+    """Static-only and/or dynamic-only "RGB+D" renders over the lists of the whole set: one 10-channel class pass each
+    (_class_fwd / _class_bwd: csrc/raster.hip with a class filter).  Returns (render_static, alpha_static, render_dynamic,
+    alpha_dynamic); classes not in `mask` (bit 1 = static, bit 2 = dynamic) are empty tensors."""
 
     @staticmethod
     def forward(ctx, means2d, conics, colors, opacities, extra, backgrounds, radii, tl: TileLists, width, height, Ns,
@@ -1201,33 +1240,15 @@ class _RasterizeClasses(torch.autograd.Function):
             records = packed  # written by the projection kernel (SharedProjection(pack_colors=))
         else:
             _refuse_token(colors, None, "_RasterizeClasses")
-            records = torch.empty(C * N, lib.mobgs_record_stride(D), dtype=torch.float32, device=dev)
-            check(lib.mobgs_pack_records(C, N, channels, ptr(means2d), ptr(conics), ptr(colors),
-                                         1 if colors.dim() == 3 else 0, ptr(opacities),
-                                         1 if opacities.dim() == 2 else 0, ptr(extra), ptr(radii), ptr(records),
-                                         stream()), "mobgs_pack_records")
+            records = _pack_records(C, N, channels, means2d, conics, colors, opacities, extra, radii)
         outs = {}
-        # quadrant masks per list entry, written by the forward passes (each for the entries of its class) and read
-        # back by the backward passes over the same lists
-        reach = torch.empty(max(tl.flatten_arena.numel(), 1), dtype=torch.uint8, device=dev)
+        # one reach buffer: each forward pass writes the entries of its class, the backward passes read them back
+        reach = _new_reach(tl, dev)
         with profiler.region("raster_class_fwd"):
             for cls in (1, 2):
                 if not (mask >> cls) & 1:
                     continue
-                render = torch.empty(C, height, width, D, dtype=torch.float32, device=dev)
-                alphas = torch.empty(C, height, width, dtype=torch.float32, device=dev)
-                last = torch.empty(C, height, width, dtype=torch.int32, device=dev)
-                while True:
-                    if reach.numel() < tl.flatten_arena.numel():  # lists rebuilt into a larger arena
-                        reach = torch.empty(tl.flatten_arena.numel(), dtype=torch.uint8, device=dev)
-                    check(lib.mobgs_raster_class_fwd(C, N, Ns, cls, D, width, height, ptr(records), ptr(bg),
-                                                     ptr(tl.tile_offsets), ptr(tl.tile_order), ptr(tl.flatten_arena),
-                                                     ptr(render), ptr(alphas), ptr(last), ptr(reach), tuning.ref(),
-                                                     stream()),
-                          "mobgs_raster_class_fwd")
-                    if not tl.resolve():
-                        break
-                outs[cls] = (render, alphas, last)
+                *outs[cls], reach = _class_fwd(tl, records, bg, reach, C, N, Ns, cls, D, width, height, False)
                 _log_path("fwd", D, tl, class_filter=True, decode=False)
         saved = [records, bg, radii]
         for cls in (1, 2):
@@ -1245,14 +1266,12 @@ class _RasterizeClasses(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *cots):
-        lib = _lib_()
         C, N, channels, width, height, colors_per_camera, opac_per_camera, Ns, mask = ctx.meta
         records, bg, radii, *rest = ctx.saved_tensors
         tl = ctx.tl
         dev = records.device
         D = channels + 1
-        stride = records.shape[1]
-        slots = torch.zeros(max(tl.n_isects, 1), stride, dtype=torch.float32, device=dev)
+        slots = torch.zeros(max(tl.n_isects, 1), records.shape[1], dtype=torch.float32, device=dev)  # (no flag row)
         reach = ctx.reach if tl.flatten_arena is ctx.arena else None
         it = iter(rest)
         with profiler.region("raster_class_bwd"):
@@ -1265,31 +1284,15 @@ class _RasterizeClasses(torch.autograd.Function):
                     continue
                 v_render = f32c(v_render) if v_render is not None else torch.zeros(C, height, width, D, device=dev)
                 v_alpha = f32c(v_alpha) if v_alpha is not None else None
-                # the two classes own disjoint slots of the one buffer
                 # (the static class IS the reference's static set: its rows' dead channels take the short blend body)
                 tn = _tuning_variant(False, ctx.static_rows if cls == 1 else 0)
                 _log_path("bwd", D, tl, class_filter=True, tn=tn, static_rows=tn.static_rows)
-                check(lib.mobgs_raster_class_bwd(C, N, Ns, cls, D, width, height, ptr(records), ptr(bg), ptr(radii),
-                                                 ptr(tl.cum_tiles), ptr(tl.keep_scan), ptr(tl.tile_offsets),
-                                                 ptr(tl.tile_order), ptr(tl.flatten_ids), ptr(alphas), ptr(last),
-                                                 ptr(v_render), ptr(v_alpha), ptr(slots), ptr(reach), None,
-                                                 tn.ref(), stream()),
-                      "mobgs_raster_class_bwd")
-        v_means2d = torch.empty(C, N, 2, dtype=torch.float32, device=dev)
-        v_conics = torch.empty(C, N, 3, dtype=torch.float32, device=dev)
-        v_opac = torch.empty(C, N, dtype=torch.float32, device=dev)
-        v_colors = torch.empty(C, N, channels, dtype=torch.float32, device=dev)
-        v_extra = torch.empty(C, N, dtype=torch.float32, device=dev)
+                _class_bwd(tl, records, bg, radii, alphas, last, v_render, v_alpha, slots, reach, None, tn, C, N, Ns, cls, D,
+                           width, height)
         # (any_record: the lists' total -- zero when an arena overflowed without a host in the loop: no slot is read then)
-        check(lib.mobgs_raster_bwd_reduce(C, N, channels, 1, ptr(records), ptr(tl.cum_tiles), ptr(tl.keep_scan), ptr(slots),
-                                          ctypes.c_void_p(_lists_total_addr(tl)),
-                                          ptr(v_means2d), ptr(v_conics), ptr(v_opac), ptr(v_colors), ptr(v_extra),
-                                          ptr(tl.tiles_per_gauss), stream()), "mobgs_raster_bwd_reduce")
-        if not colors_per_camera:
-            v_colors = v_colors.sum(0) if C > 1 else v_colors[0]
-        if not opac_per_camera:
-            v_opac = v_opac.sum(0) if C > 1 else v_opac[0]
-        return v_means2d, v_conics, v_colors, v_opac, v_extra, None, None, None, None, None, None, None, None, None
+        v_means2d, v_conics, v_opac, v_colors, v_extra = _reduce_slots(tl, records, slots, "total", C, N, channels, True)
+        return (v_means2d, v_conics, _fold_cameras(v_colors, colors_per_camera, C),
+                _fold_cameras(v_opac, opac_per_camera, C), v_extra, None, None, None, None, None, None, None, None, None)
 
 
 _cap_listed = {}  # workload key -> capacity of the listed-intersection buffers
@@ -1306,7 +1309,6 @@ class _ProjectAndBin(torch.autograd.Function):
         intersections (include/mobgs_hip.h, enum_order).  Only the single-pass path takes it; results do not depend on it.
         prep (internal, _PrepProjectAndBin): the 16 raw inputs of ops.PrepSplats -- the projection kernel builds the
         per-splat state itself; means / quats / scales / opacities are then uninitialised OUTPUT buffers."""
-        import ctypes
         lib = _lib_()
         means, quats, scales, viewmats, Ks, opac = map(f32c, (means, quats, scales, viewmats, Ks, opacities))
         if prep is not None and not (SPECULATIVE_BINNING and _fast.get() is not None):
@@ -1487,9 +1489,8 @@ class _ProjectAndBin(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, _v_radii, v_means2d, v_depths, v_conics, _v_tpg):
-        grads = _Project.backward(ctx, _v_radii, v_means2d, v_depths, v_conics, _v_tpg)
-        return (grads[0], grads[1], grads[2], grads[3], None, None, None, None, None, None, None, None, None, None,
-                None, None)
+        return (*_project_bwd(ctx.saved_tensors, ctx.dims, v_means2d, v_depths, v_conics), None, None, None, None, None, None,
+                None, None, None, None, None, None)
 
 
 class _CtxShim:
@@ -1547,16 +1548,13 @@ class _PrepProjectAndBin(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, v_means, v_quats, v_scales, v_opac, v_cols, _v_radii, v_means2d, v_depths, v_conics, _v_tpg):
-        from types import SimpleNamespace
-        from .ops import PrepSplats
         saved = ctx.saved_tensors
         means, quats, scales = saved[0], saved[1], saved[2]
         times, d_ncp, d_trbf, opac = saved[7:11]
         F = _fast.get()
         if FUSE_PREP_BWD and F is not None:
             # ONE launch: the state cotangents never leave the registers (mobgs_project_prep_bwd_fused)
-            from . import ops as _ops
-            sink = _ops._active_sink
+            sink = ops._active_sink
             use_sink = sink is not None and sink.accepts(ctx.leaf_inputs)
             have = use_sink and sink.buffers is not None
             Ns, Nd = ctx.sizes
@@ -1564,9 +1562,9 @@ class _PrepProjectAndBin(torch.autograd.Function):
             bufs, v_viewmats = F.project_prep_bwd(
                 width, height, eps2d, means, quats, scales, saved[3], saved[4], saved[5], saved[6], v_means2d, v_depths,
                 v_conics, v_means, v_quats, v_scales, Ns, Nd, times, d_ncp, d_trbf, opac, v_opac, v_cols,
-                [sink.buffers[n_] for n_ in _ops._LEAF_NAMES] if have else [], 1 if have else 0, stream_int(),
+                [sink.buffers[n_] for n_ in ops._LEAF_NAMES] if have else [], 1 if have else 0, stream_int(),
                 bool(ctx.needs_input_grad[16]))
-            g = sink.buffers if have else dict(zip(_ops._LEAF_NAMES, bufs))
+            g = sink.buffers if have else dict(zip(ops._LEAF_NAMES, bufs))
             if use_sink:
                 sink.buffers = g
                 return (None,) * 16 + (v_viewmats,) + (None,) * 9
@@ -1575,16 +1573,14 @@ class _PrepProjectAndBin(torch.autograd.Function):
                     g["d_ft"], None, v_viewmats) + (None,) * 9
         pm = pq = ps = v_viewmats = None
         if v_means2d is not None or v_depths is not None or v_conics is not None:
-            pm, pq, ps, v_viewmats = _Project.backward(SimpleNamespace(saved_tensors=saved[:7], dims=ctx.dims), None,
-                                                       v_means2d, v_depths, v_conics, None)[:4]
+            pm, pq, ps, v_viewmats = _project_bwd(saved[:7], ctx.dims, v_means2d, v_depths, v_conics)
         # cotangents that reach the state directly (a loss on out["d_means3d"], a scale regulariser, ...)
         pm = v_means if pm is None else (pm if v_means is None else pm + v_means)
         pq = v_quats if pq is None else (pq if v_quats is None else pq + v_quats)
         ps = v_scales if ps is None else (ps if v_scales is None else ps + v_scales)
-        f32 = torch.float32
-        g = PrepSplats.backward(SimpleNamespace(saved_tensors=(times, d_ncp, d_trbf, scales, opac), sizes=ctx.sizes,
-                                                leaf_inputs=ctx.leaf_inputs, half=False, attr_dtypes=(f32,) * 11),
-                                pm, pq, ps, v_opac, v_cols)
+        # (the state this node built is float32 whatever the leaves are: no half kernel, no cast back)
+        g = ops.prep_backward((times, d_ncp, d_trbf, scales, opac), ctx.sizes, ctx.leaf_inputs, False, (), pm, pq, ps, v_opac,
+                              v_cols)
         return (*g, v_viewmats, None, None, None, None, None, None, None, None, None)
 
 
