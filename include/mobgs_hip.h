@@ -15,6 +15,7 @@
  *   /root/reference/utils/loss_utils.py:233-239,351-381     L1 + SSIM
  *   /root/reference/main_utils.py:95-141                    normals from depth
  *   /root/reference/scene/gaussian_model.py:1044-1244,1352-1356,1480-1506   densification / optimiser surgery
+ *   /root/reference/scene/gaussian_model.py:420,514         simple_knn distCUDA2 (initial scales)
  *
  * Conventions
  *   - every pointer is a DEVICE pointer unless the name ends in _host;
@@ -146,7 +147,7 @@ int mobgs_cotangent_probe(int n_arrays, const float* const* arrays, const size_t
  * points changes (round 4 inserted `records` into mobgs_raster_bwd_reduce and changed the gradient-slot format without
  * one: a stale host extension would have passed shifted pointers).  Bindings compare it with the MOBGS_ABI_VERSION
  * they were built against and refuse to run on a mismatch (mobgs_amd/_lib.py, csrc/fastpath.cpp). */
-#define MOBGS_ABI_VERSION 9
+#define MOBGS_ABI_VERSION 10
 int mobgs_abi_version(void);
 /* Text of the last error raised on the calling thread ("" if none). */
 const char* mobgs_last_error(void);
@@ -850,6 +851,19 @@ typedef struct MobgsAdamTensor {
 } MobgsAdamTensor;
 int mobgs_adam_step(int n_tensors, const MobgsAdamTensor* tensors_host, double beta1, double beta2, double eps,
                     void* stream);
+
+/* ---- K17: exact 3-nearest-neighbour mean squared distance (scene initialisation) ---------------------------------
+ * Replaces simple_knn._C.distCUDA2, the CUDA-only extension behind every initial scale of
+ * /root/reference/scene/gaussian_model.py:420,514 (create_from_pcd_dynamic / create_from_pcd).
+ *   dist2[i] = (d0 + d1 + d2) / 3, the three smallest |p_i - p_j|^2 over j != i (self excluded by INDEX: a duplicate
+ *   point counts with distance 0), each evaluated in fp32 as (dx dx + dy dy) + dz dz without FMA contraction.
+ * Exact for every row order: rows are pruned in boxes of consecutive rows, and a box is skipped only when its fp32
+ * distance bound proves that it cannot change the result; the order decides the speed only (callers pass rows sorted
+ * along a Morton curve, mobgs_amd.scene_init).  Bit-reproducible; no atomics.
+ * n < 4 (fewer than three neighbours) and n > 2^30 are refused before any launch; mobgs_knn3_scratch_bytes returns
+ * 0 for them.  scratch: 16-byte aligned, at least mobgs_knn3_scratch_bytes(n) bytes. */
+size_t mobgs_knn3_scratch_bytes(int n);
+int mobgs_knn3_mean_dist2(int n, const float* points, float* dist2, void* scratch, size_t scratch_bytes, void* stream);
 
 #ifdef __cplusplus
 }

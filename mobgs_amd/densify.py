@@ -338,6 +338,37 @@ class TrainableGaussians(GaussianParams):
             pc.rgbdecoder.load_state_dict(torch.load(pt, map_location=device))
         return pc
 
+    # ---- creation from data (scene/gaussian_model.py:495-582, :406-493) ------------------------------------------------
+    @classmethod
+    def _from_init(cls, params, extras, spatial_lr_scale, is_dynamic, device, decoder, capacity_factor, spatial_sort):
+        pc = cls(params, extras, decoder=decoder, device=device, capacity_factor=capacity_factor)
+        pc.is_dynamic = is_dynamic   # (rows of a static set are ordered by their positions, not by control points)
+        pc.spatial_lr_scale = spatial_lr_scale
+        pc.pcd_order = pc.spatial_sort_() if spatial_sort else None
+        return pc
+
+    @classmethod
+    def from_pcd(cls, pcd, spatial_lr_scale: float, time_line: int = 0, *, sh_degree: int = 0, trbfslinit=None,
+                 device="cuda", decoder=None, capacity_factor: float = 1.5, spatial_sort: bool = True):
+        """create_from_pcd (:495-582): a static set from a point cloud `pcd` (.points [N,3], .colors [N,3] in [0,1],
+        .times [N,1]); `time_line` is unused, as in the reference.  Initial scales: the 3-NN kernel (csrc/knn.hip).
+        One deviation: the reference draws the static set's control_xyz from a normal distribution (:527) and no
+        kernel reads it; here it keeps GaussianParams' default.  spatial_sort: store the rows along a Morton curve
+        (spatial_sort_(); row i of the set is then row pcd_order[i] of `pcd`), False keeps the order of `pcd`."""
+        from . import scene_init
+        params, extras = scene_init.static_init(pcd, device, sh_degree, trbfslinit)
+        return cls._from_init(params, extras, spatial_lr_scale, False, device, decoder, capacity_factor, spatial_sort)
+
+    @classmethod
+    def from_pcd_dynamic(cls, pcd, spatial_lr_scale: float, time_line: int, dyn_tracjectory, *, sh_degree: int = 0,
+                         trbfslinit=None, device="cuda", decoder=None, capacity_factor: float = 1.5,
+                         spatial_sort: bool = True):
+        """create_from_pcd_dynamic (:406-493): as from_pcd, with 12 spline control points per point fitted to its tracked
+        trajectory `dyn_tracjectory` [N, T, 3] at T uniform times (scene_init.inverse_cubic_hermite)."""
+        from . import scene_init
+        params, extras = scene_init.dynamic_init(pcd, dyn_tracjectory, device, sh_degree, trbfslinit)
+        return cls._from_init(params, extras, spatial_lr_scale, True, device, decoder, capacity_factor, spatial_sort)
+
     # ---- introspection for tests ------------------------------------------------------------------------------------
     def table_state(self) -> Dict[str, torch.Tensor]:
         if self.optimizer is not None:

@@ -2,7 +2,8 @@
 
 `GaussianParams` exposes the attributes/properties of the reference's `GaussianModel` that render()/get_flow()
 read (/root/reference/scene/gaussian_model.py:91-106 activations, :209-254 accessors; parameter shapes from
-create_from_pcd* :406-582).  Optimiser surgery, densification and PLY I/O stay with the caller (out of scope).
+create_from_pcd* :406-582).  Optimiser surgery, densification, PLY I/O and creation from a point cloud are
+`mobgs_amd.densify.TrainableGaussians` (from_ply / from_pcd / from_pcd_dynamic), a subclass of it.
 """
 from __future__ import annotations
 

@@ -1,0 +1,217 @@
+"""Building a Gaussian set from data: what the reference does before its first render().
+
+    knn3_mean_dist2(points)                       simple_knn._C.distCUDA2 (CUDA-only upstream) -> csrc/knn.hip
+    inverse_cubic_hermite(curves, times, N_pts)   /root/reference/scene/gaussian_model.py:18-88
+    static_init(...) / dynamic_init(...)          the tensors of create_from_pcd (:495-582) / create_from_pcd_dynamic
+                                                  (:406-493), as the constructor dictionaries of
+                                                  densify.TrainableGaussians (from_pcd / from_pcd_dynamic)
+
+The 3-NN kernel is exact for any row order and prunes by boxes of consecutive rows; `knn3_mean_dist2` hands it the
+points sorted along a 63-bit Morton curve (21 bits per axis over the cloud's bounding cube, one torch.sort) and
+scatters the result back.  The spline fit of the reference is one least-squares problem per point over a design
+matrix that is the same for every point in every call the reference makes: that case is one float64
+pseudo-inverse on the host and one matrix product on the device.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check, ptr, stream
+
+SH_C0 = 0.28209479177387814   # utils/sh_utils.py:26
+CONTROL_NUM = 12              # GaussianModel.control_num (:111)
+
+
+# ---- 3-NN mean squared distance ----------------------------------------------------------------------------------
+def morton_order(points: torch.Tensor) -> torch.Tensor:
+    """int64 [N]: the rows of `points` [N,3] along a Z-order curve, 21 bits per axis over the bounding CUBE (one scale
+    for the three axes: cells stay cubes in space, however flat the cloud).  rendering.spatial_order is the 10-bit
+    precedent; at 1 M points 10 bits leave hundreds of points per cell."""
+    m = points.detach().reshape(-1, 3).to(torch.float32)
+    lo, hi = m.min(0).values, m.max(0).values
+    scale = 2097151.0 / (hi - lo).max().clamp_min(1e-30)
+    q = ((m - lo) * scale).clamp_(0, 2097151).to(torch.int64)
+
+    def spread(v):  # 21 bits -> every third bit
+        v = (v | (v << 32)) & 0x1F00000000FFFF
+        v = (v | (v << 16)) & 0x1F0000FF0000FF
+        v = (v | (v << 8)) & 0x100F00F00F00F00F
+        v = (v | (v << 4)) & 0x10C30C30C30C30C3
+        v = (v | (v << 2)) & 0x1249249249249249
+        return v
+    code = spread(q[:, 0]) | (spread(q[:, 1]) << 1) | (spread(q[:, 2]) << 2)
+    return torch.argsort(code)
+
+
+def knn3_sorted(points: torch.Tensor) -> torch.Tensor:
+    """mobgs_knn3_mean_dist2 on the rows as they are (fast when neighbouring rows are neighbours in space)."""
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"points must be [N,3], got {tuple(points.shape)}")
+    lib = _lib.load()
+    pts = _lib.f32c(points.detach())
+    n = int(pts.shape[0])
+    p = ptr(pts)   # (raises for CPU tensors: there is no CPU path)
+    nbytes = int(lib.mobgs_knn3_scratch_bytes(n))
+    scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=pts.device)
+    out = torch.empty(n, dtype=torch.float32, device=pts.device)
+    check(lib.mobgs_knn3_mean_dist2(n, p, ptr(out), ptr(scratch), nbytes, stream()), "mobgs_knn3_mean_dist2")
+    return out
+
+
+def knn3_mean_dist2(points: torch.Tensor) -> torch.Tensor:
+    """[N] float32: for every point the mean of the squared distances to its three nearest neighbours (the point itself
+    excluded by index; fp32 (dx dx + dy dy) + dz dz).  Exact, bit-reproducible and independent of the row order."""
+    if not points.is_cuda:
+        raise RuntimeError("mobgs_amd: tensors must live on a HIP device (device='cuda'); there is no CPU path")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"points must be [N,3], got {tuple(points.shape)}")
+    pts = _lib.f32c(points.detach())
+    if pts.shape[0] < 4:
+        return knn3_sorted(pts)   # refused by the library with its message, before any launch
+    order = morton_order(pts)
+    d_sorted = knn3_sorted(pts[order])
+    out = torch.empty_like(d_sorted)
+    out[order] = d_sorted
+    return out
+
+
+# ---- spline fit ----------------------------------------------------------------------------------------------------
+def hermite_design(times: torch.Tensor, N_pts: int) -> torch.Tensor:
+    """float64 [..., T, N_pts]: row t holds the weights with which the N_pts control points give the cubic Hermite spline
+    at times[..., t] (gaussian_model.py:24-81: segment index clamped to [0, N-2], neighbours clamped to [0, N-1],
+    one-sided derivatives where the clamp bites)."""
+    N = int(N_pts)
+    ts = times.to(torch.float64) * (N - 1)
+    idx = torch.clamp(torch.floor(ts).long(), 0, N - 2)
+    il = torch.clamp(idx - 1, 0, N - 1)
+    ir = torch.clamp(idx + 1, 0, N - 1)
+    irr = torch.clamp(idx + 2, 0, N - 1)
+    t = ts - idx.to(torch.float64)
+    h00 = (1 + 2 * t) * (1 - t) ** 2
+    h10 = t * (1 - t) ** 2
+    h01 = t ** 2 * (3 - 2 * t)
+    h11 = t ** 2 * (t - 1)
+    zero = torch.zeros_like(t)
+    first, last = il == idx, irr == ir
+    p0 = torch.where(first, zero, -h10 / 2)
+    p1 = h00 + torch.where(first, -h10, zero) + torch.where(last, -h11, -h11 / 2)
+    p2 = h01 + torch.where(first, h10, h10 / 2) + torch.where(last, h11, zero)
+    p3 = torch.where(last, zero, h11 / 2)
+    A = torch.zeros(tuple(times.shape) + (N,), dtype=torch.float64, device=times.device)
+    for i, c in ((il, p0), (idx, p1), (ir, p2), (irr, p3)):
+        A.scatter_add_(-1, i[..., None], c[..., None])
+    return A
+
+
+def _times_2d(times: torch.Tensor, B: int) -> torch.Tensor:
+    t = times
+    if t.dim() == 3 and t.shape[-1] == 1:
+        t = t[..., 0]
+    if t.dim() == 1:
+        t = t[None, :].expand(B, -1)
+    if t.dim() != 2 or t.shape[0] != B:
+        raise ValueError(f"times must be [B,T,1], [B,T] or [T] with B = {B}, got {tuple(times.shape)}")
+    return t
+
+
+def inverse_cubic_hermite(curves: torch.Tensor, times: torch.Tensor, N_pts: int = CONTROL_NUM, scale: float = 0.8,
+                          return_error: bool = False):
+    """gaussian_model.py:18-88: control points [B, N_pts, C] of the cubic Hermite splines that fit `curves` [B, T, C]
+    sampled at `times` [B, T, 1] in the least-squares sense.  (`scale` is unused there too.)
+
+    Shared times -- one vector expanded over the batch, as in every call the reference makes (:436-439) -- take no
+    per-point factorisation: one float64 pseudo-inverse of the [T, N_pts] design matrix on the host, applied to the
+    whole batch with one float64 matrix product on the curves' device.  Rows with differing times go through a
+    batched float64 torch.linalg.lstsq (correct, not fast).  A rank-deficient design (T < N_pts among others) raises
+    ValueError: the reference returns whatever its LAPACK driver makes of it."""
+    if curves.dim() != 3:
+        raise ValueError(f"curves must be [B,T,C], got {tuple(curves.shape)}")
+    B, T, _ = curves.shape
+    N = int(N_pts)
+    t2 = _times_2d(times, B)
+    if t2.shape[1] != T:
+        raise ValueError(f"times has {t2.shape[1]} samples, curves {T}")
+    if N < 2:
+        raise ValueError("N_pts must be at least 2")
+    if T < N:
+        raise ValueError(f"rank-deficient fit: {T} samples cannot determine {N} control points")
+    shared = B <= 1 or t2.stride(0) == 0 or bool((t2 == t2[:1]).all())
+    if shared:
+        A = hermite_design(t2[0].detach().cpu(), N)                      # [T, N] float64, host
+        if int(torch.linalg.matrix_rank(A)) < N:
+            raise ValueError(f"rank-deficient fit: the [{T}, {N}] design matrix of these times has rank "
+                             f"{int(torch.linalg.matrix_rank(A))}")
+        pinv = torch.linalg.pinv(A).to(curves.device)                    # [N, T]
+        sol = torch.einsum("kt,btc->bkc", pinv, curves.detach().to(torch.float64))
+    else:
+        A = hermite_design(t2.detach(), N)                               # [B, T, N] float64
+        rank = torch.linalg.matrix_rank(A)
+        if bool((rank < N).any()):
+            raise ValueError(f"rank-deficient fit: {int((rank < N).sum())} of {B} design matrices have rank < {N}")
+        sol = torch.linalg.lstsq(A, curves.detach().to(torch.float64)).solution
+    control = sol.to(curves.dtype)
+    if return_error:
+        alt = torch.linalg.pinv(hermite_design(t2.detach(), N)) @ curves.detach().to(torch.float64)
+        return control, torch.dist(sol, alt).to(curves.dtype)
+    return control
+
+
+# ---- the initial state of a set ------------------------------------------------------------------------------------
+def _pcd_tensors(pcd) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    f = lambda a: torch.as_tensor(np.asarray(a)).float().cpu()  # noqa: E731
+    points, colors, times = f(pcd.points), f(pcd.colors), f(pcd.times)
+    if points.dim() != 2 or points.shape[1] != 3 or colors.shape != points.shape:
+        raise ValueError(f"pcd.points / pcd.colors must be [N,3], got {tuple(points.shape)} / {tuple(colors.shape)}")
+    return points, colors, times.reshape(points.shape[0], -1)
+
+
+def _common_init(pcd, device, sh_degree: int, trbfslinit: Optional[float]):
+    """The part create_from_pcd and create_from_pcd_dynamic share (:408-425 / :497-519, :445-476 / :534-565).  A point
+    cloud arrives on the host; the closed-form tensors (RGB -> SH, the opacity constant) are formed there, so that they
+    are the reference's values to the bit, and copied once.  Only the scales are computed on the device."""
+    points, colors, times = _pcd_tensors(pcd)
+    n = points.shape[0]
+    sh = ((colors - 0.5) / SH_C0).to(device)
+    points = points.to(device)
+    dist2 = torch.clamp_min(knn3_mean_dist2(points), 0.0000001)
+    z = lambda *s: torch.zeros(n, *s, dtype=torch.float32, device=device)  # noqa: E731
+    rots = z(4)
+    rots[:, 0] = 1
+    tenth = 0.1 * torch.ones(n, 1, dtype=torch.float)
+    params = {"xyz": points, "scaling": torch.log(torch.sqrt(dist2))[..., None].repeat(1, 3), "rotation": rots,
+              "opacity": torch.log(tenth / (1 - tenth)).to(device), "features_dc": torch.cat((sh, sh), dim=1),
+              "features_t": z(3)}
+    extras = {"omega": z(4), "zeta": z(1), "motion": z(9), "trbf_center": times.contiguous().to(device),
+              "trbf_scale": torch.full((n, 1), 0.0 if trbfslinit is None else float(trbfslinit), dtype=torch.float32,
+                                       device=device),
+              "f_rest": z((sh_degree + 1) ** 2, 3),
+              "current_control_num": torch.full((n, 1), CONTROL_NUM, dtype=torch.int64, device=device)}
+    return params, extras
+
+
+def static_init(pcd, device="cuda", sh_degree: int = 0, trbfslinit: Optional[float] = None
+                ) -> Tuple[Dict[str, torch.Tensor], Dict[str, torch.Tensor]]:
+    """(params, extras) of create_from_pcd.  control_xyz is absent: the reference fills it with random numbers (:527)
+    that nothing reads for a static set, GaussianParams' default stands in."""
+    return _common_init(pcd, device, sh_degree, trbfslinit)
+
+
+def dynamic_init(pcd, dyn_tracjectory, device="cuda", sh_degree: int = 0, trbfslinit: Optional[float] = None
+                 ) -> Tuple[Dict[str, torch.Tensor], Dict[str, torch.Tensor]]:
+    """(params, extras) of create_from_pcd_dynamic: as the static set, plus the control points fitted to the tracked
+    trajectories [N, T, 3] at T uniform times (:436-440)."""
+    params, extras = _common_init(pcd, device, sh_degree, trbfslinit)
+    traj = torch.as_tensor(dyn_tracjectory).float().to(device)
+    n = params["xyz"].shape[0]
+    if traj.dim() != 3 or traj.shape[0] != n or traj.shape[2] != 3:
+        raise ValueError(f"dyn_tracjectory must be [{n}, T, 3], got {tuple(traj.shape)}")
+    T = traj.shape[1]
+    time_step = 1 / (T - 1.0)
+    t_step = torch.arange(0, 1 + time_step, time_step).float()[:T].to(device)
+    t_step = t_step[None, :, None].expand(n, -1, -1)
+    extras["control_xyz"] = inverse_cubic_hermite(traj * 1e2, t_step, N_pts=CONTROL_NUM)
+    return params, extras
