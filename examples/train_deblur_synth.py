@@ -114,6 +114,17 @@ class DeblurTrainer:
         self.view_buckets = ([FlatGradients(params, extra={f"view{v}": 3 * (ns + nd)}) for v in range(n_views)]
                              if shard.collective else None)
 
+    def prune_viewpoints(self, n=8):
+        """Cameras for TrainableGaussians.onedown_control_pts, with the attributes the reference's compute_prune_error
+        reads (metadata.focal_length, image_width / image_height, time, world_view_transform): a short path of `n` poses
+        over the whole time range (the first and the last are skipped by the error measure)."""
+        import types
+        c0 = self.cams[0]
+        md = types.SimpleNamespace(focal_length=float(c0.K[0, 0]))
+        return [types.SimpleNamespace(metadata=md, image_width=c0.image_width, image_height=c0.image_height,
+                                      time=i / (n - 1.0), world_view_transform=view_pose(i).transpose(0, 1).contiguous())
+                for i in range(n)]
+
     def _iteration_sharded(self) -> torch.Tensor:
         """N > 1: the same iteration with its loss kept apart per view, so that the backward pass runs view by view and
         each view's gradient message (with its densification statistics) is all-reduced on the communication stream while
@@ -308,12 +319,17 @@ class DeblurTrainer:
 
 
 def train(dev="cuda:0", iters=40, ns=4000, nd=2000, width=256, height=192, n_views=2, seed=0, lambda_flow=1e-2,
-          shard=None, log=None, graph=False):
+          shard=None, log=None, graph=False, prune_control_every=0):
     """graph=True (single process): forward + losses + backward of the iteration recorded ONCE as a HIP graph
     (mobgs_amd.graphed.GraphedCallable) and replayed, the Adam step outside -- for small images / few Gaussians, where an
-    iteration is ~1400 launches and bound by the host (the reference's own 512x288 / 30 k operating point: 9.5 -> 7.5 ms)."""
+    iteration is ~1400 launches and bound by the host (the reference's own 512x288 / 30 k operating point: 9.5 -> 7.5 ms).
+    prune_control_every=K > 0: every K iterations, between two iterations and outside any capture, the dynamic set drops
+    one spline control point where that moves the projected trajectory by at most dyn.error_threshold pixels
+    (TrainableGaussians.onedown_control_pts; in place, so a recorded iteration stays valid) and the smallest count is
+    logged as train.py:734 does (MinCtrl)."""
     t = DeblurTrainer(dev, ns, nd, width, height, n_views, seed, lambda_flow, shard, iters)
     history = []
+    prune_views = t.prune_viewpoints() if prune_control_every else None
     fb, pending = None, []
     for it in range(1, iters + 1):
         if graph and it == 2 and not t.shard.collective:   # (iteration 1 ran eagerly: arenas and hints exist)
@@ -337,6 +353,10 @@ def train(dev="cuda:0", iters=40, ns=4000, nd=2000, width=256, height=192, n_vie
             history.append(float(photo))
         else:
             history.append(float(t.iteration()))
+        if prune_control_every and it % prune_control_every == 0:
+            pruned = t.dyn.onedown_control_pts(prune_views)
+            if t.shard.rank == 0:
+                print(f"it {it:4d}  one control point down on {int(pruned)} rows  MinCtrl {int(t.dyn.current_control_num.min())}")
         if it == 2:   # everything long-lived exists now: keep Python's cyclic collector off it (66 ms per generation-2
             import gc  # pass over a torch process's objects on this host, in the middle of an iteration: DESIGN section 5)
             gc.collect()
@@ -354,6 +374,8 @@ if __name__ == "__main__":
     ap.add_argument("--width", type=int, default=512)
     ap.add_argument("--height", type=int, default=288)
     ap.add_argument("--graph", action="store_true", help="replay forward + backward as one HIP graph (single process)")
+    ap.add_argument("--prune-control-every", type=int, default=0, metavar="K",
+                    help="every K iterations drop one spline control point where the trajectory moves <= 1 px (0 = never)")
     a = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -361,4 +383,5 @@ if __name__ == "__main__":
         import torch.distributed as dist
         torch.cuda.set_device(local)
         dist.init_process_group("nccl", device_id=torch.device("cuda", local))
-    train(dev=f"cuda:{local}", iters=a.iters, ns=a.ns, nd=a.nd, width=a.width, height=a.height, log=10, graph=a.graph)
+    train(dev=f"cuda:{local}", iters=a.iters, ns=a.ns, nd=a.nd, width=a.width, height=a.height, log=10, graph=a.graph,
+          prune_control_every=a.prune_control_every)

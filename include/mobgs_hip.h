@@ -147,7 +147,7 @@ int mobgs_cotangent_probe(int n_arrays, const float* const* arrays, const size_t
  * points changes (round 4 inserted `records` into mobgs_raster_bwd_reduce and changed the gradient-slot format without
  * one: a stale host extension would have passed shifted pointers).  Bindings compare it with the MOBGS_ABI_VERSION
  * they were built against and refuse to run on a mismatch (mobgs_amd/_lib.py, csrc/fastpath.cpp). */
-#define MOBGS_ABI_VERSION 10
+#define MOBGS_ABI_VERSION 11
 int mobgs_abi_version(void);
 /* Text of the last error raised on the calling thread ("" if none). */
 const char* mobgs_last_error(void);
@@ -864,6 +864,25 @@ int mobgs_adam_step(int n_tensors, const MobgsAdamTensor* tensors_host, double b
  * 0 for them.  scratch: 16-byte aligned, at least mobgs_knn3_scratch_bytes(n) bytes. */
 size_t mobgs_knn3_scratch_bytes(int n);
 int mobgs_knn3_mean_dist2(int n, const float* points, float* dist2, void* scratch, size_t scratch_bytes, void* stream);
+
+/* ---- K18: drop one spline control point per dynamic Gaussian (motion-adaptive splines) -----------------------------
+ * The reference's scene/gaussian_model.py:274-371 (onedown_control_pts: inverse_cubic_hermite_for_prune,
+ * compute_prune_error and the commit) in ONE launch.  A row with n = control_num[i] in 5..12 points is refitted with
+ * m = n - 1 points, new[j] = sum_k P_n[j][k] old[k] with P_n = pinv_table[n - 5] (float32 [8,11,12], zero-padded: the
+ * float64 pseudo-inverse of the [n, m] Hermite design matrix at the old knot times k / (n - 1); the caller builds it,
+ * mobgs_amd.scene_init.one_down_tables).  Both splines are evaluated at times[v] of the interior views v = 1..V-2,
+ * scaled by 1e-2, transformed with viewmats[v] (row-major world-to-camera, column vectors, divide by w + 1e-7),
+ * projected with K = [focal, 0, cx; 0, focal, cy; 0, 0, 1] (divide by z + 1e-7), and the pixel distances averaged into
+ * err_out[i].  new_control_out (or NULL) receives the m fitted points followed by zeros up to slot 10.
+ * commit != 0: where err_out[i] <= threshold, slots 0..10 of control_xyz[i] := the fitted points and zeros (slot 11
+ * stays), control_num[i] := m, and counters[0] grows by the number of such rows.  commit == 0 writes no input.
+ * Rows with n == 4 are not candidates (deliberately unlike the reference, whose floor at 4 halves the fourth point):
+ * error 0, never written, their own points in new_control_out.  A count outside 4..12 is never used as an index: the
+ * row is skipped and counted in counters[1].  The caller clears counters[0..1] beforehand; nothing synchronises.
+ * Refused before any launch: n_views < 3, n_rows < 0, a NULL table or buffer.  n_rows == 0 is a no-op. */
+int mobgs_control_onedown(int n_rows, int n_views, const float* viewmats, const float* times, float focal, float cx,
+                          float cy, const float* pinv_table, float threshold, float* control_xyz, int64_t* control_num,
+                          float* err_out, float* new_control_out, int* counters, int commit, void* stream);
 
 #ifdef __cplusplus
 }

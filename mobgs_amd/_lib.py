@@ -52,7 +52,7 @@ class MobgsPrepInputs(ctypes.Structure):
 
 
 P = c_void_p
-ABI_VERSION = 10  # include/mobgs_hip.h MOBGS_ABI_VERSION
+ABI_VERSION = 11  # include/mobgs_hip.h MOBGS_ABI_VERSION
 _SIGS = {
     "mobgs_version": (c_char_p, []),
     "mobgs_abi_version": (c_int, []),
@@ -152,6 +152,8 @@ _SIGS = {
     "mobgs_deform_mlp_bwd": (c_int, [c_int] + [P] * 20 + [P]),
     "mobgs_knn3_scratch_bytes": (c_size_t, [c_int]),
     "mobgs_knn3_mean_dist2": (c_int, [c_int, P, P, P, c_size_t, P]),
+    "mobgs_control_onedown": (c_int, [c_int, c_int, P, P, c_float, c_float, c_float, P, c_float, P, P, P, P, P, c_int,
+                                      P]),
 }
 # entry points added by later translation units (bound if present in the header AND the library)
 _OPTIONAL_SIGS = {}

@@ -10,6 +10,7 @@ per-splat statistics arrays, and offers the reference's method names with the re
     densify_and_splitv2(grads, thr, extent, N)   :1207-1244
     densify_pruneclone(thr, min_opacity, extent, max_screen_size, splitN)   :1417-1434
     prune_points(mask)                       :1066-1089
+    onedown_control_pts(viewpoints)          :274-371 (scene_init.onedown_control_pts: csrc/control_prune.hip)
     reset_opacity()                          :897-903
 
 Where the reference re-allocates every group with ~50 index / cat / repeat calls per operation, every field lives
@@ -307,6 +308,19 @@ class TrainableGaussians(GaussianParams):
         sel = self._indices_of(split, 1)
         cl = self._indices_of(clone, 1)
         self._split_into(keep, [-(cl + 1)], sel, splitN, samples)
+
+    @torch.no_grad()
+    def onedown_control_pts(self, viewpoints):
+        """gaussian_model.py:274-290 on the live rows of the table: scene_init.onedown_control_pts (one launch, in
+        place, no host synchronisation) -> the number of rows pruned as a 0-dim device tensor.  Shapes, Parameters and
+        the optimiser's keys stay what they were (a captured iteration stays valid); the Adam moments of control_xyz are
+        left alone, as in the reference.  The kernel writes through raw pointers: the renderer's caches are told, and
+        the version counters of the two tensors move."""
+        from . import gaussian_renderer as _GR
+        from .scene_init import onedown_control_pts
+        pruned = onedown_control_pts(self, viewpoints, self.error_threshold)
+        _GR.parameters_changed()
+        return pruned
 
     @torch.no_grad()
     def reset_opacity(self):

@@ -16,6 +16,8 @@ from .helper_model import Sandwich
 
 
 class GaussianParams:
+    error_threshold = 1.0   # px: scene_init.onedown_control_pts keeps a shorter spline up to this mean shift (:112)
+
     def __init__(self, params: Dict[str, torch.Tensor], dynamic: Optional[Dict[str, torch.Tensor]] = None,
                  decoder: Optional[torch.nn.Module] = None, device="cpu", requires_grad: bool = False,
                  attr_dtype: torch.dtype = torch.float32):

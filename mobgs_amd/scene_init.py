@@ -215,3 +215,156 @@ def dynamic_init(pcd, dyn_tracjectory, device="cuda", sh_degree: int = 0, trbfsl
     t_step = t_step[None, :, None].expand(n, -1, -1)
     extras["control_xyz"] = inverse_cubic_hermite(traj * 1e2, t_step, N_pts=CONTROL_NUM)
     return params, extras
+
+
+# ---- motion-adaptive splines: one control point down -----------------------------------------------------------------
+MIN_CONTROL_NUM = 4           # onedown_control_pts floors the count here (:279)
+_one_down_cache: Dict[str, torch.Tensor] = {}
+
+
+def one_down_design(n: int) -> torch.Tensor:
+    """float64 [n, n-1]: the design matrix of refitting a spline of n control points (knot times k / (n - 1)) with
+    n - 1 points: rows 0..n-1 / columns 0..n-2 of the [12, 11] system of inverse_cubic_hermite_for_prune (:310-371); its
+    remaining rows only force the remaining columns to zero."""
+    n = int(n)
+    if not MIN_CONTROL_NUM < n <= CONTROL_NUM:
+        raise ValueError(f"one_down_design: n must be in {MIN_CONTROL_NUM + 1}..{CONTROL_NUM}, got {n}")
+    return hermite_design(torch.arange(n, dtype=torch.float64) / (n - 1), n - 1)
+
+
+def one_down_tables(device=None) -> torch.Tensor:
+    """float32 [8, 11, 12] (cached, host copy + one per device): block n - 5 holds pinv(one_down_design(n)) in its
+    first n - 1 rows and n columns, zeros elsewhere, so that new[:11] = table[n - 5] @ old[:12] whatever the unused slots
+    of a row hold once they are masked.  Built in float64.  A rank-deficient design raises ValueError."""
+    if "cpu" not in _one_down_cache:
+        table = torch.zeros(CONTROL_NUM - MIN_CONTROL_NUM, CONTROL_NUM - 1, CONTROL_NUM, dtype=torch.float64)
+        for n in range(MIN_CONTROL_NUM + 1, CONTROL_NUM + 1):
+            A = one_down_design(n)
+            rank = int(torch.linalg.matrix_rank(A))
+            if rank < n - 1:
+                raise ValueError(f"rank-deficient fit: the [{n}, {n - 1}] one-down design matrix has rank {rank}")
+            table[n - 5, :n - 1, :n] = torch.linalg.pinv(A)
+        _one_down_cache["cpu"] = table.float().contiguous()
+    if device is None or torch.device(device).type == "cpu":
+        return _one_down_cache["cpu"]
+    key = str(torch.device(device))
+    if key not in _one_down_cache:
+        _one_down_cache[key] = _one_down_cache["cpu"].to(device)
+    return _one_down_cache[key]
+
+
+def _one_down_launch(control_xyz, control_num, viewmats, times, focal, cx, cy, threshold, want_new: bool, commit: bool):
+    """mobgs_control_onedown on tensors that are already what the kernel wants.  -> (error [N], new [N,11,3] | None,
+    counters int32 [2] = (rows pruned, rows with a count outside 4..12)); no host synchronisation."""
+    ptr(control_xyz), ptr(control_num)   # (raises for CPU tensors: there is no CPU path)
+    if control_xyz.dim() != 3 or tuple(control_xyz.shape[1:]) != (CONTROL_NUM, 3) or control_xyz.dtype != torch.float32:
+        raise ValueError(f"control_xyz must be float32 [N,{CONTROL_NUM},3], got {control_xyz.dtype} "
+                         f"{tuple(control_xyz.shape)}")
+    n = int(control_xyz.shape[0])
+    if control_num.dtype != torch.int64 or control_num.numel() != n:
+        raise ValueError(f"current_control_num must be int64 with {n} entries, got {control_num.dtype} "
+                         f"{tuple(control_num.shape)}")
+    dev = control_xyz.device
+    viewmats = _lib.f32c(viewmats.detach().to(dev))
+    times = _lib.f32c(times.detach().to(dev)).reshape(-1)
+    V = int(times.shape[0])
+    if tuple(viewmats.shape) != (V, 4, 4):
+        raise ValueError(f"viewmats must be [{V},4,4] for {V} times, got {tuple(viewmats.shape)}")
+    err = torch.empty(n, dtype=torch.float32, device=dev)
+    new = torch.empty(n, CONTROL_NUM - 1, 3, dtype=torch.float32, device=dev) if want_new else None
+    counters = torch.zeros(2, dtype=torch.int32, device=dev)
+    if n == 0:   # (an empty tensor has no address to hand over)
+        return err, new, counters
+    check(_lib.load().mobgs_control_onedown(n, V, ptr(viewmats), ptr(times), float(focal), float(cx), float(cy),
+                                            ptr(one_down_tables(dev)), float(threshold), ptr(control_xyz),
+                                            ptr(control_num), ptr(err),
+                                            ptr(new), ptr(counters), 1 if commit else 0, stream()),
+          "mobgs_control_onedown")
+    return err, new, counters
+
+
+def _raise_on_bad_counts(counters: torch.Tensor) -> None:
+    bad = int(counters[1])
+    if bad:
+        raise ValueError(f"current_control_num: {bad} rows hold a count outside {MIN_CONTROL_NUM}..{CONTROL_NUM} "
+                         "(reported by mobgs_control_onedown; those rows were skipped)")
+
+
+def one_down_fit(control_xyz: torch.Tensor, current_control_num: torch.Tensor, viewmats: torch.Tensor,
+                 times: torch.Tensor, focal: float, width: float, height: float
+                 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Dry run of onedown_control_pts: (new_control [N,11,3], new_num [N,1], error [N]) and no input is written.
+    viewmats [V,4,4] are world-to-camera matrices in the column-vector convention (the TRANSPOSE of the reference's
+    world_view_transform), times [V]; the first and the last view are skipped and K = [focal, focal, width / 2,
+    height / 2] as in compute_prune_error (:292-308).  Rows whose count is already 4 report their own points, their own
+    count and error 0.  Checks the counts on the host (one read-back): a count outside 4..12 raises ValueError."""
+    ctrl = _lib.f32c(control_xyz.detach())
+    num = current_control_num.detach().contiguous()
+    err, new, counters = _one_down_launch(ctrl, num, viewmats, times, focal, width / 2, height / 2, 0.0, True, False)
+    _raise_on_bad_counts(counters)
+    flat = num.reshape(-1)
+    new_num = torch.where(flat > MIN_CONTROL_NUM, flat - 1, flat).reshape(-1, 1)
+    return new, new_num, err
+
+
+_last_counters: Optional[torch.Tensor] = None   # device counters of the last onedown_control_pts call
+
+
+def check_last_prune() -> None:
+    """Raise ValueError if the last onedown_control_pts met a count outside 4..12 (it skipped those rows).  The call
+    itself does not synchronise; this does."""
+    if _last_counters is not None:
+        _raise_on_bad_counts(_last_counters)
+
+
+def viewpoint_arrays(viewpoints, device) -> Tuple[torch.Tensor, torch.Tensor, float, float, float]:
+    """(viewmats [V,4,4], times [V], focal, cx, cy) read from cameras exactly as compute_prune_error reads them
+    (:293-304): fx = fy = viewpoints[0].metadata.focal_length, cx = image_width / 2, cy = image_height / 2 (not the
+    principal point), viewpoint.time, and world_view_transform, which holds the transposed world-to-camera matrix."""
+    if len(viewpoints) < 3:
+        raise ValueError(f"onedown_control_pts needs at least 3 viewpoints (the first and the last are skipped), got "
+                         f"{len(viewpoints)}")
+    v0 = viewpoints[0]
+    focal = float(v0.metadata.focal_length)
+    cx, cy = float(v0.image_width / 2), float(v0.image_height / 2)
+    # stacked on the target device: matrices that already live there (the reference keeps them on the GPU) are not read back
+    mats = torch.stack([torch.as_tensor(v.world_view_transform).detach().to(device=device, dtype=torch.float32)
+                        for v in viewpoints])
+    times = torch.tensor([float(v.time) for v in viewpoints], dtype=torch.float32).to(device)
+    return mats.transpose(1, 2).contiguous(), times, focal, cx, cy
+
+
+@torch.no_grad()
+def onedown_control_pts(pc, viewpoints, error_threshold: Optional[float] = None) -> torch.Tensor:
+    """GaussianModel.onedown_control_pts (:274-290) for any object with `control_xyz` [N,12,3] and
+    `current_control_num` [N,1] (an unchanged reference GaussianModel included): every row with more than 4 control
+    points is refitted with one point fewer, and keeps the shorter spline -- count n - 1, fitted points in slots
+    0..n-2, zeros up to slot 10, slot 11 untouched -- where the mean pixel distance between the two trajectories over
+    the interior `viewpoints` is at most `error_threshold` (default: pc.error_threshold, else 1.0).  In place, one
+    launch, no host synchronisation and nothing printed.  -> the number of rows pruned, a 0-dim int32 device tensor.
+
+    Deliberately unlike the reference: rows that already have 4 points are left bit for bit as they are (the reference
+    refits them with 4 points against a dummy equation that pins the fourth one, which halves it).  The Adam moments of
+    control_xyz are left alone, as in the reference.  A count outside 4..12 makes the kernel skip the row and count it;
+    check_last_prune() raises for it.  With an fp32 master (`control_xyz.master`, GaussianParams.enable_fp32_masters)
+    the master is pruned and copied into the stored tensor."""
+    stored = pc.control_xyz
+    master = getattr(stored, "master", None)
+    target = master if master is not None else stored
+    if target.dtype != torch.float32 or not target.is_contiguous():
+        raise ValueError("onedown_control_pts: control_xyz (or its master) must be a contiguous float32 tensor; it is "
+                         "written in place")
+    num = pc.current_control_num
+    if not num.is_contiguous():
+        raise ValueError("onedown_control_pts: current_control_num must be contiguous; it is written in place")
+    thr = error_threshold if error_threshold is not None else getattr(pc, "error_threshold", 1.0)
+    mats, times, focal, cx, cy = viewpoint_arrays(viewpoints, target.device)
+    _, _, counters = _one_down_launch(target.detach(), num.detach(), mats, times, focal, cx, cy, thr, False, True)
+    # the kernel wrote through raw pointers: move the version counters so that caches keyed on them see it
+    torch.autograd.graph.increment_version(target)
+    torch.autograd.graph.increment_version(num)
+    if master is not None:
+        stored.detach().copy_(master)
+    global _last_counters
+    _last_counters = counters
+    return counters[0]
