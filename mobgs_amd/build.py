@@ -78,14 +78,18 @@ def sources() -> list[Path]:
     return [CSRC / s for s in SOURCES if (CSRC / s).exists()]
 
 
+def headers() -> list[Path]:
+    """What every translation unit may include: all of csrc/*.h and the public header."""
+    return sorted(CSRC.glob("*.h")) + [CSRC.parent.parent / "include" / "mobgs_hip.h"]
+
+
 def is_stale() -> bool:
     if os.environ.get("MOBGS_LIB"):
         return False
     if not LIB_PATH.exists():
         return True
     t = LIB_PATH.stat().st_mtime
-    deps = sources() + [CSRC / "common.h", CSRC / "raster_shared.h", CSRC / "decoder_shared.h", CSRC / "prep_shared.h", CSRC / "hexplane.h", CSRC.parent.parent / "include" / "mobgs_hip.h"]
-    return any(d.exists() and d.stat().st_mtime > t for d in deps)
+    return any(d.exists() and d.stat().st_mtime > t for d in sources() + headers())
 
 
 def build_extension(force: bool = False, verbose: bool = False) -> Path:
@@ -102,13 +106,11 @@ def _build_extension_locked(force: bool, verbose: bool) -> Path:
     hipcc = _hipcc()
     flags = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
     procs = []
+    newest_header = max(h.stat().st_mtime for h in headers())
     for src in sources():
         obj = src.with_suffix(".o")
         objs.append(obj)
-        if not force and obj.exists() and obj.stat().st_mtime > max(
-                src.stat().st_mtime, (CSRC / "common.h").stat().st_mtime, (CSRC / "hexplane.h").stat().st_mtime,
-                (CSRC / "raster_shared.h").stat().st_mtime, (CSRC / "decoder_shared.h").stat().st_mtime, (CSRC / "prep_shared.h").stat().st_mtime,
-                (CSRC.parent.parent / "include" / "mobgs_hip.h").stat().st_mtime):
+        if not force and obj.exists() and obj.stat().st_mtime > max(src.stat().st_mtime, newest_header):
             continue
         cmd = [hipcc, *flags, *EXTRA_FLAGS.get(src.name, []), "-c", str(src), "-o", str(obj)]
         if verbose:

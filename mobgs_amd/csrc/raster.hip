@@ -20,21 +20,15 @@
 //     (log-depth, D+6 -> 1 value per lane) and writes ONE 64-byte gradient record per (tile, splat) into a
 //     slot owned by that intersection; a second streaming kernel sums each splat's contiguous slots.
 //     No floating-point atomics => bit-reproducible gradients.
+#include <tuple>
 #include <type_traits>
 
 #include "common.h"
 #include "decoder_shared.h"
+#include "raster_launch.h"
 #include "raster_shared.h"
 
 namespace mobgs {
-
-// raster_bwd_mfma.hip: the backward compositor with the gradient sums on the matrix pipe (<= 10 total channels)
-bool raster_bwd_mfma_launch(int mode, int D, bool filter, int grid, hipStream_t st, int nt, int n_groups, int tile_w, int tile_h,
-                            int width, int height, const float* records, const float* backgrounds,
-                            const int32_t* radii, const int32_t* cum_tiles, const int32_t* keep_scan,
-                            const int32_t* tile_offsets, const int32_t* flatten_ids, const float* render_alphas,
-                            const int32_t* last_ids, const float* v_render, const float* v_alphas, float* grad_slots,
-                            const int32_t* tile_order, ClassSel cls, const uint8_t* isect_reach, int32_t* any_record);
 
 // ---------------------------------------------------------------------------------------------------
 // pack: gather the per-splat inputs of the compositor into one aligned record
@@ -1725,66 +1719,9 @@ __device__ __forceinline__ void finish_geometry(const float* __restrict__ rec, b
     }
     c2 *= 0.5f;
 }
-template <int LPG>  // lanes per splat, >= record stride
-__global__ void __launch_bounds__(256)
-slot_reduce_kernel(int n_gauss, int channels, int has_extra, int stride, const int32_t* __restrict__ cum_tiles,
-                   const int32_t* __restrict__ keep_scan, const float* __restrict__ grad_slots, float* __restrict__ v_means2d,
-                   float* __restrict__ v_conics, float* __restrict__ v_opacities, float* __restrict__ v_colors,
-                   float* __restrict__ v_extra, const int32_t* __restrict__ any_record,
-                   const float* __restrict__ records, const int32_t* __restrict__ tiles_per_gauss) {
-    const int gid = (blockIdx.x * blockDim.x + threadIdx.x) / LPG;
-    const int comp = threadIdx.x % LPG;
-    if (gid >= n_gauss) return;
-    // stage 1 wrote no record at all (every cotangent of the pass was zero): all sums are zero, read nothing
-    const bool none = any_record && *any_record == 0;
-    const int a = none ? 0 : keep_index(keep_scan, cum_tiles[gid]);
-    const int b = none ? 0 : keep_index(keep_scan, box_end(cum_tiles, tiles_per_gauss, gid));
-    float acc = 0.f;
-    if (comp < stride) {
-        // 4 independent partial sums keep 4 loads in flight per lane (the loop is latency-bound otherwise);
-        // fixed association order -> still deterministic
-        const float* p = grad_slots + (size_t)a * stride + comp;
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-        int k = a;
-        for (; k + 4 <= b; k += 4, p += 4 * stride) {
-            s0 += p[0];
-            s1 += p[stride];
-            s2 += p[2 * stride];
-            s3 += p[3 * stride];
-        }
-        for (; k < b; ++k, p += stride) s0 += *p;
-        acc = (s0 + s1) + (s2 + s3);
-    }
-    const size_t g = (size_t)gid;
-    {   // one lane per component: components 0 and 1 need each other (both lanes of the group are active here)
-        const float other = __shfl_xor(acc, 1, 64);
-        if (comp < 2) {
-            if (b > a) {  // (no slots: the record may never have been packed)
-                const float* rec = records + g * stride;
-                float ca, cb, cc, op;
-                record_conic_form(rec[2], rec[3], rec[4], rec[5], ca, cb, cc, op);
-                acc = comp == 0 ? ca * acc + cb * other : cb * other + cc * acc;
-            }
-        } else if (comp == 2 || comp == 4) {
-            acc *= 0.5f;
-        }
-        else if (comp == 5) acc = (b > a && acc != 0.f) ? -acc * __builtin_amdgcn_exp2f(-records[g * stride + 5]) : 0.f;
-    }
-    if (comp < 2)
-        v_means2d[2 * g + comp] = acc;
-    else if (comp < 5)
-        v_conics[3 * g + (comp - 2)] = acc;
-    else if (comp == 5)
-        v_opacities[g] = acc;
-    else if (comp - 6 < channels)
-        v_colors[g * channels + (comp - 6)] = acc;
-    else if (has_extra && comp - 6 == channels)
-        v_extra[g] = acc;
-}
-
 // Records read as 16-byte quarters (strides 8, 12, 20 .. 32 floats: the 1-, 2-, 12- and 16-channel passes of get_flow):
 // LPS lanes per splat, lane q < stride / 4 sums quarter q of every slot of the splat, four slots in flight per lane -- a
-// quarter of the waves and of the load instructions of the one-float-per-lane kernel above (stride 20: 74 -> 40 us,
+// quarter of the waves and of the load instructions of a one-float-per-lane kernel (stride 20: 74 -> 40 us,
 // stride 8: 25 -> 20 us at 300 k splats).  Fixed association order -> deterministic.
 template <int LPS>
 __global__ void __launch_bounds__(256)
@@ -1931,21 +1868,16 @@ slot_reduce16_kernel(int n_gauss, int channels, int has_extra, const int32_t* __
     }
 }
 
-// supported total channel counts (compile-time accumulators); other counts are zero-padded by the host wrapper
-template <typename F>
-inline int dispatch_channels(int D, F&& f) {
-    switch (D) {
-        case 1: f(std::integral_constant<int, 1>{}); return MOBGS_OK;
-        case 2: f(std::integral_constant<int, 2>{}); return MOBGS_OK;
-        case 3: f(std::integral_constant<int, 3>{}); return MOBGS_OK;
-        case 4: f(std::integral_constant<int, 4>{}); return MOBGS_OK;
-        case 9: f(std::integral_constant<int, 9>{}); return MOBGS_OK;
-        case 10: f(std::integral_constant<int, 10>{}); return MOBGS_OK;
-        case 12: f(std::integral_constant<int, 12>{}); return MOBGS_OK;
-        case 16: f(std::integral_constant<int, 16>{}); return MOBGS_OK;
-        case 26: f(std::integral_constant<int, 26>{}); return MOBGS_OK;
-        default: return MOBGS_E_UNSUPPORTED;
-    }
+// the per-splat inputs of pack_records_kernel
+struct SplatInputs {
+    const float *means2d, *conics, *colors, *opacities, *extra;
+    const int32_t* radii;
+    int colors_per_camera, opac_per_camera;
+};
+static void launch_pack(int C, int N, int channels, const SplatInputs& in, float* records, hipStream_t st) {
+    hipLaunchKernelGGL(pack_records_kernel, dim3((N + 255) / 256, C), dim3(256), 0, st, N, channels,
+                       record_stride(channels + (in.extra ? 1 : 0)), in.means2d, in.conics, in.colors, in.colors_per_camera,
+                       in.opacities, in.opac_per_camera, in.extra, in.radii, records);
 }
 
 }  // namespace mobgs
@@ -1982,24 +1914,11 @@ int mobgs_cotangent_probe(int n_arrays, const float* const* arrays, const size_t
     return check_launch("cotangent_probe_many_kernel");
 }
 
-int mobgs_raster_channels_supported(int D) {
-    return D == 1 || D == 2 || D == 3 || D == 4 || D == 9 || D == 10 || D == 12 || D == 16 || D == 26;
-}
+int mobgs_raster_channels_supported(int D) { return raster_channels_supported(D); }
 
 int mobgs_raster_path(int total_channels, int class_filter, int n_tiles, const MobgsTuning* tuning) {
-    const int D = total_channels;
-    int bwd = 0;
-    // a plain pass under bwd_block_walk never takes the matrix pipe: counts without a block-walk build run the quadrant
-    // kernel (raster_bwd_impl skips raster_bwd_mfma_launch whenever bwd_block_walk is set)
-    if (!class_filter && tuning_bwd_block_walk(tuning)) {
-        if (D >= 7 && D <= 10) bwd = 3;
-    } else if (tuning_bwd_mfma(tuning, n_tiles)) {
-        const bool has = class_filter ? (D == 1 || D == 10) : (D == 1 || D == 3 || D == 4 || D == 9 || D == 10);
-        if (has) bwd = tuning_bwd_mfma(tuning, n_tiles);
-    }
-    const bool fwd_blocks = tuning_block_walk(tuning) && (class_filter ? D == 10 : (D >= 7 && D <= 12));
-    const int heavy_len = tuning_heavy_len(tuning, n_tiles);
-    return bwd | (fwd_blocks ? 4 : 0) | (heavy_len > 0 ? 8 : 0) | (heavy_len << 8);
+    const RasterPlan p = raster_plan(total_channels, class_filter, n_tiles, tuning);
+    return p.bwd | (p.fwd_blocks ? 4 : 0) | (p.heavy_len > 0 ? 8 : 0) | (p.heavy_len << 8);
 }
 
 int mobgs_pack_records(int C, int N, int channels, const float* means2d, const float* conics, const float* colors,
@@ -2011,59 +1930,41 @@ int mobgs_pack_records(int C, int N, int channels, const float* means2d, const f
         return MOBGS_E_INVALID;
     }
     if (N == 0) return MOBGS_OK;
-    hipLaunchKernelGGL(pack_records_kernel, dim3((N + 255) / 256, C), dim3(256), 0, (hipStream_t)stream, N, channels,
-                       record_stride(D), means2d, conics, colors, colors_per_camera, opacities, opac_per_camera, extra,
-                       radii, records);
+    launch_pack(C, N, channels, {means2d, conics, colors, opacities, extra, radii, colors_per_camera, opac_per_camera},
+                records, (hipStream_t)stream);
     return check_launch("pack_records_kernel");
 }
 
-static int raster_fwd_impl(int C, int N, int channels, int width, int height, const float* means2d,
-                           const float* conics, const float* colors, int colors_per_camera, const float* opacities,
-                           int opac_per_camera, const float* extra, const float* backgrounds, const int32_t* radii,
-                           const int32_t* tile_offsets, const int32_t* tile_order, const int32_t* flatten_ids,
-                           float* records, float* render, float* alphas, int32_t* last_ids, uint8_t* isect_reach,
-                           const MobgsTuning* tuning, void* stream, const DecodeEpi* dec) {
+static int raster_fwd_impl(int C, int N, int channels, int width, int height, const SplatInputs& in, float* records,
+                           const RasterFwdArgs& a, const MobgsTuning* tuning, void* stream, const DecodeEpi* dec) {
     hipStream_t st = (hipStream_t)stream;
-    const int g_all_reach = tuning_all_reach(tuning);
-    const int D = channels + (extra ? 1 : 0);
+    const int D = channels + (in.extra ? 1 : 0);
     if (C <= 0 || N < 0 || channels < 0 || D < 1 || width <= 0 || height <= 0) {
         set_error("mobgs_raster_fwd: bad sizes C=%d N=%d channels=%d W=%d H=%d", C, N, channels, width, height);
         return MOBGS_E_INVALID;
     }
-    const int tile_w = (width + MOBGS_TILE - 1) / MOBGS_TILE, tile_h = (height + MOBGS_TILE - 1) / MOBGS_TILE;
-    const int nt = C * tile_w * tile_h;
-    const int stride = record_stride(D);
-    if (N > 0 && colors != nullptr) {  // colors == NULL: `records` were packed by mobgs_project_and_bin_speculative
-        hipLaunchKernelGGL(pack_records_kernel, dim3((N + 255) / 256, C), dim3(256), 0, st, N, channels, stride,
-                           means2d, conics, colors, colors_per_camera, opacities, opac_per_camera, extra, radii,
-                           records);
-    }
-    const int n_groups = (nt + TILES_PER_WG - 1) / TILES_PER_WG;
-    const int grid = tile_order ? (int)((sched_slots((size_t)nt) + TILES_PER_WG - 1) / TILES_PER_WG) : ((n_groups + 7) / 8) * 8;
-    const int block_walk = tuning_block_walk(tuning);
+    const RasterGrid g = raster_grid(C, width, height, a.tile_order, TILES_PER_WG);
+    // colors == NULL: `records` were packed by mobgs_project_and_bin_speculative
+    if (N > 0 && in.colors != nullptr) launch_pack(C, N, channels, in, records, st);
+    const RasterPlan plan = raster_plan(D, 0, g.nt, tuning);
+    const ClassSel cls{0, 1, 0, tuning_all_reach(tuning)};
     if (dec) {  // decoder epilogue: the block-walk kernel of the 9 + 1 channel pass
-        if (D != 10 || !extra || !block_walk) {
+        if (D != 10 || !in.extra || !plan.fwd_blocks) {
             set_error("mobgs_raster_fwd_decode: needs 9 feature channels + the depth channel and the block-walk kernel");
             return MOBGS_E_UNSUPPORTED;
         }
-        hipLaunchKernelGGL((raster_fwd_blocks_kernel<10, false, true>), dim3(grid), dim3(64 * TILES_PER_WG), 0, st, nt,
-                           n_groups, tile_w, tile_h, width, height, records, backgrounds, tile_offsets, flatten_ids, render,
-                           alphas, last_ids, tile_order, ClassSel{0, 1, 0, g_all_reach}, isect_reach, *dec);
+        launch_raster_fwd(raster_fwd_blocks_kernel<10, false, true>, g, a, st, cls, *dec);
         return check_launch("raster_fwd_kernel(decode)");
     }
     const int rc = dispatch_channels(D, [&](auto cd) {
         constexpr int CD = decltype(cd)::value;
-        // measured (profiles/r03): the block walk wins where a pixel's blend is wide -- 10 channels 256 -> 218 us, 12
-        // channels 280 -> 255 us -- and loses where the per-step bookkeeping dominates (1 channel 86 -> 90 us) or the
-        // accumulators leave two waves per SIMD (16 channels 313 -> 335 us)
-        if (block_walk && CD >= 7 && CD <= 12)
-            hipLaunchKernelGGL((raster_fwd_blocks_kernel<CD, false>), dim3(grid), dim3(64 * TILES_PER_WG), 0, st, nt,
-                               n_groups, tile_w, tile_h, width, height, records, backgrounds, tile_offsets, flatten_ids,
-                               render, alphas, last_ids, tile_order, ClassSel{0, 1, 0, g_all_reach}, isect_reach, DecodeEpi{});
-        else
-        hipLaunchKernelGGL((raster_fwd_kernel<CD, false>), dim3(grid), dim3(64 * TILES_PER_WG), 0, st, nt, n_groups,
-                           tile_w, tile_h, width, height, records, backgrounds, tile_offsets, flatten_ids, render,
-                           alphas, last_ids, tile_order, ClassSel{0, 1, 0, g_all_reach}, isect_reach);
+        if constexpr (has_fwd_blocks(CD, false)) {
+            if (plan.fwd_blocks) {
+                launch_raster_fwd(raster_fwd_blocks_kernel<CD, false>, g, a, st, cls, DecodeEpi{});
+                return;
+            }
+        }
+        launch_raster_fwd(raster_fwd_kernel<CD, false>, g, a, st, cls);
     });
     if (rc != MOBGS_OK) {
         set_error("mobgs_raster_fwd: %d total channels not compiled in (pad to a supported count)", D);
@@ -2078,9 +1979,10 @@ int mobgs_raster_fwd(int C, int N, int channels, int width, int height, const fl
                      const int32_t* tile_offsets, const int32_t* tile_order, const int32_t* flatten_ids,
                      float* records, float* render, float* alphas, int32_t* last_ids, uint8_t* isect_reach,
                      const MobgsTuning* tuning, void* stream) {
-    return raster_fwd_impl(C, N, channels, width, height, means2d, conics, colors, colors_per_camera, opacities,
-                           opac_per_camera, extra, backgrounds, radii, tile_offsets, tile_order, flatten_ids, records, render,
-                           alphas, last_ids, isect_reach, tuning, stream, nullptr);
+    return raster_fwd_impl(C, N, channels, width, height,
+                           {means2d, conics, colors, opacities, extra, radii, colors_per_camera, opac_per_camera}, records,
+                           {records, backgrounds, tile_offsets, tile_order, flatten_ids, render, alphas, last_ids, isect_reach},
+                           tuning, stream, nullptr);
 }
 
 int mobgs_raster_fwd_decode(int C, int N, int channels, int width, int height, const float* means2d,
@@ -2095,76 +1997,55 @@ int mobgs_raster_fwd_decode(int C, int N, int channels, int width, int height, c
         return MOBGS_E_INVALID;
     }
     const DecodeEpi dec{ray_intr, ray_c2w, w1, w2, rgb, depth, intr_stride, c2w_stride};
-    return raster_fwd_impl(C, N, channels, width, height, means2d, conics, colors, colors_per_camera, opacities,
-                           opac_per_camera, extra, backgrounds, radii, tile_offsets, tile_order, flatten_ids, records, render,
-                           alphas, last_ids, isect_reach, tuning, stream, &dec);
+    return raster_fwd_impl(C, N, channels, width, height,
+                           {means2d, conics, colors, opacities, extra, radii, colors_per_camera, opac_per_camera}, records,
+                           {records, backgrounds, tile_offsets, tile_order, flatten_ids, render, alphas, last_ids, isect_reach},
+                           tuning, stream, &dec);
 }
 
-static int raster_bwd_impl(int C, int N, int channels, int has_extra, int width, int height, const float* records,
-                     const float* backgrounds, const int32_t* radii, const float* means2d,
-                     const int32_t* cum_tiles, const int32_t* keep_scan, const int32_t* tile_offsets,
-                     const int32_t* tile_order, const int32_t* flatten_ids, const float* render_alphas,
-                     const int32_t* last_ids, const float* v_render, const float* v_alphas, float* grad_slots,
-                     const uint8_t* isect_reach, int32_t* any_record, const MobgsTuning* tuning, void* stream,
-                     const DecodeBwd* db) {
+static int raster_bwd_impl(int C, int N, int channels, int has_extra, int width, int height, const RasterBwdArgs& a,
+                           const MobgsTuning* tuning, void* stream, const DecodeBwd* db) {
     hipStream_t st = (hipStream_t)stream;
-    const int g_all_reach = tuning_all_reach(tuning);
-    (void)means2d;
     const int D = channels + (has_extra ? 1 : 0);
     if (C <= 0 || N < 0 || D < 1) {
         set_error("mobgs_raster_bwd: bad sizes C=%d N=%d channels=%d", C, N, channels);
         return MOBGS_E_INVALID;
     }
-    const int tile_w = (width + MOBGS_TILE - 1) / MOBGS_TILE, tile_h = (height + MOBGS_TILE - 1) / MOBGS_TILE;
-    const int nt = C * tile_w * tile_h;
-    const int stride = record_stride(D);
-    const int n_groups = (nt + TILES_PER_WG - 1) / TILES_PER_WG;
-    const int grid = tile_order ? (int)((sched_slots((size_t)nt) + TILES_PER_WG - 1) / TILES_PER_WG) : ((n_groups + 7) / 8) * 8;
-    const int bwd_blocks = tuning_bwd_block_walk(tuning);
-    ClassSel cls{0, 1, 0, g_all_reach};
+    const RasterGrid g = raster_grid(C, width, height, a.tile_order, TILES_PER_WG);
+    const RasterPlan plan = raster_plan(D, 0, g.nt, tuning);
+    ClassSel cls{0, 1, 0, tuning_all_reach(tuning)};
     cls.static_rows = tuning_static_rows(tuning);
     cls.set_n = N > 0 ? N : 1;
     cls.cover = tuning_cover_slots(tuning);
-    const bool quadrant_selected = (mobgs_raster_path(D, 0, nt, tuning) & 3) == 0;   // (what the dispatch below arrives at)
-    if (cls.cover && (!quadrant_selected || tuning_gate_zero_cotangent(tuning))) {
+    if (cls.cover && (plan.bwd != BWD_QUADRANT || tuning_gate_zero_cotangent(tuning))) {
         set_error("mobgs_raster_bwd: cover_slots needs the quadrant kernel and no zero-cotangent gate");
         return MOBGS_E_UNSUPPORTED;
     }
     if (db) {   // decoder prologue: the quadrant kernel of the 9 + 1 channel pass (mobgs_raster_path tells beforehand)
-        if (D != 10 || !has_extra || !quadrant_selected) {
+        if (D != 10 || !has_extra || plan.bwd != BWD_QUADRANT) {
             set_error("mobgs_raster_bwd_decode: needs 9 feature channels + the depth channel and the quadrant kernel "
                       "(mobgs_raster_path(10, 0, n_tiles, tuning) & 3 == 0)");
             return MOBGS_E_UNSUPPORTED;
         }
-        hipLaunchKernelGGL((raster_bwd_kernel<10, false, true>), dim3(grid), dim3(64 * TILES_PER_WG), 0, st, nt, n_groups,
-                           tile_w, tile_h, width, height, records, backgrounds, radii, cum_tiles, keep_scan,
-                           tile_offsets, flatten_ids, render_alphas, last_ids, v_render, v_alphas, grad_slots,
-                           tile_order, cls, isect_reach, any_record, *db);
+        launch_raster_bwd(raster_bwd_kernel<10, false, true>, g, a, st, cls, *db);
         return check_launch("raster_bwd_kernel(decode)");
     }
-    if (!bwd_blocks)
-        cls.gate = arm_cotangent_gate(tuning, v_render, (size_t)C * height * width * D, v_alphas,
-                                      (size_t)C * height * width, any_record, st);
-    if (tuning_bwd_mfma(tuning, nt) && !bwd_blocks &&
-        raster_bwd_mfma_launch(tuning_bwd_mfma(tuning, nt), D, false, grid, st, nt, n_groups, tile_w, tile_h, width, height, records, backgrounds,
-                               radii, cum_tiles, keep_scan, tile_offsets, flatten_ids, render_alphas, last_ids, v_render,
-                               v_alphas, grad_slots, tile_order, cls, isect_reach, any_record))
-        return check_launch("raster_bwd_mfma_kernel");
+    if (plan.gate)
+        cls.gate = arm_cotangent_gate(tuning, a.v_render, (size_t)C * height * width * D, a.v_alphas,
+                                      (size_t)C * height * width, a.any_record, st);
+    if (plan.mfma()) {
+        const int rc = raster_bwd_mfma_launch(plan.bwd, D, false, g, a, cls, st);
+        return rc != MOBGS_OK ? rc : check_launch("raster_bwd_mfma_kernel");
+    }
     const int rc = dispatch_channels(D, [&](auto cd) {
         constexpr int CD = decltype(cd)::value;
-        if constexpr (CD >= 7 && CD <= 10) {
-            if (bwd_blocks) {
-                hipLaunchKernelGGL((raster_bwd_blocks_kernel<CD>), dim3(grid), dim3(64 * TILES_PER_WG), 0, st, nt,
-                                   n_groups, tile_w, tile_h, width, height, records, backgrounds, radii, cum_tiles,
-                                   keep_scan, tile_offsets, flatten_ids, render_alphas, last_ids, v_render, v_alphas,
-                                   grad_slots, tile_order, g_all_reach, isect_reach, any_record);
+        if constexpr (has_bwd_blocks(CD)) {
+            if (plan.bwd == BWD_BLOCKS) {
+                launch_raster_bwd(raster_bwd_blocks_kernel<CD>, g, a, st, cls.all_reach);
                 return;
             }
         }
-        hipLaunchKernelGGL((raster_bwd_kernel<CD, false>), dim3(grid), dim3(64 * TILES_PER_WG), 0, st, nt, n_groups,
-                           tile_w, tile_h, width, height, records, backgrounds, radii, cum_tiles, keep_scan,
-                           tile_offsets, flatten_ids, render_alphas, last_ids, v_render, v_alphas, grad_slots,
-                           tile_order, cls, isect_reach, any_record, DecodeBwd{});
+        launch_raster_bwd(raster_bwd_kernel<CD, false>, g, a, st, cls, DecodeBwd{});
     });
     if (rc != MOBGS_OK) {
         set_error("mobgs_raster_bwd: %d total channels not compiled in", D);
@@ -2179,9 +2060,10 @@ int mobgs_raster_bwd(int C, int N, int channels, int has_extra, int width, int h
                      const int32_t* tile_order, const int32_t* flatten_ids, const float* render_alphas,
                      const int32_t* last_ids, const float* v_render, const float* v_alphas, float* grad_slots,
                      const uint8_t* isect_reach, int32_t* any_record, const MobgsTuning* tuning, void* stream) {
-    return raster_bwd_impl(C, N, channels, has_extra, width, height, records, backgrounds, radii, means2d, cum_tiles,
-                           keep_scan, tile_offsets, tile_order, flatten_ids, render_alphas, last_ids, v_render, v_alphas,
-                           grad_slots, isect_reach, any_record, tuning, stream, nullptr);
+    return raster_bwd_impl(C, N, channels, has_extra, width, height,
+                           {records, backgrounds, radii, cum_tiles, keep_scan, tile_offsets, tile_order, flatten_ids,
+                            render_alphas, last_ids, v_render, v_alphas, grad_slots, isect_reach, any_record},
+                           tuning, stream, nullptr);
 }
 
 int mobgs_raster_bwd_decode(int C, int N, int width, int height, const float* records, const float* backgrounds,
@@ -2196,12 +2078,12 @@ int mobgs_raster_bwd_decode(int C, int N, int width, int height, const float* re
         set_error("mobgs_raster_bwd_decode: render, v_rgb, ray_intr, ray_c2w, w1, w2 and w_partial are required");
         return MOBGS_E_INVALID;
     }
-    const int tiles = ((width + MOBGS_TILE - 1) / MOBGS_TILE) * ((height + MOBGS_TILE - 1) / MOBGS_TILE);
-    const DecodeBwd db{render, v_rgb, v_depth, ray_intr, ray_c2w, w1, w2, w_partial, decoder_wgrad_ticket(w_partial, C, tiles),
-                       intr_stride, c2w_stride};
-    return raster_bwd_impl(C, N, 9, 1, width, height, records, backgrounds, radii, nullptr, cum_tiles, keep_scan,
-                           tile_offsets, tile_order, flatten_ids, render_alphas, last_ids, nullptr, v_alphas,
-                           grad_slots, isect_reach, any_record, tuning, stream, &db);
+    const DecodeBwd db{render, v_rgb, v_depth, ray_intr, ray_c2w, w1, w2, w_partial,
+                       decoder_wgrad_ticket(w_partial, C, tiles_per_image(width, height)), intr_stride, c2w_stride};
+    return raster_bwd_impl(C, N, 9, 1, width, height,
+                           {records, backgrounds, radii, cum_tiles, keep_scan, tile_offsets, tile_order, flatten_ids,
+                            render_alphas, last_ids, nullptr, v_alphas, grad_slots, isect_reach, any_record},
+                           tuning, stream, &db);
 }
 
 int mobgs_raster_bwd_decode_finish(int C, int width, int height, float* w_partial, int c2w_stride, float* g_w1,
@@ -2215,8 +2097,8 @@ int mobgs_raster_bwd_decode_finish(int C, int width, int height, float* w_partia
         set_error("mobgs_raster_bwd_decode_finish: a pose shared by the images of a batch cannot receive a gradient");
         return MOBGS_E_INVALID;
     }
-    const int tiles = ((width + MOBGS_TILE - 1) / MOBGS_TILE) * ((height + MOBGS_TILE - 1) / MOBGS_TILE);
-    launch_decoder_wgrad_reduce(C, tiles, w_partial, g_w1, g_w2, g_c2w, g_c2w_floats, accumulate_wgrad, (hipStream_t)stream);
+    launch_decoder_wgrad_reduce(C, tiles_per_image(width, height), w_partial, g_w1, g_w2, g_c2w, g_c2w_floats,
+                                accumulate_wgrad, (hipStream_t)stream);
     return check_launch("decoder_wgrad_reduce_rows_kernel");
 }
 
@@ -2236,7 +2118,7 @@ int mobgs_raster_bwd_reduce_decode(int C, int N, const float* records, const int
     wf.g_w1 = g_w1;
     wf.g_w2 = g_w2;
     wf.g_c2w = g_c2w;
-    wf.rows_per_image = ((width + MOBGS_TILE - 1) / MOBGS_TILE) * ((height + MOBGS_TILE - 1) / MOBGS_TILE);
+    wf.rows_per_image = tiles_per_image(width, height);
     wf.n_images = C;
     wf.accumulate = accumulate_wgrad;
     wf.c2w_floats = g_c2w_floats;
@@ -2250,7 +2132,7 @@ int mobgs_raster_bwd_reduce_decode(int C, int N, const float* records, const int
 
 size_t mobgs_raster_bwd_decode_scratch_floats(int C, int width, int height) {
     if (C <= 0 || width <= 0 || height <= 0) return 0;
-    return decoder_wgrad_scratch_floats(C, ((width + MOBGS_TILE - 1) / MOBGS_TILE) * ((height + MOBGS_TILE - 1) / MOBGS_TILE));
+    return decoder_wgrad_scratch_floats(C, tiles_per_image(width, height));
 }
 
 // class-restricted passes over the lists of the whole set: 10 total channels (the render() configuration) or 1 (the
@@ -2259,32 +2141,22 @@ int mobgs_raster_class_fwd(int C, int N, int Ns, int class_sel, int channels_tot
                            const float* records, const float* backgrounds, const int32_t* tile_offsets,
                            const int32_t* tile_order, const int32_t* flatten_ids, float* render, float* alphas,
                            int32_t* last_ids, uint8_t* isect_reach, const MobgsTuning* tuning, void* stream) {
-    const int g_all_reach = tuning_all_reach(tuning);
     if (C <= 0 || N <= 0 || Ns < 0 || Ns > N || (class_sel != 1 && class_sel != 2) ||
         (channels_total != 10 && channels_total != 1)) {
         set_error("mobgs_raster_class_fwd: unsupported arguments (C=%d N=%d Ns=%d class=%d D=%d)", C, N, Ns, class_sel,
                   channels_total);
         return MOBGS_E_UNSUPPORTED;
     }
-    const int tile_w = (width + MOBGS_TILE - 1) / MOBGS_TILE, tile_h = (height + MOBGS_TILE - 1) / MOBGS_TILE;
-    const int nt = C * tile_w * tile_h;
-    const int n_groups = (nt + TILES_PER_WG - 1) / TILES_PER_WG;
-    const int grid = tile_order ? (int)((sched_slots((size_t)nt) + TILES_PER_WG - 1) / TILES_PER_WG) : ((n_groups + 7) / 8) * 8;
-    const ClassSel cls{class_sel, N, Ns, g_all_reach};
-    const dim3 g3(grid), b3(64 * TILES_PER_WG);
+    const RasterGrid g = raster_grid(C, width, height, tile_order, TILES_PER_WG);
+    const RasterFwdArgs a{records, backgrounds, tile_offsets, tile_order, flatten_ids, render, alphas, last_ids, isect_reach};
+    const ClassSel cls{class_sel, N, Ns, tuning_all_reach(tuning)};
     hipStream_t st = (hipStream_t)stream;
-    if (tuning_block_walk(tuning) && channels_total == 10)  // (the 1-channel coverage pass: 86 us vs 90 us, see above)
-        hipLaunchKernelGGL((raster_fwd_blocks_kernel<10, true>), g3, b3, 0, st, nt, n_groups, tile_w, tile_h, width,
-                           height, records, backgrounds, tile_offsets, flatten_ids, render, alphas, last_ids,
-                           tile_order, cls, isect_reach, DecodeEpi{});
+    if (raster_plan(channels_total, 1, g.nt, tuning).fwd_blocks)  // (10 channels only)
+        launch_raster_fwd(raster_fwd_blocks_kernel<10, true>, g, a, st, cls, DecodeEpi{});
     else if (channels_total == 10)
-        hipLaunchKernelGGL((raster_fwd_kernel<10, true>), g3, b3, 0, st, nt, n_groups, tile_w, tile_h, width, height,
-                           records, backgrounds, tile_offsets, flatten_ids, render, alphas, last_ids, tile_order, cls,
-                           isect_reach);
+        launch_raster_fwd(raster_fwd_kernel<10, true>, g, a, st, cls);
     else
-        hipLaunchKernelGGL((raster_fwd_kernel<1, true>), g3, b3, 0, st, nt, n_groups, tile_w, tile_h, width, height,
-                           records, backgrounds, tile_offsets, flatten_ids, render, alphas, last_ids, tile_order, cls,
-                           isect_reach);
+        launch_raster_fwd(raster_fwd_kernel<1, true>, g, a, st, cls);
     return check_launch("raster_fwd_kernel(class)");
 }
 
@@ -2294,84 +2166,74 @@ int mobgs_raster_class_bwd(int C, int N, int Ns, int class_sel, int channels_tot
                            const int32_t* tile_order, const int32_t* flatten_ids, const float* render_alphas,
                            const int32_t* last_ids, const float* v_render, const float* v_alphas, float* grad_slots,
                            const uint8_t* isect_reach, int32_t* any_record, const MobgsTuning* tuning, void* stream) {
-    const int g_all_reach = tuning_all_reach(tuning);
     if (C <= 0 || N <= 0 || Ns < 0 || Ns > N || (class_sel != 1 && class_sel != 2) ||
         (channels_total != 10 && channels_total != 1)) {
         set_error("mobgs_raster_class_bwd: unsupported arguments");
         return MOBGS_E_UNSUPPORTED;
     }
-    const int tile_w = (width + MOBGS_TILE - 1) / MOBGS_TILE, tile_h = (height + MOBGS_TILE - 1) / MOBGS_TILE;
-    const int nt = C * tile_w * tile_h;
-    const int n_groups = (nt + TILES_PER_WG - 1) / TILES_PER_WG;
-    const int grid = tile_order ? (int)((sched_slots((size_t)nt) + TILES_PER_WG - 1) / TILES_PER_WG) : ((n_groups + 7) / 8) * 8;
-    ClassSel cls{class_sel, N, Ns, g_all_reach};
+    hipStream_t st = (hipStream_t)stream;
+    const RasterGrid g = raster_grid(C, width, height, tile_order, TILES_PER_WG);
+    const RasterBwdArgs a{records, backgrounds, radii, cum_tiles, keep_scan, tile_offsets, tile_order, flatten_ids,
+                          render_alphas, last_ids, v_render, v_alphas, grad_slots, isect_reach, any_record};
+    const RasterPlan plan = raster_plan(channels_total, 1, g.nt, tuning);
+    ClassSel cls{class_sel, N, Ns, tuning_all_reach(tuning)};
     cls.static_rows = tuning_static_rows(tuning);
     cls.set_n = N;
-    cls.gate = arm_cotangent_gate(tuning, v_render, (size_t)C * height * width * channels_total, v_alphas,
-                                  (size_t)C * height * width, any_record, (hipStream_t)stream);
-    if (tuning_bwd_mfma(tuning, nt) &&
-        raster_bwd_mfma_launch(tuning_bwd_mfma(tuning, nt), channels_total, true, grid, (hipStream_t)stream, nt, n_groups, tile_w, tile_h, width,
-                               height, records, backgrounds, radii, cum_tiles, keep_scan, tile_offsets, flatten_ids,
-                               render_alphas, last_ids, v_render, v_alphas, grad_slots, tile_order,
-                               cls, isect_reach, any_record))
-        return check_launch("raster_bwd_mfma_kernel(class)");
+    if (plan.gate)  // (always, for a class pass)
+        cls.gate = arm_cotangent_gate(tuning, v_render, (size_t)C * height * width * channels_total, v_alphas,
+                                      (size_t)C * height * width, any_record, st);
+    if (plan.mfma()) {
+        const int rc = raster_bwd_mfma_launch(plan.bwd, channels_total, true, g, a, cls, st);
+        return rc != MOBGS_OK ? rc : check_launch("raster_bwd_mfma_kernel(class)");
+    }
     if (channels_total == 10)
-        hipLaunchKernelGGL((raster_bwd_kernel<10, true>), dim3(grid), dim3(64 * TILES_PER_WG), 0, (hipStream_t)stream,
-                           nt, n_groups, tile_w, tile_h, width, height, records, backgrounds, radii, cum_tiles,
-                           keep_scan, tile_offsets, flatten_ids, render_alphas, last_ids, v_render, v_alphas,
-                           grad_slots, tile_order, cls, isect_reach, any_record, DecodeBwd{});
+        launch_raster_bwd(raster_bwd_kernel<10, true>, g, a, st, cls, DecodeBwd{});
     else
-        hipLaunchKernelGGL((raster_bwd_kernel<1, true>), dim3(grid), dim3(64 * TILES_PER_WG), 0, (hipStream_t)stream,
-                           nt, n_groups, tile_w, tile_h, width, height, records, backgrounds, radii, cum_tiles,
-                           keep_scan, tile_offsets, flatten_ids, render_alphas, last_ids, v_render, v_alphas,
-                           grad_slots, tile_order, cls, isect_reach, any_record, DecodeBwd{});
+        launch_raster_bwd(raster_bwd_kernel<1, true>, g, a, st, cls, DecodeBwd{});
     return check_launch("raster_bwd_kernel(class)");
 }
 
+// Supported counts have records of 8, 12, 16, 20, 24 or 32 floats (record_stride(D) = (D + 9) & ~3).  More than 26 total
+// channels -- records of more than 32 floats, which no kernel here sums -- are refused with MOBGS_E_UNSUPPORTED before
+// anything is launched (they used to reach a kernel launched outside its own premise; no caller of the project can
+// send such a count: the host wrapper's channel padding raises first).
 int mobgs_raster_bwd_reduce(int C, int N, int channels, int has_extra, const float* records,
                             const int32_t* cum_tiles, const int32_t* keep_scan, const float* grad_slots,
                             const int32_t* any_record, float* v_means2d, float* v_conics, float* v_opacities,
                             float* v_colors, float* v_extra, const int32_t* tiles_per_gauss, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     const int D = channels + (has_extra ? 1 : 0);
+    const int stride = record_stride(D);
+    if (stride > 32) {
+        set_error("mobgs_raster_bwd_reduce: %d total channels not compiled in (at most 26: records of 32 floats)", D);
+        return MOBGS_E_UNSUPPORTED;
+    }
     if (C <= 0 || N < 0 || D < 1 || ((long long)C * N > 0 && !records)) {
         set_error("mobgs_raster_bwd_reduce: bad sizes C=%d N=%d channels=%d", C, N, channels);
         return MOBGS_E_INVALID;
     }
-    const int stride = record_stride(D);
     const int n = C * N;
+    // `lanes` lanes per splat; lead: what a kernel takes in front of the shared arguments, tail: what behind them
+    auto launch = [&](auto kernel, int lanes, auto lead, auto tail) {
+        std::apply([&](auto... args) {
+            hipLaunchKernelGGL(kernel, dim3((int)(((size_t)n * lanes + 255) / 256)), dim3(256), 0, st, n, channels,
+                               has_extra, args...);
+        }, std::tuple_cat(lead, std::make_tuple(cum_tiles, keep_scan, grad_slots, v_means2d, v_conics, v_opacities,
+                                                v_colors, v_extra, any_record, records, tiles_per_gauss), tail));
+    };
+    const auto quarters = std::make_tuple(stride / 4);   // the wide kernels: 16-byte quarters per record
+    const std::tuple<> none;
     if (n > 0) {
-        if (stride == 8) {
-            hipLaunchKernelGGL(slot_reduce_wide_kernel<2>, dim3((int)(((size_t)n * 2 + 255) / 256)), dim3(256), 0, st, n,
-                               channels, has_extra, 2, cum_tiles, keep_scan, grad_slots, v_means2d, v_conics,
-                               v_opacities, v_colors, v_extra, any_record, records, tiles_per_gauss);
-        } else if (stride < 8) {
-            hipLaunchKernelGGL(slot_reduce_kernel<8>, dim3((n * 8 + 255) / 256), dim3(256), 0, st, n, channels,
-                               has_extra, stride, cum_tiles, keep_scan, grad_slots, v_means2d, v_conics, v_opacities, v_colors,
-                               v_extra, any_record, records, tiles_per_gauss);
-        } else if (stride == 12) {
-            hipLaunchKernelGGL(slot_reduce_wide_kernel<4>, dim3((int)(((size_t)n * 4 + 255) / 256)), dim3(256), 0, st, n,
-                               channels, has_extra, 3, cum_tiles, keep_scan, grad_slots, v_means2d, v_conics,
-                               v_opacities, v_colors, v_extra, any_record, records, tiles_per_gauss);
-        } else if (stride == 16) {  // (slot_reduce_wide_kernel<4> measures the same here: 29.0 vs 28.7 us)
-            hipLaunchKernelGGL(slot_reduce16_kernel<8>, dim3((int)(((size_t)n * 8 + 255) / 256)), dim3(256), 0, st, n,
-                               channels, has_extra, cum_tiles, keep_scan, grad_slots, v_means2d, v_conics, v_opacities,
-                               v_colors, v_extra, any_record, records, tiles_per_gauss);
-        } else if (stride <= 16) {
-            hipLaunchKernelGGL(slot_reduce_kernel<16>, dim3((int)(((size_t)n * 16 + 255) / 256)), dim3(256), 0, st, n,
-                               channels, has_extra, stride, cum_tiles, keep_scan, grad_slots, v_means2d, v_conics, v_opacities,
-                               v_colors, v_extra, any_record, records, tiles_per_gauss);
-        } else if (stride <= 32 && (stride & 3) == 0) {
-            hipLaunchKernelGGL(slot_reduce_wide_kernel<8>, dim3((int)(((size_t)n * 8 + 255) / 256)), dim3(256), 0, st, n,
-                               channels, has_extra, stride / 4, cum_tiles, keep_scan, grad_slots, v_means2d, v_conics,
-                               v_opacities, v_colors, v_extra, any_record, records, tiles_per_gauss);
-        } else {
-            hipLaunchKernelGGL(slot_reduce_kernel<32>, dim3((int)(((size_t)n * 32 + 255) / 256)), dim3(256), 0, st, n,
-                               channels, has_extra, stride, cum_tiles, keep_scan, grad_slots, v_means2d, v_conics, v_opacities,
-                               v_colors, v_extra, any_record, records, tiles_per_gauss);
-        }
+        if (stride == 8)
+            launch(slot_reduce_wide_kernel<2>, 2, quarters, none);
+        else if (stride == 12)
+            launch(slot_reduce_wide_kernel<4>, 4, quarters, none);
+        else if (stride == 16)  // (slot_reduce_wide_kernel<4> measures the same here: 29.0 vs 28.7 us)
+            launch(slot_reduce16_kernel<8, false>, 8, none, std::make_tuple(WgradFinish{}));
+        else
+            launch(slot_reduce_wide_kernel<8>, 8, quarters, none);
     }
-    return check_launch("slot_reduce_kernel");
+    return check_launch("slot_reduce kernels");
 }
 
 }  // extern "C"

@@ -41,6 +41,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "raster_launch.h"
 #include "raster_shared.h"
 
 namespace mobgs {
@@ -685,43 +686,35 @@ raster_bwd_mfma_kernel(int n_tiles_total, int n_groups, int tile_w, int tile_h, 
     }
 }
 
-// launcher used by mobgs_raster_bwd / mobgs_raster_class_bwd (raster.hip); false: channel count not built here.
-// mode 1: one wave per tile (+ team for the schedule's heavy tiles), mode 2: team for every tile
-bool raster_bwd_mfma_launch(int mode, int D, bool filter, int grid, hipStream_t st, int nt, int n_groups, int tile_w,
-                            int tile_h, int width, int height, const float* records, const float* backgrounds,
-                            const int32_t* radii, const int32_t* cum_tiles, const int32_t* keep_scan,
-                            const int32_t* tile_offsets, const int32_t* flatten_ids, const float* render_alphas,
-                            const int32_t* last_ids, const float* v_render, const float* v_alphas, float* grad_slots,
-                            const int32_t* tile_order, ClassSel cls, const uint8_t* isect_reach, int32_t* any_record) {
-#define MOBGS_LAUNCH_MFMA(CDV, FLT)                                                                                   \
-    do {                                                                                                              \
-        if (mode == 2)                                                                                                \
-            hipLaunchKernelGGL((raster_bwd_mfma_kernel<CDV, FLT, true>), dim3(grid), dim3(64 * TILES_PER_WG), 0, st,  \
-                               nt, n_groups, tile_w, tile_h, width, height, records, backgrounds, radii, cum_tiles,   \
-                               keep_scan, tile_offsets, flatten_ids, render_alphas, last_ids, v_render, v_alphas,     \
-                               grad_slots, tile_order, cls, isect_reach, any_record);                                 \
-        else                                                                                                          \
-            hipLaunchKernelGGL((raster_bwd_mfma_kernel<CDV, FLT, false>), dim3(grid), dim3(64 * TILES_PER_WG), 0, st, \
-                               nt, n_groups, tile_w, tile_h, width, height, records, backgrounds, radii, cum_tiles,   \
-                               keep_scan, tile_offsets, flatten_ids, render_alphas, last_ids, v_render, v_alphas,     \
-                               grad_slots, tile_order, cls, isect_reach, any_record);                                 \
-    } while (0)
-    if (!filter) {
-        switch (D) {
-            case 1: MOBGS_LAUNCH_MFMA(1, false); return true;
-            case 3: MOBGS_LAUNCH_MFMA(3, false); return true;
-            case 4: MOBGS_LAUNCH_MFMA(4, false); return true;
-            case 9: MOBGS_LAUNCH_MFMA(9, false); return true;
-            case 10: MOBGS_LAUNCH_MFMA(10, false); return true;
-            default: return false;
+// launcher used by mobgs_raster_bwd / mobgs_raster_class_bwd (raster.hip) when their plan says BWD_MFMA (one wave per
+// tile + team for the schedule's heavy tiles) or BWD_MFMA_TEAM (team for every tile).  raster_plan chooses these only
+// for counts with a build here (has_bwd_mfma): any other count is a disagreement between plan and builds, an error.
+int raster_bwd_mfma_launch(int kernel, int D, bool class_filter, const RasterGrid& g, const RasterBwdArgs& a,
+                           const ClassSel& cls, hipStream_t st) {
+    bool built = false;
+    dispatch_channels(D, [&](auto cd) {
+        constexpr int CD = decltype(cd)::value;
+        auto launch = [&](auto filter) {
+            constexpr bool FILTER = decltype(filter)::value;
+            if (kernel == BWD_MFMA_TEAM)
+                launch_raster_bwd(raster_bwd_mfma_kernel<CD, FILTER, true>, g, a, st, cls);
+            else
+                launch_raster_bwd(raster_bwd_mfma_kernel<CD, FILTER, false>, g, a, st, cls);
+            built = true;
+        };
+        if constexpr (has_bwd_mfma(CD, true)) {
+            if (class_filter) launch(std::true_type{});
         }
+        if constexpr (has_bwd_mfma(CD, false)) {
+            if (!class_filter) launch(std::false_type{});
+        }
+    });
+    if (!built) {
+        set_error("raster_bwd_mfma_launch: no matrix-pipe backward is built for %d total channels (class_filter=%d)", D,
+                  (int)class_filter);
+        return MOBGS_E_UNSUPPORTED;
     }
-    switch (D) {
-        case 1: MOBGS_LAUNCH_MFMA(1, true); return true;
-        case 10: MOBGS_LAUNCH_MFMA(10, true); return true;
-        default: return false;
-    }
-#undef MOBGS_LAUNCH_MFMA
+    return MOBGS_OK;
 }
 
 }  // namespace mobgs

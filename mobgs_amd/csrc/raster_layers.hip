@@ -17,6 +17,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "raster_launch.h"
 
 namespace mobgs {
 
@@ -25,6 +26,7 @@ constexpr float L_ALPHA_MAX = 0.999f;
 constexpr float L_T_STOP = 1e-4f;
 constexpr int LPPL = 2;      // pixels per lane
 constexpr int LWAVES = 4;    // waves per workgroup = 2 tiles x 2 halves
+constexpr int LTILES = LWAVES / 2;   // tiles per workgroup
 constexpr int NL = 3;        // layers: 0 = all, 1 = static (flat id % N < Ns), 2 = dynamic
 
 __device__ inline void l_fence() {
@@ -523,13 +525,10 @@ int mobgs_raster_layers_fwd(int C, int N, int Ns, int layer_mask, int channels_t
             return MOBGS_E_INVALID;
         }
     }
-    const int tile_w = (width + MOBGS_TILE - 1) / MOBGS_TILE, tile_h = (height + MOBGS_TILE - 1) / MOBGS_TILE;
-    const int nt = C * tile_w * tile_h;
-    const int n_groups = (nt + 1) / 2;
-    const int grid = tile_order ? (int)((sched_slots((size_t)nt) + 1) / 2) : ((n_groups + 7) / 8) * 8;
-    hipLaunchKernelGGL(raster_layers_fwd_kernel<10>, dim3(grid), dim3(64 * LWAVES), 0, (hipStream_t)stream, nt, n_groups,
-                       tile_w, tile_h, width, height, N, Ns, layer_mask, records, backgrounds, tile_offsets, tile_order,
-                       flatten_ids, o);
+    const RasterGrid g = raster_grid(C, width, height, tile_order, LTILES);
+    hipLaunchKernelGGL(raster_layers_fwd_kernel<10>, dim3(g.grid), dim3(64 * LWAVES), 0, (hipStream_t)stream, g.nt,
+                       g.n_groups, g.tile_w, g.tile_h, width, height, N, Ns, layer_mask, records, backgrounds, tile_offsets,
+                       tile_order, flatten_ids, o);
     return check_launch("raster_layers_fwd_kernel");
 }
 
@@ -559,19 +558,16 @@ int mobgs_raster_layers_bwd(int C, int N, int Ns, int layer_mask, int channels, 
         }
     }
     hipStream_t st = (hipStream_t)stream;
-    const int tile_w = (width + MOBGS_TILE - 1) / MOBGS_TILE, tile_h = (height + MOBGS_TILE - 1) / MOBGS_TILE;
-    const int nt = C * tile_w * tile_h;
-    const int n_groups = (nt + 1) / 2;
-    const int grid = tile_order ? (int)((sched_slots((size_t)nt) + 1) / 2) : ((n_groups + 7) / 8) * 8;
-    hipLaunchKernelGGL(raster_layers_bwd_kernel<10>, dim3(grid), dim3(64 * LWAVES), 0, st, nt, n_groups, tile_w, tile_h,
-                       width, height, N, Ns, layer_mask, records, backgrounds, radii, cum_tiles, keep_scan, tile_offsets,
-                       tile_order, flatten_ids, in, grad_slots, grad_xy0);
+    const RasterGrid g = raster_grid(C, width, height, tile_order, LTILES);
+    hipLaunchKernelGGL(raster_layers_bwd_kernel<10>, dim3(g.grid), dim3(64 * LWAVES), 0, st, g.nt, g.n_groups, g.tile_w,
+                       g.tile_h, width, height, N, Ns, layer_mask, records, backgrounds, radii, cum_tiles, keep_scan,
+                       tile_offsets, tile_order, flatten_ids, in, grad_slots, grad_xy0);
     const int n = C * N;
     if (n > 0)
         hipLaunchKernelGGL(layers_slot_reduce_kernel, dim3((int)(((size_t)n * 16 + 255) / 256)), dim3(256), 0, st, n,
                            channels, has_extra, record_stride(D), cum_tiles, keep_scan, grad_slots, grad_xy0,
                            v_means2d_layer0, v_means2d, v_conics, v_opacities, v_colors, v_extra, tiles_per_gauss,
-                           tile_offsets ? tile_offsets + nt : nullptr);
+                           tile_offsets ? tile_offsets + g.nt : nullptr);
     return check_launch("raster_layers_bwd_kernel");
 }
 
