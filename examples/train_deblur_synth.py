@@ -59,6 +59,55 @@ class _Intrinsics:
         self.skew = float(K[0, 1])
 
 
+def sets_from_views(dev, ns, nd, width, height, dec, seed=0, n_views=12, n_tracks=2000):
+    """--from-views: both sets built the way train.py builds them from a data set -- synthetic training views (a slanted
+    textured plane with its analytic depth, a disc of another colour that moves across it and carries the motion mask,
+    2-D tracks that follow the plane and the disc) -> scene_init.scene_initialization -> from_pcd / from_pcd_dynamic.
+    12 views: the spline fit wants at least as many trajectory samples as control points."""
+    import math
+    import types
+
+    from mobgs_amd.scene_init import scene_initialization
+    scam = SynthCamera().scaled(width, height)
+    f, cx, cy = float(scam.focal), width / 2.0, height / 2.0
+    D = torch.float64
+    normal, offset = torch.tensor([0.15, -0.1, 1.0], dtype=D), 3.5          # the plane normal . X = offset
+    vv, uu = torch.meshgrid(torch.arange(height, dtype=D), torch.arange(width, dtype=D), indexing="ij")
+    rays = torch.stack([(uu - cx) / f, (vv - cy) / f, torch.ones_like(uu)], -1).reshape(-1, 3)
+    half_w = offset * width / (2 * f)
+    g = torch.Generator().manual_seed(seed + 300)
+    track_xy = torch.stack([(2 * torch.rand(n_tracks, generator=g, dtype=D) - 1) * 1.2 * half_w,
+                            (2 * torch.rand(n_tracks, generator=g, dtype=D) - 1) * 1.2 * half_w * height / width], 1)
+    disc = lambda i: torch.tensor([-0.5 * half_w + 0.08 * half_w * i, 0.05], dtype=D)  # noqa: E731
+    radius = 0.22 * half_w
+    follows = ((track_xy - disc(0)) ** 2).sum(1) < radius ** 2
+    views, tracks = [], []
+    for i in range(n_views):
+        a = (i - (n_views - 1) / 2) * 0.01
+        R = torch.tensor([[math.cos(a), 0, -math.sin(a)], [0, 1, 0], [math.sin(a), 0, math.cos(a)]], dtype=D)
+        eye = torch.tensor([0.04 * (i - (n_views - 1) / 2), 0.0, 0.0], dtype=D)
+        world_rays = rays @ R                                               # R^T applied to every camera ray
+        depth = (offset - normal @ eye) / (world_rays @ normal)
+        X = eye + depth[:, None] * world_rays
+        on_disc = ((X[:, :2] - disc(i)) ** 2).sum(1) < radius ** 2
+        colour = torch.stack([0.5 + 0.3 * torch.sin(1.7 * X[:, 0] + 0.4), 0.5 + 0.3 * torch.sin(1.3 * X[:, 1] - 0.7),
+                              0.5 + 0.3 * torch.cos(0.9 * X[:, 0] - 1.6 * X[:, 1])])
+        colour[:, on_disc] = torch.tensor([0.95, 0.12, 0.10], dtype=D)[:, None]
+        p = track_xy + torch.where(follows[:, None], disc(i) - disc(0), torch.zeros(2, dtype=D))
+        P = torch.cat([p, ((offset - normal[0] * p[:, 0] - normal[1] * p[:, 1]) / normal[2])[:, None]], 1)
+        cam = (P - eye) @ R.T
+        tracks.append(torch.stack([f * cam[:, 0] / cam[:, 2] + cx, f * cam[:, 1] / cam[:, 2] + cy], 1))
+        views.append(types.SimpleNamespace(
+            original_image=colour.reshape(3, height, width).float().to(dev), depth=depth.reshape(1, height, width).float().to(dev),
+            R=R.T.float().numpy(), T=(-R @ eye).float().numpy(), focal=f, time=i / (n_views - 1.0),
+            metadata=types.SimpleNamespace(principal_point_x=cx, principal_point_y=cy),
+            mask=on_disc.reshape(1, height, width).float().to(dev)))
+    views[0].tracklet = torch.stack(tracks).float().to(dev)
+    stat_pc, dyn_pc, trajectory = scene_initialization(views, ns, nd, generator=torch.Generator().manual_seed(seed + 301))
+    return (TrainableGaussians.from_pcd(stat_pc, 5.0, decoder=dec, device=dev),
+            TrainableGaussians.from_pcd_dynamic(dyn_pc, 5.0, 0, trajectory, decoder=dec, device=dev))
+
+
 class DeblurTrainer:
     """State of the miniature training loop; `iteration()` is ONE iteration of train.py:430-807 on this stack:
     blurry views (K latent renders each, BLCE cameras) -> K get_flow() calls per view -> photometric + depth + mask +
@@ -66,7 +115,7 @@ class DeblurTrainer:
     Adam on both Gaussian sets (incl. the decoder) and the BLCE parameters.  bench.py times it at full size."""
 
     def __init__(self, dev="cuda:0", ns=4000, nd=2000, width=256, height=192, n_views=2, seed=0, lambda_flow=1e-2,
-                 shard=None, iters=40):
+                 shard=None, iters=40, from_views=False):
         from mobgs_amd.main_utils import get_normals
         self.get_normals = get_normals
         self.shard = shard = shard or SubframeShard()
@@ -76,8 +125,12 @@ class DeblurTrainer:
         dec = Sandwich(9, 3).to(dev)
         sp, dp = gaussian_cloud(ns, scam, seed), gaussian_cloud(nd, scam, seed + 1)
         dx = dynamic_extras(dp["xyz"], seed)
-        self.stat = stat = TrainableGaussians(sp, None, dec, device=dev)
-        self.dyn = dyn = TrainableGaussians(dp, dx, dec, device=dev)
+        if from_views:   # opt-in: the two sets come from synthetic views through scene_initialization
+            self.stat, self.dyn = sets_from_views(dev, ns, nd, width, height, dec, seed)
+        else:
+            self.stat = TrainableGaussians(sp, None, dec, device=dev)
+            self.dyn = TrainableGaussians(dp, dx, dec, device=dev)
+        stat, dyn = self.stat, self.dyn
         self.bg = bg = torch.zeros(9, device=dev)
         g = torch.Generator().manual_seed(seed + 100)
         self.cams = cams = []
@@ -319,15 +372,17 @@ class DeblurTrainer:
 
 
 def train(dev="cuda:0", iters=40, ns=4000, nd=2000, width=256, height=192, n_views=2, seed=0, lambda_flow=1e-2,
-          shard=None, log=None, graph=False, prune_control_every=0):
+          shard=None, log=None, graph=False, prune_control_every=0, from_views=False):
     """graph=True (single process): forward + losses + backward of the iteration recorded ONCE as a HIP graph
     (mobgs_amd.graphed.GraphedCallable) and replayed, the Adam step outside -- for small images / few Gaussians, where an
     iteration is ~1400 launches and bound by the host (the reference's own 512x288 / 30 k operating point: 9.5 -> 7.5 ms).
     prune_control_every=K > 0: every K iterations, between two iterations and outside any capture, the dynamic set drops
     one spline control point where that moves the projected trajectory by at most dyn.error_threshold pixels
     (TrainableGaussians.onedown_control_pts; in place, so a recorded iteration stays valid) and the smallest count is
-    logged as train.py:734 does (MinCtrl)."""
-    t = DeblurTrainer(dev, ns, nd, width, height, n_views, seed, lambda_flow, shard, iters)
+    logged as train.py:734 does (MinCtrl).
+    from_views=True: both sets are built by scene_init.scene_initialization from synthetic views (sets_from_views)
+    instead of being sampled directly."""
+    t = DeblurTrainer(dev, ns, nd, width, height, n_views, seed, lambda_flow, shard, iters, from_views)
     history = []
     prune_views = t.prune_viewpoints() if prune_control_every else None
     fb, pending = None, []
@@ -376,6 +431,8 @@ if __name__ == "__main__":
     ap.add_argument("--graph", action="store_true", help="replay forward + backward as one HIP graph (single process)")
     ap.add_argument("--prune-control-every", type=int, default=0, metavar="K",
                     help="every K iterations drop one spline control point where the trajectory moves <= 1 px (0 = never)")
+    ap.add_argument("--from-views", action="store_true",
+                    help="build both sets through scene_initialization from synthetic views instead of sampling them")
     a = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -384,4 +441,4 @@ if __name__ == "__main__":
         torch.cuda.set_device(local)
         dist.init_process_group("nccl", device_id=torch.device("cuda", local))
     train(dev=f"cuda:{local}", iters=a.iters, ns=a.ns, nd=a.nd, width=a.width, height=a.height, log=10, graph=a.graph,
-          prune_control_every=a.prune_control_every)
+          prune_control_every=a.prune_control_every, from_views=a.from_views)

@@ -147,7 +147,7 @@ int mobgs_cotangent_probe(int n_arrays, const float* const* arrays, const size_t
  * points changes (round 4 inserted `records` into mobgs_raster_bwd_reduce and changed the gradient-slot format without
  * one: a stale host extension would have passed shifted pointers).  Bindings compare it with the MOBGS_ABI_VERSION
  * they were built against and refuse to run on a mismatch (mobgs_amd/_lib.py, csrc/fastpath.cpp). */
-#define MOBGS_ABI_VERSION 11
+#define MOBGS_ABI_VERSION 12
 int mobgs_abi_version(void);
 /* Text of the last error raised on the calling thread ("" if none). */
 const char* mobgs_last_error(void);
@@ -883,6 +883,37 @@ int mobgs_knn3_mean_dist2(int n, const float* points, float* dist2, void* scratc
 int mobgs_control_onedown(int n_rows, int n_views, const float* viewmats, const float* times, float focal, float cx,
                           float cy, const float* pinv_table, float threshold, float* control_xyz, int64_t* control_num,
                           float* err_out, float* new_control_out, int* counters, int commit, void* stream);
+
+/* ---- K19: seeding both Gaussian sets from depth maps, poses and 2-D tracks (scene initialisation) -------------------
+ * The numerical part of the reference's scene_initialization (/root/reference/train.py:58-199) in three launches on
+ * the caller's stream, with no float atomics and no host synchronisation.  V views of H x W pixels, 2 <= V <= 4096,
+ * H, W >= 2, H * W <= 2^28 (anything else is refused before any launch; mobgs_seed_scratch_bytes returns 0 for it).
+ *
+ * mobgs_seed_consistency: images [V,3,H,W], depths [V,H,W], pair_table [V,V,12]; entry (i, j) is the row-major 3x4
+ *   matrix K_j [R_j R_i^T | t_j - R_j R_i^T t_i] K_i^-1 that takes (d u, d v, d, 1) of pixel (u, v) with depth d in view
+ *   i to the homogeneous pixel (x, y, z) of view j (the caller builds it in float64: mobgs_amd.scene_init.pair_table).
+ *   Per (pixel of i, view j), as inverse_warp_rt1_rt2 + train.py:105-106: |z| < 1e-6 -> 1e-6; normalise 2 (x / z) /
+ *   (W - 1) - 1, 2 (y / z) / (H - 1) - 1; either coordinate outside [-1, 1] -> the sample is zero; else the 4-tap bilinear
+ *   sample (align_corners, zero padding) of the 3 channels of image j; out_mask = (sum of channels > 0);
+ *   accum_error[i] += mean_c(out_mask |sample - image_i|), j = i included.  scratch receives one partial sum of
+ *   accum_error per workgroup: mobgs_seed_scratch_bytes(V, H, W) bytes, 4-byte aligned.
+ * mobgs_seed_classify: reads that scratch; mean[i] = sum of view i's partials (fixed order: deterministic) / (H W);
+ *   inconsistent = accum_error > mean[i] (uint8); cls = 0 (static candidate: !inconsistent and motion == 0), 1 (dynamic
+ *   candidate: inconsistent and motion == 1) or 2 (neither; any other motion byte lands here); points [V,H,W,3] =
+ *   unproject_table[i] (d u, d v, d, 1), unproject_table [V,12] holding the row-major 3x4 [R_i^T K_i^-1 | -R_i^T t_i].
+ * mobgs_seed_trajectories: coords [N,2] pixel coordinates, tracklet [T,M,2] with T == V (refused otherwise), points as
+ *   above.  track_index[n] = argmin_m |coords[n] - tracklet[0][m]|^2, evaluated in fp32 as (dx dx + dy dy) without FMA
+ *   contraction, ties to the lowest m; trajectory [N,T,3]: points[t] at the pixel (nearbyint(u - 0.5), nearbyint(v - 0.5))
+ *   (ties to even) of (u, v) = tracklet[t][track_index[n]] -- grid_sample(mode="nearest", align_corners=False,
+ *   padding_mode="zeros") after the reference's / W, / H, * 2 - 1 -- and zeros outside the image.  N == 0 is a no-op. */
+size_t mobgs_seed_scratch_bytes(int V, int H, int W);
+int mobgs_seed_consistency(int V, int H, int W, const float* images, const float* depths, const float* pair_table,
+                           float* accum_error, void* scratch, size_t scratch_bytes, void* stream);
+int mobgs_seed_classify(int V, int H, int W, const float* accum_error, const void* scratch, size_t scratch_bytes,
+                        const float* depths, const uint8_t* motion, const float* unproject_table,
+                        uint8_t* inconsistent, uint8_t* cls, float* points, float* mean, void* stream);
+int mobgs_seed_trajectories(int N, int T, int M, int V, int H, int W, const float* coords, const float* tracklet,
+                            const float* points, int32_t* track_index, float* trajectory, void* stream);
 
 #ifdef __cplusplus
 }

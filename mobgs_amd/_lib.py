@@ -52,7 +52,7 @@ class MobgsPrepInputs(ctypes.Structure):
 
 
 P = c_void_p
-ABI_VERSION = 11  # include/mobgs_hip.h MOBGS_ABI_VERSION
+ABI_VERSION = 12  # include/mobgs_hip.h MOBGS_ABI_VERSION
 _SIGS = {
     "mobgs_version": (c_char_p, []),
     "mobgs_abi_version": (c_int, []),
@@ -154,6 +154,10 @@ _SIGS = {
     "mobgs_knn3_mean_dist2": (c_int, [c_int, P, P, P, c_size_t, P]),
     "mobgs_control_onedown": (c_int, [c_int, c_int, P, P, c_float, c_float, c_float, P, c_float, P, P, P, P, P, c_int,
                                       P]),
+    "mobgs_seed_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "mobgs_seed_consistency": (c_int, [c_int, c_int, c_int, P, P, P, P, P, c_size_t, P]),
+    "mobgs_seed_classify": (c_int, [c_int, c_int, c_int, P, P, c_size_t, P, P, P, P, P, P, P, P]),
+    "mobgs_seed_trajectories": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P]),
 }
 # entry points added by later translation units (bound if present in the header AND the library)
 _OPTIONAL_SIGS = {}

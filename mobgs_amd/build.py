@@ -13,7 +13,7 @@ from pathlib import Path
 CSRC = Path(__file__).resolve().parent / "csrc"
 # MOBGS_LIB: load another build of the same library instead (A/B timing of kernel variants on one GPU box)
 LIB_PATH = Path(os.environ["MOBGS_LIB"]).resolve() if os.environ.get("MOBGS_LIB") else CSRC / "libmobgs_hip.so"
-SOURCES = ["project.hip", "isect.hip", "raster.hip", "raster_bwd_mfma.hip", "raster_layers.hip", "pipeline.hip", "prep.hip", "decoder.hip", "deform.hip", "deform_bwd.hip", "hexplane_bwd.hip", "blce.hip", "loss.hip", "flowloss.hip", "densify.hip", "normals.hip", "knn.hip", "control_prune.hip"]
+SOURCES = ["project.hip", "isect.hip", "raster.hip", "raster_bwd_mfma.hip", "raster_layers.hip", "pipeline.hip", "prep.hip", "decoder.hip", "deform.hip", "deform_bwd.hip", "hexplane_bwd.hip", "blce.hip", "loss.hip", "flowloss.hip", "densify.hip", "normals.hip", "knn.hip", "control_prune.hip", "scene_seed.hip"]
 ARCH = "gfx950"
 # host fast path (csrc/fastpath.cpp): a plain C++ torch extension, no device code, no link against libmobgs_hip.so
 FAST_SRC = CSRC / "fastpath.cpp"
@@ -34,6 +34,9 @@ EXTRA_FLAGS["project.hip"] = EXTRA_FLAGS["project.hip"] + ["-ffp-contract=off"]
 # every squared distance is the one expression (dx dx + dy dy) + dz dz, symmetric in its two points, and the box bound
 # is the same expression on the gaps to the box, so that fp32 monotonicity makes the pruning exact (csrc/knn.hip).
 EXTRA_FLAGS["knn.hip"] = EXTRA_FLAGS.get("knn.hip", []) + ["-ffp-contract=off"]
+# scene_seed.hip: the same for the nearest-track search: (dx dx + dy dy) compares bit-equal with torch's
+# square().sum(-1).argmin(-1), so ties between tracks resolve to the same (lowest) index (csrc/scene_seed.hip).
+EXTRA_FLAGS["scene_seed.hip"] = EXTRA_FLAGS.get("scene_seed.hip", []) + ["-ffp-contract=off"]
 # raster.hip: top-down pre-RA machine scheduling.  The compositing loops are long straight-line blocks bound by VALU
 # issue; of ten scheduler settings swept in round 4 (scripts/ab/build_variant_raster.sh + kernel_ab2.sh, three A/B
 # repetitions on one box) this is the only one outside the noise: raster_bwd<10> 512 -> 506 us, raster_fwd_blocks<10>

@@ -2,6 +2,7 @@
 
     knn3_mean_dist2(points)                       simple_knn._C.distCUDA2 (CUDA-only upstream) -> csrc/knn.hip
     inverse_cubic_hermite(curves, times, N_pts)   /root/reference/scene/gaussian_model.py:18-88
+    scene_initialization(viewpoints, ...)         /root/reference/train.py:58-199 -> csrc/scene_seed.hip
     static_init(...) / dynamic_init(...)          the tensors of create_from_pcd (:495-582) / create_from_pcd_dynamic
                                                   (:406-493), as the constructor dictionaries of
                                                   densify.TrainableGaussians (from_pcd / from_pcd_dynamic)
@@ -14,7 +15,7 @@ pseudo-inverse on the host and one matrix product on the device.
 """
 from __future__ import annotations
 
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -162,7 +163,8 @@ def inverse_cubic_hermite(curves: torch.Tensor, times: torch.Tensor, N_pts: int 
 
 # ---- the initial state of a set ------------------------------------------------------------------------------------
 def _pcd_tensors(pcd) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    f = lambda a: torch.as_tensor(np.asarray(a)).float().cpu()  # noqa: E731
+    # (a tensor may live on the device -- scene_initialization leaves its clouds there -- np.asarray cannot read those)
+    f = lambda a: (a.detach() if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))).float().cpu()  # noqa: E731
     points, colors, times = f(pcd.points), f(pcd.colors), f(pcd.times)
     if points.dim() != 2 or points.shape[1] != 3 or colors.shape != points.shape:
         raise ValueError(f"pcd.points / pcd.colors must be [N,3], got {tuple(points.shape)} / {tuple(colors.shape)}")
@@ -368,3 +370,300 @@ def onedown_control_pts(pc, viewpoints, error_threshold: Optional[float] = None)
     global _last_counters
     _last_counters = counters
     return counters[0]
+
+
+# ---- seeding the two sets from depth maps, poses and 2-D tracks ------------------------------------------------------
+class SeedMaps(NamedTuple):
+    accum_error: torch.Tensor    # [V,H,W] float32: the masked photometric error summed over all views
+    inconsistent: torch.Tensor   # [V,H,W] uint8: accum_error > the view's own mean
+    cls: torch.Tensor            # [V,H,W] uint8: 0 static candidate, 1 dynamic candidate, 2 neither
+    points: torch.Tensor         # [V,H,W,3] float32: the world point of every pixel
+
+
+class PointCloud(NamedTuple):
+    """The fields of the reference's BasicPointCloud (utils/graphics_utils.py)."""
+    points: torch.Tensor
+    colors: torch.Tensor
+    normals: None
+    times: torch.Tensor
+
+
+def _rt64(w2c: torch.Tensor, K: torch.Tensor):
+    w = torch.as_tensor(w2c).detach().to("cpu", torch.float64)
+    k = torch.as_tensor(K).detach().to("cpu", torch.float64)
+    if w.dim() != 3 or tuple(w.shape[1:]) != (3, 4) or tuple(k.shape) != (w.shape[0], 3, 3):
+        raise ValueError(f"w2c must be [V,3,4] and K [V,3,3], got {tuple(w.shape)} and {tuple(k.shape)}")
+    return w[:, :, :3], w[:, :, 3], k
+
+
+def pair_table(w2c: torch.Tensor, K: torch.Tensor) -> torch.Tensor:
+    """float32 [V,V,12] on the host: entry (i, j) is the row-major 3x4 matrix K_j [R_j R_i^T | t_j - R_j R_i^T t_i] K_i^-1
+    that takes (d u, d v, d, 1) of pixel (u, v) with depth d in view i to the homogeneous pixel of view j.  Formed in
+    float64 and rounded once, as one_down_tables is."""
+    R, t, k = _rt64(w2c, K)
+    Rij = torch.einsum("jab,icb->ijac", R, R)                        # R_j R_i^T
+    A = torch.einsum("jab,ijbc,icd->ijad", k, Rij, torch.linalg.inv(k))
+    b = torch.einsum("jab,ijb->ija", k, t[None, :, :] - torch.einsum("ijab,ib->ija", Rij, t))
+    V = R.shape[0]
+    return torch.cat([A, b[..., None]], dim=-1).reshape(V, V, 12).float().contiguous()
+
+
+def unproject_table(w2c: torch.Tensor, K: torch.Tensor) -> torch.Tensor:
+    """float32 [V,12] on the host: the row-major 3x4 matrix [R_i^T K_i^-1 | -R_i^T t_i] (float64, rounded once) that takes
+    (d u, d v, d, 1) to the world point of the pixel (points_from_DRTK)."""
+    R, t, k = _rt64(w2c, K)
+    Rt = R.transpose(1, 2)
+    A = Rt @ torch.linalg.inv(k)
+    b = -(Rt @ t[..., None])
+    return torch.cat([A, b], dim=-1).reshape(-1, 12).float().contiguous()
+
+
+def nearest_pixel(u: torch.Tensor) -> torch.Tensor:
+    """The pixel that grid_sample(mode="nearest", align_corners=False) reads for the pixel coordinate u after the
+    reference's u / W * 2 - 1 (train.py:184-187): nearbyint(u - 0.5), ties to even."""
+    return torch.round(u - 0.5)
+
+
+def _check_views(images, depths, w2c, K, motion=None):
+    if images.dim() != 4 or images.shape[1] != 3:
+        raise ValueError(f"images must be [V,3,H,W], got {tuple(images.shape)}")
+    V, _, H, W = images.shape
+    if V < 2:
+        raise ValueError(f"scene seeding compares every view with the others: at least 2 views are needed, got {V}")
+    if H < 2 or W < 2:
+        raise ValueError(f"images must be at least 2 x 2 pixels, got {H} x {W}")
+    if tuple(depths.shape) != (V, H, W):
+        raise ValueError(f"depths must be [{V},{H},{W}] like the images, got {tuple(depths.shape)}")
+    if tuple(w2c.shape) != (V, 3, 4) or tuple(K.shape) != (V, 3, 3):
+        raise ValueError(f"w2c must be [{V},3,4] and K [{V},3,3], got {tuple(w2c.shape)} and {tuple(K.shape)}")
+    if motion is not None and tuple(motion.shape) != (V, H, W):
+        raise ValueError(f"motion_masks must be [{V},{H},{W}], got {tuple(motion.shape)}")
+    # one read-back; everything after it is enqueued without another
+    if not bool((torch.isfinite(depths) & (depths > 0)).all()):
+        raise ValueError("depths must be finite and positive everywhere (a pixel without depth has no world point)")
+    return V, H, W
+
+
+def _motion_bytes(motion: torch.Tensor) -> torch.Tensor:
+    """uint8: 0 where the mask is exactly 0, 1 where it is exactly 1, 2 elsewhere (the reference selects with
+    `motion_error == 0` / `== 1`, train.py:132-139: any other value is in neither set)."""
+    two = torch.full(motion.shape, 2, dtype=torch.uint8, device=motion.device)
+    return torch.where(motion == 0, torch.zeros_like(two), torch.where(motion == 1, torch.ones_like(two), two))
+
+
+def _seed_maps_host(images, depths, w2c, K, motion):
+    """The float64 composition for tensors on the host (no kernel runs there): the reference's own steps, view by view.
+    One of three statements of the sampling rules, with csrc/scene_seed.hip and tests/seed_restatement.py: they change
+    together."""
+    V, _, H, W = images.shape
+    img, d = images.double(), depths.double()
+    R, t, k = _rt64(w2c, K)
+    vv, uu = torch.meshgrid(torch.arange(H, dtype=torch.float64), torch.arange(W, dtype=torch.float64), indexing="ij")
+    pix = torch.stack([uu, vv, torch.ones_like(uu)], 0).reshape(3, -1)
+    accum = torch.zeros(V, H * W, dtype=torch.float64)
+    points = torch.empty(V, H * W, 3, dtype=torch.float64)
+    for i in range(V):
+        cam = (torch.linalg.inv(k[i]) @ pix) * d[i].reshape(1, -1)
+        world = R[i].T @ cam - (R[i].T @ t[i])[:, None]
+        points[i] = world.T
+        for j in range(V):
+            c2 = R[j] @ world + t[j][:, None]
+            z = torch.where(c2[2].abs() < 1e-6, torch.full_like(c2[2], 1e-6), c2[2])
+            p2 = k[j] @ (c2 / z)
+            xn, yn = 2 * p2[0] / (W - 1) - 1, 2 * p2[1] / (H - 1) - 1
+            inside = (xn >= -1) & (xn <= 1) & (yn >= -1) & (yn <= 1)
+            ix, iy = (xn + 1) / 2 * (W - 1), (yn + 1) / 2 * (H - 1)
+            x0, y0 = torch.floor(ix), torch.floor(iy)
+            s = torch.zeros(3, H * W, dtype=torch.float64)
+            for ox, oy in ((0, 0), (1, 0), (0, 1), (1, 1)):
+                xs, ys = x0 + ox, y0 + oy
+                w = (1 - (ix - xs).abs()) * (1 - (iy - ys).abs())
+                ok = inside & (xs >= 0) & (xs < W) & (ys >= 0) & (ys < H)
+                at = (ys.clamp(0, H - 1) * W + xs.clamp(0, W - 1)).long()
+                at = torch.where(ok, at, torch.zeros_like(at))
+                s = s + torch.where(ok, w, torch.zeros_like(w)) * img[j].reshape(3, -1)[:, at]
+            mask = (s.sum(0) > 0).double()
+            accum[i] += (mask * (s - img[i].reshape(3, -1)).abs()).mean(0)
+    mean = accum.mean(1)
+    inc = accum > mean[:, None]
+    mo = motion.reshape(V, -1)
+    cls = torch.full((V, H * W), 2, dtype=torch.uint8)
+    cls[~inc & (mo == 0)] = 0
+    cls[inc & (mo == 1)] = 1
+    return (accum.float().reshape(V, H, W), mean.float(), inc.to(torch.uint8).reshape(V, H, W), cls.reshape(V, H, W),
+            points.float().reshape(V, H, W, 3))
+
+
+def _seed_launch(images, depths, w2c, K, motion):
+    """-> (accum_error, mean [V], inconsistent, cls, points).  Device tensors: mobgs_seed_consistency, then
+    mobgs_seed_classify, on the current stream.  Host tensors: the float64 composition."""
+    images, depths = _lib.f32c(images.detach()), _lib.f32c(depths.detach())
+    V, H, W = _check_views(images, depths, w2c, K, motion)
+    dev = images.device
+    mbytes = torch.zeros(V, H, W, dtype=torch.uint8, device=dev) if motion is None else \
+        _motion_bytes(motion.detach().to(dev)).contiguous()
+    if not images.is_cuda:
+        return _seed_maps_host(images, depths, w2c, K, mbytes)
+    depths = depths.to(dev)
+    lib = _lib.load()
+    nbytes = int(lib.mobgs_seed_scratch_bytes(V, H, W))
+    if nbytes == 0:
+        raise ValueError(f"scene seeding: {V} views of {H} x {W} pixels are outside what mobgs_seed_* accepts "
+                         "(2..4096 views, H * W <= 2^28)")
+    pairs, unproj = pair_table(w2c, K).to(dev), unproject_table(w2c, K).to(dev)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    accum = torch.empty(V, H, W, dtype=torch.float32, device=dev)
+    check(lib.mobgs_seed_consistency(V, H, W, ptr(images), ptr(depths), ptr(pairs), ptr(accum), ptr(scratch), nbytes,
+                                     stream()), "mobgs_seed_consistency")
+    inc = torch.empty(V, H, W, dtype=torch.uint8, device=dev)
+    cls = torch.empty(V, H, W, dtype=torch.uint8, device=dev)
+    points = torch.empty(V, H, W, 3, dtype=torch.float32, device=dev)
+    mean = torch.empty(V, dtype=torch.float32, device=dev)
+    check(lib.mobgs_seed_classify(V, H, W, ptr(accum), ptr(scratch), nbytes, ptr(depths), ptr(mbytes), ptr(unproj),
+                                  ptr(inc), ptr(cls), ptr(points), ptr(mean), stream()), "mobgs_seed_classify")
+    return accum, mean, inc, cls, points
+
+
+@torch.no_grad()
+def view_consistency(images: torch.Tensor, depths: torch.Tensor, w2c: torch.Tensor, K: torch.Tensor
+                     ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(accum_error [V,H,W], mean [V]): every view warped into every other through the target's depth map, the masked
+    photometric error summed per target pixel (train.py:90-108), and its mean per view.  images [V,3,H,W], depths
+    [V,H,W] (finite, positive), w2c [V,3,4], K [V,3,3]."""
+    accum, mean, _, _, _ = _seed_launch(images, depths, w2c, K, None)
+    return accum, mean
+
+
+@torch.no_grad()
+def seed_maps(images: torch.Tensor, depths: torch.Tensor, w2c: torch.Tensor, K: torch.Tensor,
+              motion_masks: torch.Tensor) -> SeedMaps:
+    """view_consistency plus, per pixel, the thresholded error, the candidate class against `motion_masks` [V,H,W]
+    (0 = still, 1 = moving) and the world point (train.py:108-158).  Two launches, one read-back (the depth check)."""
+    accum, _, inc, cls, points = _seed_launch(images, depths, w2c, K, motion_masks)
+    return SeedMaps(accum, inc, cls, points)
+
+
+@torch.no_grad()
+def track_trajectories(coords: torch.Tensor, tracklet: torch.Tensor, points: torch.Tensor
+                       ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(track_index [N] int32, trajectory [N,T,3]): for every pixel coordinate coords[n] the track whose start
+    tracklet[0] is nearest (fp32 squared distance, ties to the lowest index), and points[t] read at that track's position
+    in every frame t (nearest_pixel; zeros where the track has left the image).  tracklet [T,M,2], points [V,H,W,3] with
+    T == V (train.py:171-189)."""
+    if points.dim() != 4 or points.shape[3] != 3:
+        raise ValueError(f"points must be [V,H,W,3], got {tuple(points.shape)}")
+    V, H, W, _ = points.shape
+    if tracklet.dim() != 3 or tracklet.shape[2] != 2 or tracklet.shape[1] < 1:
+        raise ValueError(f"tracklet must be [T,M,2] with M >= 1, got {tuple(tracklet.shape)}")
+    T, M, _ = tracklet.shape
+    if T != V:
+        raise ValueError(f"the tracklet has {T} frames and the point maps {V} views: one frame per view is needed")
+    if coords.dim() != 2 or coords.shape[1] != 2:
+        raise ValueError(f"coords must be [N,2], got {tuple(coords.shape)}")
+    dev = points.device
+    coords, tracklet = _lib.f32c(coords.detach().to(dev)), _lib.f32c(tracklet.detach().to(dev))
+    points = _lib.f32c(points.detach())
+    N = int(coords.shape[0])
+    if not points.is_cuda:
+        d = torch.square(coords[:, None, :] - tracklet[0][None]).sum(-1)       # fp32, as the reference forms it
+        index = d.argmin(-1)
+        uv = tracklet[:, index, :].double()                                    # [T,N,2]
+        x, y = nearest_pixel(uv[..., 0]), nearest_pixel(uv[..., 1])
+        ok = (x >= 0) & (x < W) & (y >= 0) & (y < H)
+        at = torch.where(ok, y * W + x, torch.zeros_like(x)).long()
+        got = torch.gather(points.reshape(V, H * W, 3), 1, at[..., None].expand(-1, -1, 3))
+        got = torch.where(ok[..., None], got, torch.zeros_like(got))
+        return index.to(torch.int32), got.permute(1, 0, 2).contiguous()
+    index = torch.empty(N, dtype=torch.int32, device=dev)
+    traj = torch.empty(N, T, 3, dtype=torch.float32, device=dev)
+    if N:
+        check(_lib.load().mobgs_seed_trajectories(N, T, M, V, H, W, ptr(coords), ptr(tracklet), ptr(points), ptr(index),
+                                                  ptr(traj), stream()), "mobgs_seed_trajectories")
+    return index, traj
+
+
+def seed_view_arrays(viewpoints, device=None):
+    """(images [V,3,H,W], depths [V,H,W], w2c [V,3,4] float64 host, K [V,3,3] float64 host, motion [V,H,W], times [V],
+    tracklet [T,M,2]) read from cameras as scene_initialization reads them (train.py:71-99,128,171): original_image,
+    depth, R (stored transposed: the world-to-camera rotation is R.T), T, focal, metadata.principal_point_x / _y, mask,
+    time, and the tracklet of the FIRST view."""
+    if len(viewpoints) < 2:
+        raise ValueError(f"scene_initialization compares every view with the others: at least 2 viewpoints are "
+                         f"needed, got {len(viewpoints)}")
+    shapes = {tuple(v.original_image.shape) for v in viewpoints}
+    if len(shapes) != 1:
+        raise ValueError(f"all views must have one image size, got {sorted(shapes)}")
+    dev = torch.device(device) if device is not None else viewpoints[0].original_image.device
+    T_ = lambda a: a.detach() if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))  # noqa: E731
+    images = torch.stack([T_(v.original_image).to(dev, torch.float32) for v in viewpoints])
+    V, _, H, W = images.shape
+    depths = torch.stack([T_(v.depth).to(dev, torch.float32).reshape(H, W) for v in viewpoints])
+    motion = torch.stack([T_(v.mask).to(dev, torch.float32).reshape(H, W) for v in viewpoints])
+    w2c = torch.zeros(V, 3, 4, dtype=torch.float64)
+    K = torch.zeros(V, 3, 3, dtype=torch.float64)
+    for i, v in enumerate(viewpoints):
+        w2c[i, :, :3] = T_(v.R).to("cpu", torch.float64).T
+        w2c[i, :, 3] = T_(v.T).to("cpu", torch.float64)
+        K[i, 0, 0] = K[i, 1, 1] = float(v.focal)
+        K[i, 0, 2], K[i, 1, 2] = float(v.metadata.principal_point_x), float(v.metadata.principal_point_y)
+        K[i, 2, 2] = 1.0
+    times = torch.tensor([float(v.time) for v in viewpoints], dtype=torch.float32)
+    tracklet = T_(viewpoints[0].tracklet).to(dev, torch.float32)
+    if tracklet.dim() != 3 or tracklet.shape[0] != V:
+        raise ValueError(f"the tracklet of the first view must be [T,M,2] with one frame per view (T = {V}), got "
+                         f"{tuple(tracklet.shape)}")
+    return images, depths, w2c, K, motion, times, tracklet
+
+
+@torch.no_grad()
+def scene_initialization(viewpoints, stat_npts: int, dyn_npts: int, *, generator: Optional[torch.Generator] = None,
+                         select=None, device=None):
+    """The reference's scene_initialization (train.py:58-199) -> (stat_pc, dyn_pc, dyn_tracjectory), ready for
+    TrainableGaussians.from_pcd(stat_pc, ...) and from_pcd_dynamic(dyn_pc, ..., dyn_tracjectory).  The clouds carry the
+    fields of BasicPointCloud; their tensors stay on the device of the images (or `device`).
+
+    Static points are drawn without replacement from the static candidates of ALL views (in view order, row-major inside
+    a view, as the reference concatenates them); dynamic points from the dynamic candidates of view 0 only, with
+    replacement when there are fewer than `dyn_npts`.  The draw comes from `generator` (torch; the reference uses
+    Python's `random`, whose sequence is not reproduced); `select=(stat_idx, dyn_idx)` -- indices into the two candidate
+    lists -- replaces it: `stat_npts` and `dyn_npts` are then unused (the clouds have as many points as `select` names) and
+    only the indices' range is checked.  `device` moves the views there first (default: where the first image lives).  Raises ValueError for fewer than 2 views, a tracklet whose frame count is not the view
+    count, mixed image sizes, a depth that is not finite and positive, more static points asked for than there are
+    candidates, and no dynamic candidate at all."""
+    images, depths, w2c, K, motion, times, tracklet = seed_view_arrays(viewpoints, device)
+    V, _, H, W = images.shape
+    maps = seed_maps(images, depths, w2c, K, motion)
+    dev = images.device
+    stat_flat = torch.nonzero(maps.cls.reshape(-1) == 0).reshape(-1)          # index into [V * H * W]
+    dyn_flat = torch.nonzero(maps.cls[0].reshape(-1) == 1).reshape(-1)        # view 0: index into [H * W]
+    n_stat, n_dyn = int(stat_flat.shape[0]), int(dyn_flat.shape[0])
+    if select is not None:
+        stat_idx = torch.as_tensor(np.asarray(select[0])).long().reshape(-1)
+        dyn_idx = torch.as_tensor(np.asarray(select[1])).long().reshape(-1)
+        if stat_idx.numel() and not (0 <= int(stat_idx.min()) and int(stat_idx.max()) < n_stat):
+            raise ValueError(f"select: static indices must lie in 0..{n_stat - 1}")
+        if n_dyn == 0 or (dyn_idx.numel() and not (0 <= int(dyn_idx.min()) and int(dyn_idx.max()) < n_dyn)):
+            raise ValueError(f"select: dynamic indices must lie in 0..{n_dyn - 1}")
+    else:
+        if int(stat_npts) > n_stat:
+            raise ValueError(f"stat_npts = {stat_npts} but only {n_stat} static candidates exist (pixels that are "
+                             "consistent across the views and outside the motion masks)")
+        if n_dyn == 0:
+            raise ValueError("no dynamic candidate in the first view (no pixel is both inconsistent across the views "
+                             "and inside its motion mask)")
+        stat_idx = torch.randperm(n_stat, generator=generator)[:int(stat_npts)]
+        if n_dyn < int(dyn_npts):
+            dyn_idx = torch.randint(n_dyn, (int(dyn_npts),), generator=generator)
+        else:
+            dyn_idx = torch.randperm(n_dyn, generator=generator)[:int(dyn_npts)]
+    stat_at, dyn_at = stat_flat[stat_idx.to(dev)], dyn_flat[dyn_idx.to(dev)]
+    colors = images.permute(0, 2, 3, 1).reshape(-1, 3)
+    points = maps.points.reshape(-1, 3)
+    times = times.to(dev)
+    stat_pc = PointCloud(points=points[stat_at], colors=colors[stat_at], normals=None,
+                         times=times[torch.div(stat_at, H * W, rounding_mode="floor")].reshape(-1, 1))
+    dyn_pc = PointCloud(points=points[dyn_at], colors=colors[dyn_at], normals=None,
+                        times=times[0].expand(dyn_at.shape[0]).reshape(-1, 1).contiguous())
+    coords = torch.stack([dyn_at % W, torch.div(dyn_at, W, rounding_mode="floor")], dim=1).to(torch.float32)
+    _, trajectory = track_trajectories(coords, tracklet, maps.points)
+    return stat_pc, dyn_pc, trajectory
