@@ -159,7 +159,9 @@ __global__ void __launch_bounds__(256) adam_step_kernel(AdamTable tab, float w1,
     if (i0 >= T.n) return;
     auto one = [&](float& p, float g, float& m, float& v) {
         m = m + w1 * (g - m);                  // exp_avg.lerp_(grad, 1 - beta1)
-        v = v * beta2 + w2 * g * g;            // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
+        // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2); torch.optim.Adam's multi-tensor addcmul forms
+        // grad * grad first, so |grad| >= 1.9e19 overflows to inf there -- (w2 * g) * g stayed finite up to 5.8e20
+        v = v * beta2 + w2 * (g * g);
         const float denom = sqrtf(v) / T.bias2_sqrt + eps;
         p = p - T.step_size * (m / denom);     // param.addcdiv_(exp_avg, denom, value = -step_size)
     };

@@ -148,9 +148,11 @@ _pack_memo = {}
 
 def invalidate_packed_weights() -> None:
     """Forget the re-laid-out MLP weights.  Needed only after edits autograd's version counter does not see -- writes
-    through `p.data` (`p.data.copy_()`, manual EMA / weight surgery, old-style optimizers): in-place ops on the
-    parameter itself (every torch.optim step, load_state_dict, `with torch.no_grad(): p.mul_()`) bump `_version`
-    and re-pack automatically, and a re-allocated `.data` changes the storage pointer that is part of the key."""
+    through `p.data` (`p.data.copy_()`, manual EMA / weight surgery, old-style optimizers) and kernels that write a
+    parameter through its raw pointer without calling torch.autograd.graph.increment_version() afterwards: in-place ops
+    on the parameter itself (every torch.optim step, load_state_dict, `with torch.no_grad(): p.mul_()`) bump `_version`
+    and re-pack automatically, optim.fused_adam_step / FusedAdam.step move `_version` of every parameter their kernel
+    wrote, and a re-allocated `.data` changes the storage pointer that is part of the key."""
     _pack_memo.clear()
 
 

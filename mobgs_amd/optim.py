@@ -83,8 +83,8 @@ def fused_adam_step(optimizers: Iterable[torch.optim.Optimizer]) -> int:
                 for p, g in hidden:
                     p.grad = g
     if batches:
-        # the kernel writes the parameters through raw pointers: Tensor._version does not move, which is what render-side
-        # caches key on (gaussian_renderer._shared_mid_state: ADVICE r5) -- tell them
+        # the kernel writes the parameters through raw pointers: the render-side caches that are told directly
+        # (gaussian_renderer._shared_mid_state: ADVICE r5) ...
         from . import gaussian_renderer as _GR
         _GR.parameters_changed()
     for (b1, b2, eps), descs in batches.items():
@@ -92,6 +92,10 @@ def fused_adam_step(optimizers: Iterable[torch.optim.Optimizer]) -> int:
             chunk = descs[i:i + 64]
             arr = (_AdamTensor * len(chunk))(*chunk)
             check(lib.mobgs_adam_step(len(chunk), arr, b1, b2, eps, stream()), "mobgs_adam_step")
+    # ... and Tensor._version, which everything else keys on (deformation._packed, _lib.DerivedCache, blce.py): moved
+    # by hand for every parameter the kernel wrote, as torch's own in-place step would have (host only)
+    for i in range(0, len(keep), 4):
+        torch.autograd.graph.increment_version(keep[i])
     return fused
 
 

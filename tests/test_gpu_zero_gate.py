@@ -215,10 +215,11 @@ def test_separate_get_flow_calls_share_the_mid_exposure_state(hip_device):
 
 
 def test_mid_state_cache_sees_the_fused_adam_step_and_row_permutations(hip_device):
-    """optim.fused_adam_step writes the parameters through raw pointers -- Tensor._version does not
-    move -- and GaussianParams.spatial_sort_ swaps `.data`; the implicit mid-exposure cache of separate get_flow() calls
-    keyed on (storage, version, shape) would hand back the projection of the OLD values.  Both now announce themselves
-    (gaussian_renderer.parameters_changed): the next call is a miss and renders the new parameters."""
+    """optim.fused_adam_step writes the parameters through raw pointers and GaussianParams.spatial_sort_
+    swaps `.data`; the implicit mid-exposure cache of separate get_flow() calls keyed on (storage, version, shape) would
+    hand back the projection of the OLD values.  Both announce themselves (gaussian_renderer.parameters_changed), and
+    the fused step also moves Tensor._version of what it wrote: the next call is a miss and renders
+    the new parameters."""
     import mobgs_amd.gaussian_renderer as G
     from mobgs_amd.optim import fused_adam_step
     dev = hip_device
@@ -233,7 +234,7 @@ def test_mid_state_cache_sees_the_fused_adam_step_and_row_permutations(hip_devic
     dyn.control_xyz.grad = torch.ones_like(dyn.control_xyz)
     stat._xyz.grad = torch.ones_like(stat._xyz)
     assert fused_adam_step([opt]) == 2
-    assert (dyn.control_xyz._version, stat._xyz._version) == ver, "(the premise: the fused step does not bump versions)"
+    assert dyn.control_xyz._version > ver[0] and stat._xyz._version > ver[1], "the fused step moves the version counters"
     m0 = G.mid_cache_stats["misses"]
     with torch.no_grad():
         o2 = G.get_flow(cam, stat, dyn, None, bg, delta_exposure=0.25)
