@@ -241,31 +241,12 @@ struct BinArgs {
     int opac_per_camera, cull;
 };
 
-// ---- launchers shared between translation units (the orchestrator in pipeline.hip fuses small steps) ---------
-// project_fwd with the option to clear `zero_n` ints at `zero_ptr` on the way (the binning scratch counters) and to
-// pack the compositor's records
-int project_fwd_launch(int C, int N, const float* means, const float* quats, const float* scales, const float* viewmats,
-                       const float* Ks, int width, int height, float eps2d, float near_plane, float far_plane,
-                       float radius_clip, int32_t* radii, float* means2d, float* depths, float* conics,
-                       int32_t* tiles_per_gauss, int32_t* zero_ptr, size_t zero_n, PackArgs pack, void* stream,
-                       int geometry_per_camera = 0, BinArgs bin = BinArgs{nullptr, nullptr, 0, 0},
-                       const MobgsPrepInputs* prep = nullptr);
-// mobgs_isect_offsets; scratch_zeroed: the counters were cleared by the caller; stats_mirror: device-visible host
-// address that receives a copy of stats[0..2] (or NULL) and then, in word 3, stats_seq (when non-zero)
-int isect_offsets_launch(int C, int N, int tile_w, int tile_h, int width, int height, int cull, int capacity,
-                         const int32_t* tiles_per_gauss, const float* means2d, const int32_t* radii, const float* conics,
-                         const float* opacities, int opac_per_camera, int32_t* cum_tiles, int32_t* keep_scan,
-                         int32_t* tile_offsets, int32_t* tile_order, int64_t capacity_listed, int64_t* stats,
-                         void* scratch, bool scratch_zeroed, int64_t* stats_mirror, int64_t stats_seq,
-                         const MobgsTuning* tuning, void* stream);
-
 // per-call policy (include/mobgs_hip.h MobgsTuning): NULL or a negative field = the library default
 // default: lists of >= 1024 entries; on grids too small to fill the chip every non-empty list qualifies
 inline int tuning_heavy_len(const MobgsTuning* t, int n_tiles) {
     if (t && t->heavy_tile_len >= 0) return t->heavy_tile_len;
     return (size_t)n_tiles <= SCHED_SMALL_GRID ? 1 : 1024;
 }
-inline int tuning_list_hint(const MobgsTuning* t) { return (t && t->longest_list_hint >= 0) ? t->longest_list_hint : 0; }
 inline int tuning_all_reach(const MobgsTuning* t) { return (t && t->quadrant_culling == 0) ? 1 : 0; }
 inline int tuning_block_walk(const MobgsTuning* t) { return (t && t->block_walk == 0) ? 0 : 1; }
 inline int tuning_bwd_block_walk(const MobgsTuning* t) { return (t && t->bwd_block_walk == 1) ? 1 : 0; }
@@ -287,15 +268,6 @@ inline int tuning_gate_zero_cotangent(const MobgsTuning* t) { return (t && t->ga
 inline int tuning_static_rows(const MobgsTuning* t) { return (t && t->static_rows > 0) ? t->static_rows : 0; }
 inline int tuning_cover_slots(const MobgsTuning* t) { return (t && t->cover_slots > 0) ? 1 : 0; }
 inline int tuning_geometry_per_camera(const MobgsTuning* t) { return (t && t->geometry_per_camera == 1) ? 1 : 0; }
-void isect_zeroed_region(void* scratch, size_t n_gauss, size_t n_tiles, size_t capacity, int32_t** ptr, size_t* count);
-// fused single-pass lists (isect.hip): where the projection kernel leaves the bin records inside the binning scratch,
-// and the launcher of scan -> bin (keys into strided segments) -> offsets / schedule -> per-tile sort
-float* isect_bin_records(void* scratch, size_t n_gauss, size_t n_tiles, size_t capacity);
-int isect_fused_launch(int C, int N, int tile_w, int tile_h, int width, int height, int capacity,
-                       const int32_t* tiles_per_gauss, int32_t* cum_tiles, int32_t* keep_scan, int32_t* tile_offsets,
-                       int32_t* tile_order, int64_t capacity_listed, int64_t* stats, void* scratch, int64_t* stats_mirror,
-                       int64_t stats_seq, uint64_t* seg_keys, int seg_stride, int32_t* flatten_ids, uint64_t* isect_ids,
-                       int64_t max_tile_len_hint, const int32_t* enum_order, const MobgsTuning* tuning, void* stream);
 
 // bit q = 2 * qy + qx set <=> the splat may reach alpha >= 1/255 at a pixel centre of the 8x8 quadrant (qx, qy) of
 // the 16x16 tile (tx, ty).  Same conservative test as min_sigma_over_tile / reach_threshold, on the four quadrant

@@ -17,7 +17,7 @@
 // compositor would skip it at all 256 pixels; dropping the pair from the list leaves every pixel bit-identical (gradients: same terms)
 // and removes ~half of the intersections on anisotropic scenes.  The test is conservative (margin on the
 // threshold); with culling off the lists are exactly upstream's.
-#include "common.h"
+#include "isect_launch.h"
 
 namespace mobgs {
 
@@ -204,17 +204,7 @@ __device__ inline int owner_in_wave(const int32_t* __restrict__ cum, int lo, int
     return lo;
 }
 
-// stride of the per-tile list counters (1 = packed; giving each counter its own 128-byte line was measured: no gain
-// for the atomics of a dense image region, +12 us in tile_scan)
-constexpr int TC_STRIDE = 1;
-// The rank counters exist TC_COPIES times ([copy][tile]); workgroup (chunk) c of bin_kernel uses copy c mod TC_COPIES.
-// Device-scope atomics on one address are served one after the other at the memory side of the chip (~120 ns each:
-// the L2s of the eight XCDs are not coherent with each other); every tile counter receives one atomic from almost
-// every chunk that touches the tile -- ~200 per counter at 300 k splats, 150 at 30 k -- and that queue was 42 % /
-// 62 % of bin_kernel (ablated build: 59.1 -> 34.4 us, 29.8 -> 11.3 us).  With the copies a counter's queue is 8 x
-// shorter; tile_scan_kernel sums the copies into the list lengths and leaves every (copy, tile) pair's first
-// position in tile_base, which is what emit_kernel adds the rank to.  Ranks only have to be distinct inside a list.
-constexpr int TC_COPIES = 8;
+// (TC_STRIDE, TC_COPIES: the per-tile rank counters and their copies, isect_launch.h)
 // (Tried in round 5 and dropped: one counter copy per XCD -- the copy chosen by HW_REG_XCC_ID, each in its own cache
 // lines -- with workgroup-scope atomics, hoping to have them performed in the XCD's own L2.  gfx950 emits the same
 // global_atomic_add for either scope and the kernel's time did not move: bin_kernel is bound by the RATE of returning
@@ -938,7 +928,7 @@ __device__ __forceinline__ void sort_tile_in_wave(const uint64_t* __restrict__ s
 // lists of up to 64 * MAXEPL entries sort in registers; three builds of the kernel (MAXEPL = 8 / 16 / 32 keys per lane:
 // 512 / 1024 / 2048 entries) because the register count of the longest network sets the occupancy of all of them
 // (MAXEPL 16: 76 VGPRs, 32: 138 VGPRs = 3 waves per SIMD)
-constexpr int SHORT_SORT_LDS_KEYS = 2048;  // 16 KiB: longer lists belong to the long-list launch (or sort in global memory)
+// (SHORT_SORT_LDS_KEYS = 2048, isect_launch.h: longer lists belong to the long-list launch, or sort in global memory)
 
 // A workgroup sorts one list of any length: bitonic network in LDS when it fits, in place in global memory else.
 template <int THREADS>
@@ -1545,43 +1535,142 @@ __global__ void __launch_bounds__(256) tile_sort_seg_kernel(int n_tiles_total, i
 using namespace mobgs;
 
 // MobgsTuning.heavy_tile_len: list length from which a tile is composited by a whole workgroup (scheduling policy,
-// see tile_scan_kernel); MobgsTuning.longest_list_hint: longest list the caller expects (no longer consulted here).
-// Both travel with the call -- the library keeps no mutable state.
-constexpr int DENSE_MAX_TILES = 8192;  // 32 KiB of LDS
+// see tile_scan_kernel).  It travels with the call -- the library keeps no mutable state.
+
+// bin_kernel<DENSE, FUSED> from a grid, the scratch layout and the bundles; `window`: tiles in the LDS rank table (DENSE),
+// else 0.  The fused variant reads the projection's bin records instead of its arrays (the record's threshold carries
+// the cull decision), searches the enumeration-order scan when the caller gave an order, and writes keys into the
+// strided segments; the two-pass variant has none of those.
+template <bool DENSE, bool FUSED>
+static void launch_bin(const BinGrid& g, const IsectScratch& L, int window, const ProjectIn& in, const ProjectOut& po,
+                       const ListsOut& lo, const FusedLists& fl, hipStream_t st) {
+    const int32_t* none_i = nullptr;
+    const float* none_f = nullptr;
+    hipLaunchKernelGGL((bin_kernel<DENSE, FUSED>), dim3(g.n_chunks), dim3(SCAN_THREADS), sizeof(int32_t) * (size_t)window, st,
+                       g.n, g.N, g.tile_w, g.tile_h, g.width, g.height, FUSED ? 1 : in.cull, g.capacity,
+                       FUSED && fl.enum_order ? L.cum_enum : lo.cum_tiles, FUSED ? none_f : po.means2d,
+                       FUSED ? none_i : po.radii, FUSED ? none_f : po.conics, FUSED ? none_f : in.opacities,
+                       FUSED ? 0 : in.opac_per_camera, L.chunk_cnt, L.owner, L.tile_of_j, L.rank_of_j, L.tile_count,
+                       lo.keep_scan, g.nt, L.chunk_owner, FUSED ? L.bin_records() : none_f, FUSED ? lo.keys : nullptr,
+                       FUSED ? fl.seg_stride : 0, FUSED ? (int)count_stride((size_t)g.nt) : 0, FUSED ? fl.enum_order : none_i,
+                       window);
+}
+
+int mobgs::isect_offsets_launch(const BinGrid& g, const ProjectIn& in, const ProjectOut& po, const ListsOut& lo,
+                                const Speculation& sp, bool scratch_zeroed, const MobgsTuning* tuning, void* stream) {
+    if (int rc = bin_grid_check("mobgs_isect_offsets", g, lo.scratch)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const int heavy_len = tuning_heavy_len(tuning, g.nt);
+    const IsectScratch L(lo.scratch, g);
+    if (!scratch_zeroed || g.n == 0)
+        hipMemsetAsync(L.zeroed().ptr, 0, sizeof(int32_t) * L.zeroed().count, st);  // tile counters, tickets, status words
+    if (g.n == 0) {
+        hipMemsetAsync(lo.cum_tiles, 0, sizeof(int32_t), st);
+        hipMemsetAsync(lo.keep_scan, 0, 2 * sizeof(int32_t), st);  // base and first local of chunk 0
+        hipMemsetAsync(lo.stats_dev, 0, 3 * sizeof(int64_t), st);
+        hipLaunchKernelGGL(tile_scan_kernel, dim3(lo.tile_order ? 3 : 2), dim3(TSCAN_THREADS), 0, st, g.nt, L.tile_count,
+                           L.tile_base, lo.tile_offsets, lo.stats_dev, lo.tile_order, (int64_t)g.capacity, (int64_t)0,
+                           (int32_t*)nullptr, 0, heavy_len, sp.stats_mirror, sp.stats_seq);
+        return check_launch("isect_offsets(empty)");
+    }
+    // bounding-box counts -> cum_tiles; stats[0] = I_box
+    hipLaunchKernelGGL(scan_lookback_kernel, dim3(g.nb1), dim3(SCAN_THREADS), 0, st, g.n, po.tiles_per_gauss, lo.cum_tiles,
+                       L.tickets, L.status1, lo.stats_dev, L.chunk_owner, L.owner_slots, (const int32_t*)nullptr,
+                       (int32_t*)nullptr);
+    // keep flags, per-tile ranks and keep_scan over the first min(I_box, capacity) intersections (the caller
+    // re-runs with a larger buffer when stats[0] > capacity); stats[1] = I_listed
+    const FusedLists two_pass{0, nullptr};
+    if (const int window = bin_window_two_pass(g.nt))
+        launch_bin<true, false>(g, L, window, in, po, lo, two_pass, st);
+    else
+        launch_bin<false, false>(g, L, 0, in, po, lo, two_pass, st);
+    hipLaunchKernelGGL(tile_scan_kernel, dim3(lo.tile_order ? 3 : 2), dim3(TSCAN_THREADS), 0, st, g.nt, L.tile_count,
+                       L.tile_base, lo.tile_offsets, lo.stats_dev, lo.tile_order, (int64_t)g.capacity, lo.capacity_listed,
+                       lo.keep_scan, g.n_chunks, heavy_len, sp.stats_mirror, sp.stats_seq);
+    return check_launch("isect_offsets");
+}
+
+// shared by the synchronous entry point (the caller has read the counts) and the speculative one
+int mobgs::emit_sort(const BinGrid& g, const ListsOut& lo, const float* depths, int64_t n_isects, int64_t max_tile_len,
+                     bool counts_on_device, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (n_isects < 0 || n_isects >= (1ll << 31) - 1 || max_tile_len < 0) {
+        set_error("mobgs_isect_emit_sort: n_isects=%lld out of range", (long long)n_isects);
+        return MOBGS_E_INVALID;
+    }
+    if (n_isects == 0) return MOBGS_OK;
+    if (int rc = bin_grid_check("mobgs_isect_emit_sort", g, lo.scratch)) return rc;
+    const int64_t* stats_dev = counts_on_device ? lo.stats_dev : nullptr;
+    const int64_t capacity_listed = counts_on_device ? lo.capacity_listed : 0;
+    // the compacted (owner, tile, rank) arrays pass A left in the scratch buffer of mobgs_isect_offsets
+    const IsectScratch L(lo.scratch, g);
+    hipLaunchKernelGGL(emit_kernel, dim3(4096), dim3(1024), 0, st, lo.cum_tiles + g.n, L.chunk_cnt, L.owner, L.tile_of_j,
+                       L.rank_of_j, depths, L.tile_base, g.nt, lo.keys, g.capacity, stats_dev, capacity_listed);
+    const SortPlan plan = sort_plan(max_tile_len, counts_on_device ? lo.capacity_listed : n_isects, g.capacity);
+    auto sort_short = plan.epl == 32 ? tile_sort_short_kernel<32>
+                      : plan.epl == 16 ? tile_sort_short_kernel<16> : tile_sort_short_kernel<8>;
+    hipLaunchKernelGGL(sort_short, dim3((g.nt + 3) / 4), dim3(256), 0, st, g.nt, g.tile_bits, lo.tile_offsets, lo.keys,
+                       lo.flatten_ids, lo.isect_ids, g.tiles_per_cam, plan.split ? SHORT_SORT_LDS_KEYS : 0x7fffffff);
+    if (plan.split) {
+        // the per-tile counters of pass A (dead since tile_scan) hold the list of long tiles, a zeroed ticket word its length
+        int32_t* long_ids = L.tile_count;
+        int32_t* long_count = L.tickets + 1;
+        hipLaunchKernelGGL(long_lists_kernel, dim3((g.nt + 255) / 256), dim3(256), 0, st, g.nt, lo.tile_offsets,
+                           SHORT_SORT_LDS_KEYS, long_ids, long_count);
+        static_assert(sizeof(RadixShared) <= 160 * 1024, "radix sort state must fit the LDS of a CU");
+        hipLaunchKernelGGL(tile_sort_kernel<1024>, dim3(g.nt < 256 ? g.nt : 256), dim3(1024), sizeof(RadixShared), st, g.nt,
+                           LONG_SORT_LDS_KEYS, g.tile_bits, lo.tile_offsets, lo.keys, lo.flatten_ids, lo.isect_ids,
+                           g.tiles_per_cam, SHORT_SORT_LDS_KEYS + 1, plan.huge ? LONG_SORT_LDS_KEYS : 0x7fffffff, long_ids,
+                           long_count);
+        if (plan.huge) {
+            int32_t* max_chunks = L.tickets + 2;  // zeroed with the frame's counters
+            uint64_t* tmp = reinterpret_cast<uint64_t*>(L.owner);
+            hipLaunchKernelGGL(huge_chunk_sort_kernel, dim3(256), dim3(1024), sizeof(RadixShared), st, lo.tile_offsets,
+                               lo.keys, long_ids, long_count, max_chunks);
+            for (int p = 0; p < plan.merge_passes; ++p)
+                hipLaunchKernelGGL(huge_merge_kernel, dim3(256), dim3(256), 0, st, p, lo.tile_offsets, lo.keys, tmp,
+                                   long_ids, long_count, max_chunks);
+            hipLaunchKernelGGL(huge_finish_kernel, dim3(256), dim3(256), 0, st, g.tile_bits, g.tiles_per_cam, lo.tile_offsets,
+                               lo.keys, tmp, lo.flatten_ids, lo.isect_ids, long_ids, long_count, max_chunks);
+        }
+    }
+    return check_launch("isect_emit_sort");
+}
+
+// scan -> bin (keys straight into the strided segments) -> offsets / schedule / counts -> per-tile sort: four launches
+// (the two-pass path: five, with a second pass over the kept intersections and six dependent counter sweeps)
+int mobgs::isect_fused_launch(const BinGrid& g, const ProjectOut& po, const ListsOut& lo, const Speculation& sp,
+                              const FusedLists& fl, const MobgsTuning* tuning, void* stream) {
+    if (!bin_grid_fused_ok(g, lo.scratch) || !lo.keys || fl.seg_stride < 1 || fl.seg_stride > SHORT_SORT_LDS_KEYS ||
+        lo.capacity_listed < 1) {
+        set_error("mobgs_project_and_bin_fused: bad sizes C=%d N=%d tiles=%dx%d capacity=%d seg_stride=%d", g.C, g.N, g.tile_w,
+                  g.tile_h, g.capacity, fl.seg_stride);
+        return MOBGS_E_INVALID;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int heavy_len = tuning_heavy_len(tuning, g.nt);
+    const IsectScratch L(lo.scratch, g);
+    const int cstride = (int)count_stride((size_t)g.nt);
+    // enum_order: the scan runs in the caller's splat order; its enumeration-order copy lives in the scratch buffer
+    hipLaunchKernelGGL(scan_lookback_kernel, dim3(g.nb1), dim3(SCAN_THREADS), 0, st, g.n, po.tiles_per_gauss, lo.cum_tiles,
+                       L.tickets, L.status1, lo.stats_dev, L.chunk_owner, L.owner_slots, fl.enum_order, L.cum_enum);
+    const ProjectIn records_only{};  // (the bin records carry what the reach test reads)
+    if (const int window = bin_window_fused(g.nt, g.tiles_per_cam, sp.max_tile_len_hint, fl.enum_order != nullptr,
+                                            tuning_coherent_order(tuning)))
+        launch_bin<true, true>(g, L, window, records_only, po, lo, fl, st);
+    else
+        launch_bin<false, true>(g, L, 0, records_only, po, lo, fl, st);
+    hipLaunchKernelGGL(tile_finish_kernel, dim3(lo.tile_order ? 3 : 2), dim3(TSCAN_THREADS), 0, st, g.nt, L.tile_count,
+                       cstride, lo.tile_offsets, lo.stats_dev, lo.tile_order, (int64_t)g.capacity, lo.capacity_listed,
+                       fl.seg_stride, lo.keep_scan, g.n_chunks, heavy_len, sp.stats_mirror, sp.stats_seq);
+    const int epl = short_sort_epl(sp.max_tile_len_hint > fl.seg_stride ? fl.seg_stride : sp.max_tile_len_hint);
+    auto sort_seg = epl == 32 ? tile_sort_seg_kernel<32> : epl == 16 ? tile_sort_seg_kernel<16> : tile_sort_seg_kernel<8>;
+    hipLaunchKernelGGL(sort_seg, dim3((g.nt + 3) / 4), dim3(256), 0, st, g.nt, g.tile_bits, lo.tile_offsets, L.tile_count,
+                       cstride, lo.keys, fl.seg_stride, lo.flatten_ids, lo.isect_ids, g.tiles_per_cam);
+    return check_launch("isect_fused");
+}
 
 extern "C" {
-
-// Layout of the scratch buffer shared by mobgs_isect_offsets and mobgs_isect_emit_sort (int32 units):
-//   [tile_count TC_COPIES * nt | ticket (+3 pad) | status 2*(nb1+1)]  <- zeroed by one memset
-//   [owner cap | tile cap | rank cap | chunk_cnt (cap >> 11) + 1]
-static inline size_t count_stride(size_t n_tiles) { return (n_tiles * TC_STRIDE + 31) & ~(size_t)31; }
-struct IsectScratch {
-    int32_t *tile_count, *tickets, *chunk_cnt, *owner, *tile_of_j, *rank_of_j, *chunk_owner, *tile_base, *cum_enum;
-    int owner_slots;
-    uint64_t* status1;
-    size_t zeroed_ints, total_ints;
-    int nb1;
-    IsectScratch(void* scratch, size_t n_gauss, size_t n_tiles, size_t capacity) {
-        nb1 = (int)((n_gauss + SCAN_BLOCK - 1) / SCAN_BLOCK);
-        // every counter copy of the fused path starts on its own 128-byte line; the two-pass path packs its copies at the start
-        const size_t nt_pad = count_stride(n_tiles) * TC_COPIES;  // (even: the 64-bit status words stay 8-byte aligned)
-        int32_t* p = (int32_t*)scratch;
-        tile_count = p;
-        tickets = p + nt_pad;
-        status1 = (uint64_t*)(p + nt_pad + 4);
-        zeroed_ints = nt_pad + 4 + 2 * (size_t)(nb1 + 1);
-        owner = p + zeroed_ints;
-        tile_of_j = owner + capacity;
-        rank_of_j = tile_of_j + capacity;
-        chunk_cnt = rank_of_j + capacity;
-        owner_slots = (int)(capacity >> KEEP_CHUNK_LOG2) + 2;
-        chunk_owner = chunk_cnt + (capacity >> KEEP_CHUNK_LOG2) + 1;
-        tile_base = chunk_owner + owner_slots;
-        cum_enum = tile_base + n_tiles * TC_COPIES;  // [n_gauss + 1]: the scan in the caller's enumeration order (fused path)
-        total_ints = zeroed_ints + 3 * capacity + (capacity >> KEEP_CHUNK_LOG2) + 1 + (size_t)owner_slots +
-                     n_tiles * TC_COPIES + n_gauss + 1;
-    }
-};
 
 size_t mobgs_tile_order_len(int n_tiles) { return sched_slots((size_t)n_tiles); }
 
@@ -1592,158 +1681,44 @@ size_t mobgs_isect_scratch_bytes(int n_gauss, int n_tiles, int capacity) {
     return sizeof(int32_t) * (L.total_ints + 32);
 }
 
+size_t mobgs_fused_seg_keys_len(int n_tiles, int seg_stride) {
+    return (size_t)(n_tiles > 0 ? n_tiles : 0) * TC_COPIES * (size_t)(seg_stride > 0 ? seg_stride : 0);
+}
+int mobgs_fused_max_seg_stride(void) { return SHORT_SORT_LDS_KEYS; }
+
+// The standalone stages read what the bundles name as the earlier stages' outputs: the casts below drop a const the
+// launchers never use.
 int mobgs_isect_offsets(int C, int N, int tile_w, int tile_h, int width, int height, int cull, int capacity,
                         const int32_t* tiles_per_gauss, const float* means2d, const int32_t* radii,
                         const float* conics, const float* opacities, int opac_per_camera, int32_t* cum_tiles,
                         int32_t* keep_scan, int32_t* tile_offsets, int32_t* tile_order, int64_t capacity_listed,
                         int64_t* stats, void* scratch, const MobgsTuning* tuning, void* stream) {
-    return mobgs::isect_offsets_launch(C, N, tile_w, tile_h, width, height, cull, capacity, tiles_per_gauss, means2d, radii,
-                                       conics, opacities, opac_per_camera, cum_tiles, keep_scan, tile_offsets, tile_order,
-                                       capacity_listed, stats, scratch, /*scratch_zeroed=*/false, /*stats_mirror=*/nullptr,
-                                       /*stats_seq=*/0, tuning, stream);
+    const ProjectIn in{.opacities = opacities, .opac_per_camera = opac_per_camera, .cull = cull};
+    const ProjectOut po{.radii = const_cast<int32_t*>(radii), .means2d = const_cast<float*>(means2d),
+                        .conics = const_cast<float*>(conics), .tiles_per_gauss = const_cast<int32_t*>(tiles_per_gauss)};
+    const ListsOut lo{.cum_tiles = cum_tiles, .keep_scan = keep_scan, .tile_offsets = tile_offsets, .tile_order = tile_order,
+                      .stats_dev = stats, .scratch = scratch, .capacity_listed = capacity_listed};
+    return mobgs::isect_offsets_launch(bin_grid_tiles(C, N, tile_w, tile_h, width, height, capacity), in, po, lo,
+                                       Speculation{}, /*scratch_zeroed=*/false, tuning, stream);
 }
 
-}  // extern "C"
-
-void mobgs::isect_zeroed_region(void* scratch, size_t n_gauss, size_t n_tiles, size_t capacity, int32_t** ptr,
-                                size_t* count) {
-    const IsectScratch L(scratch, n_gauss, n_tiles, capacity);
-    *ptr = L.tile_count;
-    *count = L.zeroed_ints;
-}
-
-int mobgs::isect_offsets_launch(int C, int N, int tile_w, int tile_h, int width, int height, int cull, int capacity,
-                                const int32_t* tiles_per_gauss, const float* means2d, const int32_t* radii,
-                                const float* conics, const float* opacities, int opac_per_camera, int32_t* cum_tiles,
-                                int32_t* keep_scan, int32_t* tile_offsets, int32_t* tile_order, int64_t capacity_listed,
-                                int64_t* stats, void* scratch, bool scratch_zeroed, int64_t* stats_mirror,
-                                int64_t stats_seq, const MobgsTuning* tuning, void* stream) {
-    const long long ng = (long long)C * N;
-    const long long nt = (long long)C * tile_w * tile_h;
-    const int heavy_len = tuning_heavy_len(tuning, (int)(nt < (1ll << 30) ? nt : (1ll << 30)));
-    const int dense_hint = tuning_list_hint(tuning);
-    if (C <= 0 || N < 0 || capacity < 1 || ng >= (1ll << 31) - 1 || nt >= (1ll << 31) - 1) {
-        set_error("mobgs_isect_offsets: bad sizes C=%d N=%d tiles=%dx%d capacity=%d", C, N, tile_w, tile_h, capacity);
-        return MOBGS_E_INVALID;
-    }
-    if (((uintptr_t)scratch & 7) != 0) {
-        set_error("mobgs_isect_offsets: scratch must be 8-byte aligned");
-        return MOBGS_E_INVALID;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const int n = (int)ng;
-    const IsectScratch L(scratch, (size_t)n, (size_t)nt, (size_t)capacity);
-    if (!scratch_zeroed || n == 0)
-        hipMemsetAsync(L.tile_count, 0, sizeof(int32_t) * L.zeroed_ints, st);  // tile counters, tickets, status words
-    if (n == 0) {
-        hipMemsetAsync(cum_tiles, 0, sizeof(int32_t), st);
-        hipMemsetAsync(keep_scan, 0, 2 * sizeof(int32_t), st);  // base and first local of chunk 0
-        hipMemsetAsync(stats, 0, 3 * sizeof(int64_t), st);
-        hipLaunchKernelGGL(tile_scan_kernel, dim3(tile_order ? 3 : 2), dim3(TSCAN_THREADS), 0, st, (int)nt, L.tile_count, L.tile_base, tile_offsets,
-                           stats, tile_order, (int64_t)capacity, (int64_t)0, (int32_t*)nullptr, 0, heavy_len,
-                           stats_mirror, stats_seq);
-        return check_launch("isect_offsets(empty)");
-    }
-    // bounding-box counts -> cum_tiles; stats[0] = I_box
-    hipLaunchKernelGGL(scan_lookback_kernel, dim3(L.nb1), dim3(SCAN_THREADS), 0, st, n, tiles_per_gauss, cum_tiles,
-                       L.tickets, L.status1, stats, L.chunk_owner, L.owner_slots, (const int32_t*)nullptr, (int32_t*)nullptr);
-    // keep flags, per-tile ranks and keep_scan over the first min(I_box, capacity) intersections (the caller
-    // re-runs with a larger buffer when stats[0] > capacity); stats[1] = I_listed
-    const int n_chunks = (capacity >> KEEP_CHUNK_LOG2) + 1;
-    // LDS-ranked variant whenever one int per tile fits in LDS: measured faster at every grid size that qualifies
-    // (scripts/ab/sweep_dense.sh: 576 tiles 47 -> 33 us, 1100 tiles 48 -> 40, 2040 tiles 50 -> 46, 5440 tiles 66.6 ->
-    // 65.3), several times faster on dense image regions (long lists); larger grids keep the direct atomics
-    (void)dense_hint;
-    if (nt <= DENSE_MAX_TILES)
-        hipLaunchKernelGGL((bin_kernel<true, false>), dim3(n_chunks), dim3(SCAN_THREADS), sizeof(int32_t) * (size_t)nt, st, n, N,
-                           tile_w, tile_h, width, height, cull, capacity, cum_tiles, means2d, radii, conics, opacities,
-                           opac_per_camera, L.chunk_cnt, L.owner, L.tile_of_j, L.rank_of_j, L.tile_count, keep_scan,
-                           (int)nt, L.chunk_owner, (const float*)nullptr, (uint64_t*)nullptr, 0, 0, (const int32_t*)nullptr, (int)nt);
-    else
-        hipLaunchKernelGGL((bin_kernel<false, false>), dim3(n_chunks), dim3(SCAN_THREADS), 0, st, n, N, tile_w, tile_h, width,
-                           height, cull, capacity, cum_tiles, means2d, radii, conics, opacities, opac_per_camera,
-                           L.chunk_cnt, L.owner, L.tile_of_j, L.rank_of_j, L.tile_count, keep_scan, (int)nt,
-                           L.chunk_owner, (const float*)nullptr, (uint64_t*)nullptr, 0, 0, (const int32_t*)nullptr, 0);
-    hipLaunchKernelGGL(tile_scan_kernel, dim3(tile_order ? 3 : 2), dim3(TSCAN_THREADS), 0, st, (int)nt, L.tile_count, L.tile_base, tile_offsets,
-                       stats, tile_order, (int64_t)capacity, capacity_listed, keep_scan, n_chunks, heavy_len,
-                       stats_mirror, stats_seq);
-    return check_launch("isect_offsets");
-}
-
-extern "C" {
-
-// shared by the synchronous entry point (stats_dev = NULL: the caller has read the counts) and the speculative one
-static int emit_sort(int C, int N, int tile_w, int tile_h, int capacity, int64_t n_isects, int64_t max_tile_len,
-                     const float* depths, const int32_t* cum_tiles, const int32_t* tile_offsets,
-                     const void* offsets_scratch, uint64_t* sort_keys, int32_t* flatten_ids, uint64_t* isect_ids,
-                     const int64_t* stats_dev, int64_t capacity_listed, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    const int tiles_per_cam = tile_w * tile_h;
-    const int nt = C * tiles_per_cam;
-    if (n_isects < 0 || n_isects >= (1ll << 31) - 1 || max_tile_len < 0) {
-        set_error("mobgs_isect_emit_sort: n_isects=%lld out of range", (long long)n_isects);
-        return MOBGS_E_INVALID;
-    }
-    if (n_isects == 0) return MOBGS_OK;
-    const int n = C * N;
-    // the compacted (owner, tile, rank) arrays pass A left in the scratch buffer of mobgs_isect_offsets
-    const IsectScratch L(const_cast<void*>(offsets_scratch), (size_t)n, (size_t)nt, (size_t)capacity);
-    hipLaunchKernelGGL(emit_kernel, dim3(4096), dim3(1024), 0, st, cum_tiles + n, L.chunk_cnt, L.owner, L.tile_of_j,
-                       L.rank_of_j, depths, L.tile_base, nt, sort_keys, capacity, stats_dev, capacity_listed);
-    // gsplat: tile_n_bits = floor(log2(n_tiles)) + 1
-    int tile_bits = 0;
-    while ((1ll << tile_bits) <= (long long)tiles_per_cam) ++tile_bits;
-    // lists <= 2048 (all of them unless longer ones are expected): ONE launch, four tiles per workgroup, a wave per
-    // list of <= 512 entries (registers), the workgroup for the few longer ones (16 KiB LDS).  Longer lists, when the
-    // previous frame had any: 1024 threads, 128 KiB of the 160 KiB LDS (<= 16384 keys; beyond that in place in global
-    // memory), in a separate launch over a compacted list of those tiles, so that the short lists keep their
-    // occupancy.  The per-tile counters of pass A (dead since tile_scan) hold that list, a zeroed ticket word its length.
-    const int small_cap = SHORT_SORT_LDS_KEYS, big_cap = 16384;
-    const bool split = max_tile_len > small_cap;
-    const int nmax_small = split ? small_cap : 0x7fffffff;
-    // (max_tile_len: the previous frame's longest list, or this frame's in the synchronous form)
-    auto sort_short = max_tile_len > 1024 ? tile_sort_short_kernel<32>
-                      : max_tile_len > 512 ? tile_sort_short_kernel<16> : tile_sort_short_kernel<8>;
-    hipLaunchKernelGGL(sort_short, dim3((nt + 3) / 4), dim3(256), 0, st, nt, tile_bits, tile_offsets, sort_keys,
-                       flatten_ids, isect_ids, tiles_per_cam, nmax_small);
-    if (split) {
-        int32_t* long_ids = L.tile_count;
-        int32_t* long_count = L.tickets + 1;
-        hipLaunchKernelGGL(long_lists_kernel, dim3((nt + 255) / 256), dim3(256), 0, st, nt, tile_offsets, small_cap,
-                           long_ids, long_count);
-        static_assert(sizeof(RadixShared) <= 160 * 1024, "radix sort state must fit the LDS of a CU");
-        // Lists beyond the LDS radix sort (> 16384 entries): chunks + merge passes (see huge_chunk_sort_kernel) when the
-        // previous frame's longest list says they are near -- and the dead (owner, tile, rank) triples of pass A, 12
-        // bytes per bounding-box intersection, can hold a second copy of the keys; otherwise such a list takes the old
-        // one-workgroup network in global memory (correct, slow; the next frame's hint then selects this path).
-        const int64_t listed_cap = stats_dev ? capacity_listed : n_isects;
-        const bool huge = max_tile_len > (3 * (int64_t)big_cap) / 4 && 8 * listed_cap <= 12 * (int64_t)capacity;
-        hipLaunchKernelGGL(tile_sort_kernel<1024>, dim3(nt < 256 ? nt : 256), dim3(1024), sizeof(RadixShared), st,
-                           nt, big_cap, tile_bits, tile_offsets, sort_keys, flatten_ids, isect_ids, tiles_per_cam,
-                           small_cap + 1, huge ? big_cap : 0x7fffffff, long_ids, long_count);
-        if (huge) {
-            int32_t* max_chunks = L.tickets + 2;  // zeroed with the frame's counters
-            uint64_t* tmp = reinterpret_cast<uint64_t*>(L.owner);
-            hipLaunchKernelGGL(huge_chunk_sort_kernel, dim3(256), dim3(1024), sizeof(RadixShared), st, tile_offsets,
-                               sort_keys, long_ids, long_count, max_chunks);
-            int passes = 0;  // enough for one list holding every listed intersection
-            while (((int64_t)big_cap << passes) < listed_cap) ++passes;
-            for (int p = 0; p < passes; ++p)
-                hipLaunchKernelGGL(huge_merge_kernel, dim3(256), dim3(256), 0, st, p, tile_offsets, sort_keys, tmp,
-                                   long_ids, long_count, max_chunks);
-            hipLaunchKernelGGL(huge_finish_kernel, dim3(256), dim3(256), 0, st, tile_bits, tiles_per_cam, tile_offsets,
-                               sort_keys, tmp, flatten_ids, isect_ids, long_ids, long_count, max_chunks);
-        }
-    }
-    return check_launch("isect_emit_sort");
+static ListsOut emit_sort_lists(const int32_t* cum_tiles, const int32_t* tile_offsets, const int64_t* stats_dev,
+                                const void* offsets_scratch, int64_t capacity_listed, uint64_t* sort_keys,
+                                int32_t* flatten_ids, uint64_t* isect_ids) {
+    return ListsOut{.cum_tiles = const_cast<int32_t*>(cum_tiles), .tile_offsets = const_cast<int32_t*>(tile_offsets),
+                    .stats_dev = const_cast<int64_t*>(stats_dev), .scratch = const_cast<void*>(offsets_scratch),
+                    .capacity_listed = capacity_listed, .flatten_ids = flatten_ids, .keys = sort_keys,
+                    .isect_ids = isect_ids};
 }
 
 int mobgs_isect_emit_sort(int C, int N, int tile_w, int tile_h, int capacity, int64_t n_isects,
                           int64_t max_tile_len, const float* depths, const int32_t* cum_tiles,
                           const int32_t* tile_offsets, const void* offsets_scratch, uint64_t* sort_keys,
                           int32_t* flatten_ids, uint64_t* isect_ids, void* stream) {
-    return emit_sort(C, N, tile_w, tile_h, capacity, n_isects, max_tile_len, depths, cum_tiles, tile_offsets,
-                     offsets_scratch, sort_keys, flatten_ids, isect_ids, nullptr, 0, stream);
+    return mobgs::emit_sort(bin_grid_tiles(C, N, tile_w, tile_h, 0, 0, capacity),
+                            emit_sort_lists(cum_tiles, tile_offsets, nullptr, offsets_scratch, 0, sort_keys, flatten_ids,
+                                            isect_ids),
+                            depths, n_isects, max_tile_len, /*counts_on_device=*/false, stream);
 }
 
 int mobgs_isect_emit_sort_speculative(int C, int N, int tile_w, int tile_h, int capacity, int64_t capacity_listed,
@@ -1755,88 +1730,10 @@ int mobgs_isect_emit_sort_speculative(int C, int N, int tile_w, int tile_h, int 
         set_error("mobgs_isect_emit_sort_speculative: stats_dev and capacity_listed are required");
         return MOBGS_E_INVALID;
     }
-    return emit_sort(C, N, tile_w, tile_h, capacity, /*n_isects (unknown, > 0)*/ 1, max_tile_len_hint, depths,
-                     cum_tiles, tile_offsets, offsets_scratch, sort_keys, flatten_ids, isect_ids, stats_dev,
-                     capacity_listed, stream);
+    return mobgs::emit_sort(bin_grid_tiles(C, N, tile_w, tile_h, 0, 0, capacity),
+                            emit_sort_lists(cum_tiles, tile_offsets, stats_dev, offsets_scratch, capacity_listed, sort_keys,
+                                            flatten_ids, isect_ids),
+                            depths, /*n_isects (unknown, > 0)*/ 1, max_tile_len_hint, /*counts_on_device=*/true, stream);
 }
 
 }  // extern "C"
-
-// ---- fused single-pass lists (round 5) --------------------------------------------------------------------------------
-extern "C" {
-
-size_t mobgs_fused_seg_keys_len(int n_tiles, int seg_stride) {
-    return (size_t)(n_tiles > 0 ? n_tiles : 0) * TC_COPIES * (size_t)(seg_stride > 0 ? seg_stride : 0);
-}
-int mobgs_fused_max_seg_stride(void) { return SHORT_SORT_LDS_KEYS; }
-
-}  // extern "C"
-
-float* mobgs::isect_bin_records(void* scratch, size_t n_gauss, size_t n_tiles, size_t capacity) {
-    // the (owner, tile, rank) triples of the two-pass path are not written by the fused one: 3 * capacity ints, and
-    // capacity >= 4 * n_gauss + 2 is checked by the launcher (12 floats per splat + the alignment slack)
-    const IsectScratch L(scratch, n_gauss, n_tiles, capacity);
-    return reinterpret_cast<float*>(((uintptr_t)L.owner + 15) & ~(uintptr_t)15);  // rows are read as float4
-}
-
-// scan -> bin (keys straight into the strided segments) -> offsets / schedule / counts -> per-tile sort: four launches
-// (the two-pass path: five, with a second pass over the kept intersections and six dependent counter sweeps)
-int mobgs::isect_fused_launch(int C, int N, int tile_w, int tile_h, int width, int height, int capacity,
-                              const int32_t* tiles_per_gauss, int32_t* cum_tiles, int32_t* keep_scan,
-                              int32_t* tile_offsets, int32_t* tile_order, int64_t capacity_listed, int64_t* stats,
-                              void* scratch, int64_t* stats_mirror, int64_t stats_seq, uint64_t* seg_keys,
-                              int seg_stride, int32_t* flatten_ids, uint64_t* isect_ids, int64_t max_tile_len_hint,
-                              const int32_t* enum_order, const MobgsTuning* tuning, void* stream) {
-    const long long ng = (long long)C * N;
-    const long long nt = (long long)C * tile_w * tile_h;
-    if (C <= 0 || N <= 0 || capacity < 1 || ng >= (1ll << 31) - 1 || nt >= (1ll << 31) - 1 || !seg_keys ||
-        seg_stride < 1 || seg_stride > SHORT_SORT_LDS_KEYS || (long long)capacity < 4 * ng + 2 || capacity_listed < 1 ||
-        tile_w > 0xFFFF || tile_h > 0xFFFF || C > 0xFFFF || ((uintptr_t)scratch & 127) != 0) {
-        set_error("mobgs_project_and_bin_fused: bad sizes C=%d N=%d tiles=%dx%d capacity=%d seg_stride=%d", C, N, tile_w,
-                  tile_h, capacity, seg_stride);
-        return MOBGS_E_INVALID;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const int n = (int)ng;
-    const int heavy_len = tuning_heavy_len(tuning, (int)(nt < (1ll << 30) ? nt : (1ll << 30)));
-    const IsectScratch L(scratch, (size_t)n, (size_t)nt, (size_t)capacity);
-    const float* binrec = isect_bin_records(scratch, (size_t)n, (size_t)nt, (size_t)capacity);
-    const int cstride = (int)count_stride((size_t)nt);
-    // enum_order: the scan runs in the caller's splat order; its enumeration-order copy lives in the scratch buffer
-    const int32_t* cum_search = enum_order ? L.cum_enum : cum_tiles;
-    hipLaunchKernelGGL(scan_lookback_kernel, dim3(L.nb1), dim3(SCAN_THREADS), 0, st, n, tiles_per_gauss, cum_tiles,
-                       L.tickets, L.status1, stats, L.chunk_owner, L.owner_slots, enum_order, L.cum_enum);
-    const int n_chunks = (capacity >> KEEP_CHUNK_LOG2) + 1;
-    // LDS-ranked variant: small grids (every workgroup touches most tiles several times) and scenes with long lists
-    // (dense image regions: thousands of atomics on a few counters); on a large grid with short lists the plain
-    // returning atomics are ahead (47.4 against 50.2 us at 5440 tiles / 300 k splats)
-    // ... and with a (spatially coherent) enumeration order, whose whole point is that a workgroup's intersections
-    // concentrate on few tiles
-    // ... or with splats STORED in such an order (MobgsTuning.coherent_order: the caller's statement)
-    // ... for a batch of cameras the table covers ONE camera's tiles (bin_kernel, dense_window)
-    const long long dense_window = nt < (long long)tile_w * tile_h ? nt : (long long)tile_w * tile_h;
-    if (dense_window <= DENSE_MAX_TILES &&
-        (nt <= 2048 || max_tile_len_hint >= 1024 || enum_order || tuning_coherent_order(tuning)))
-        hipLaunchKernelGGL((bin_kernel<true, true>), dim3(n_chunks), dim3(SCAN_THREADS), sizeof(int32_t) * (size_t)dense_window, st, n,
-                           N, tile_w, tile_h, width, height, 1, capacity, cum_search, (const float*)nullptr,
-                           (const int32_t*)nullptr, (const float*)nullptr, (const float*)nullptr, 0, L.chunk_cnt, L.owner,
-                           L.tile_of_j, L.rank_of_j, L.tile_count, keep_scan, (int)nt, L.chunk_owner, binrec, seg_keys,
-                           seg_stride, cstride, enum_order, (int)dense_window);
-    else
-        hipLaunchKernelGGL((bin_kernel<false, true>), dim3(n_chunks), dim3(SCAN_THREADS), 0, st, n, N, tile_w, tile_h,
-                           width, height, 1, capacity, cum_search, (const float*)nullptr, (const int32_t*)nullptr,
-                           (const float*)nullptr, (const float*)nullptr, 0, L.chunk_cnt, L.owner, L.tile_of_j,
-                           L.rank_of_j, L.tile_count, keep_scan, (int)nt, L.chunk_owner, binrec, seg_keys, seg_stride,
-                           cstride, enum_order, 0);
-    hipLaunchKernelGGL(tile_finish_kernel, dim3(tile_order ? 3 : 2), dim3(TSCAN_THREADS), 0, st, (int)nt, L.tile_count,
-                       cstride, tile_offsets, stats, tile_order, (int64_t)capacity, capacity_listed, seg_stride, keep_scan,
-                       n_chunks, heavy_len, stats_mirror, stats_seq);
-    const int tiles_per_cam = tile_w * tile_h;
-    int tile_bits = 0;
-    while ((1ll << tile_bits) <= (long long)tiles_per_cam) ++tile_bits;
-    const int64_t longest = max_tile_len_hint > seg_stride ? seg_stride : max_tile_len_hint;
-    auto sort_seg = longest > 1024 ? tile_sort_seg_kernel<32> : longest > 512 ? tile_sort_seg_kernel<16> : tile_sort_seg_kernel<8>;
-    hipLaunchKernelGGL(sort_seg, dim3(((int)nt + 3) / 4), dim3(256), 0, st, (int)nt, tile_bits, tile_offsets, L.tile_count,
-                       cstride, seg_keys, seg_stride, flatten_ids, isect_ids, tiles_per_cam);
-    return check_launch("isect_fused");
-}

@@ -7,9 +7,77 @@
 // Buffers whose size depends on the intersection count live in a caller-owned arena sized from the previous call;
 // when it is too small the function returns MOBGS_E_CAPACITY with the required sizes in `stats_host` and has
 // written nothing past the arena.
-#include "common.h"
+#include "isect_launch.h"
 
 using namespace mobgs;
+
+static const PackArgs NO_PACK{nullptr, nullptr, nullptr, 0, 0, 0, 0};
+static const BinArgs NO_BIN_RECORDS{nullptr, nullptr, 0, 0};
+
+// fl.seg_stride > 0: the fused single-pass lists (isect.hip, isect_fused_launch) -- lo.keys is then the strided key
+// arena [C * n_tiles][8][seg_stride]; 0: the two-pass path.  pack.records == NULL: no packed records.
+static int project_and_bin_enqueue(const BinGrid& g, const ProjectIn& in, const ProjectOut& po, const ListsOut& lo,
+                                   const FusedLists& fl, int64_t max_tile_len_hint, int64_t* stats_host_pinned,
+                                   int64_t stats_seq, PackArgs pack, const MobgsTuning* tuning, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!stats_host_pinned || lo.capacity_listed < 1) {
+        set_error("mobgs_project_and_bin_speculative: stats_host_pinned and capacity_listed are required");
+        return MOBGS_E_INVALID;
+    }
+    // two launches fewer on the critical path: project_fwd clears the binning counters on the way, and tile_scan
+    // writes the host's copy of the counts itself when the pinned slot is mapped into the device address space
+    const bool fuse_zero = bin_grid_ok(g, lo.scratch) && g.N > 0;
+    const IntSpan zero = fuse_zero ? IsectScratch(lo.scratch, g).zeroed() : IntSpan{nullptr, 0};
+    if (pack.records) {
+        if ((!pack.colors && !in.prep) || !in.opacities || pack.channels < 0) {
+            set_error("mobgs_project_and_bin_speculative: pack_records needs pack_colors and opacities");
+            return MOBGS_E_INVALID;
+        }
+        pack.opacities = in.opacities;
+        pack.opac_per_camera = in.opac_per_camera;
+        pack.stride = mobgs_record_stride(pack.channels + 1);
+    } else {
+        pack = NO_PACK;
+    }
+    BinArgs bin = NO_BIN_RECORDS;
+    if (fl.seg_stride > 0) {
+        if (!bin_grid_fused_ok(g, lo.scratch) || !in.opacities) {
+            set_error("mobgs_project_and_bin_fused: needs N > 0, opacities, a 128-byte aligned scratch and capacity_box >= 4 C N + 2");
+            return MOBGS_E_INVALID;
+        }
+        bin = BinArgs{IsectScratch(lo.scratch, g).bin_records(), in.opacities, in.opac_per_camera, in.cull};
+    }
+    int rc = project_fwd_launch(g, in, po, zero, pack, bin, tuning_geometry_per_camera(tuning), stream);
+    if (rc != MOBGS_OK) return rc;
+    Speculation sp{.max_tile_len_hint = max_tile_len_hint};
+    void* mirror = nullptr;
+    if (hipHostGetDevicePointer(&mirror, stats_host_pinned, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        mirror = nullptr;
+    }
+    sp.stats_mirror = (int64_t*)mirror;
+    sp.stats_seq = mirror ? stats_seq : 0;
+    // the binning variant follows the caller's expectation of the longest list (max_tile_len_hint)
+    if (fl.seg_stride > 0)
+        rc = isect_fused_launch(g, po, lo, sp, fl, tuning, stream);
+    else
+        rc = isect_offsets_launch(g, in, po, lo, sp, fuse_zero, tuning, stream);
+    if (rc != MOBGS_OK) return rc;
+    if (!sp.stats_mirror) {
+        hipError_t e = hipMemcpyAsync(stats_host_pinned, lo.stats_dev, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, st);
+        if (e != hipSuccess) {
+            set_error("mobgs_project_and_bin_speculative: statistics copy failed: %s", hipGetErrorString(e));
+            return MOBGS_E_LAUNCH;
+        }
+    }
+    if (fl.seg_stride == 0) {
+        rc = emit_sort(g, lo, po.depths, /*n_isects (unknown, > 0)*/ 1, max_tile_len_hint, /*counts_on_device=*/true, stream);
+        if (rc != MOBGS_OK) return rc;
+    }
+    // 1: the counts travel by an ordinary asynchronous copy (or no sequence number was asked for) -- the caller
+    // records an event behind this call and waits on it; 0: poll stats_host_pinned[3] for stats_seq instead
+    return (sp.stats_mirror && stats_seq) ? MOBGS_OK : 1;
+}
 
 extern "C" {
 
@@ -23,15 +91,20 @@ int mobgs_project_and_bin(int C, int N, const float* means, const float* quats, 
                           int32_t* flatten_ids, uint64_t* sort_keys, uint64_t* isect_ids, int64_t* stats_host,
                           const MobgsTuning* tuning, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    const int tile_w = (width + MOBGS_TILE - 1) / MOBGS_TILE, tile_h = (height + MOBGS_TILE - 1) / MOBGS_TILE;
-    int rc = mobgs::project_fwd_launch(C, N, means, quats, scales, viewmats, Ks, width, height, eps2d, near_plane, far_plane,
-                               radius_clip, radii, means2d, depths, conics, tiles_per_gauss, nullptr, 0, PackArgs{nullptr, nullptr, nullptr, 0, 0, 0, 0}, stream,
-                                       tuning_geometry_per_camera(tuning));
+    const BinGrid g = bin_grid(C, N, width, height, capacity_box);
+    const ProjectIn in{.means = means, .quats = quats, .scales = scales, .viewmats = viewmats, .Ks = Ks,
+                       .opacities = opacities, .opac_per_camera = opac_per_camera, .eps2d = eps2d,
+                       .near_plane = near_plane, .far_plane = far_plane, .radius_clip = radius_clip, .cull = cull};
+    const ProjectOut po{.radii = radii, .means2d = means2d, .depths = depths, .conics = conics,
+                        .tiles_per_gauss = tiles_per_gauss};
+    // (capacity_listed is checked on the host below, not on the device)
+    const ListsOut lo{.cum_tiles = cum_tiles, .keep_scan = keep_scan, .tile_offsets = tile_offsets, .tile_order = tile_order,
+                      .stats_dev = stats_dev, .scratch = scratch, .capacity_listed = 0, .flatten_ids = flatten_ids,
+                      .keys = sort_keys, .isect_ids = isect_ids};
+    int rc = project_fwd_launch(g, in, po, IntSpan{nullptr, 0}, NO_PACK, NO_BIN_RECORDS, tuning_geometry_per_camera(tuning),
+                                stream);
     if (rc != MOBGS_OK) return rc;
-    rc = mobgs_isect_offsets(C, N, tile_w, tile_h, width, height, cull, capacity_box, tiles_per_gauss, means2d, radii,
-                             conics, opacities, opac_per_camera, cum_tiles, keep_scan, tile_offsets, tile_order, /*capacity_listed (checked on the host)*/ 0,
-                             stats_dev, scratch, tuning,
-                             stream);
+    rc = isect_offsets_launch(g, in, po, lo, Speculation{}, /*scratch_zeroed=*/false, tuning, stream);
     if (rc != MOBGS_OK) return rc;
     // the pipeline's one host synchronisation (upstream gsplat has the same one): {I_box, I_listed, longest list}
     // (busy-polling hipStreamQuery instead of a blocking hipStreamSynchronize: the wait is ~0.2 ms at most and a
@@ -50,96 +123,7 @@ int mobgs_project_and_bin(int C, int N, const float* means, const float* quats, 
                   (long long)stats_host[0], capacity_box, (long long)stats_host[1], (long long)capacity_listed);
         return MOBGS_E_CAPACITY;
     }
-    return mobgs_isect_emit_sort(C, N, tile_w, tile_h, capacity_box, stats_host[1], stats_host[2], depths, cum_tiles,
-                                 tile_offsets, scratch, sort_keys, flatten_ids, isect_ids, stream);
-}
-
-// seg_stride > 0: the fused single-pass lists (isect.hip, isect_fused_launch) -- sort_keys is then the strided key
-// arena [C * n_tiles][8][seg_stride]; 0: the two-pass path
-static int project_and_bin_enqueue(int C, int N, const float* means, const float* quats, const float* scales,
-                                   const float* viewmats, const float* Ks, const float* opacities,
-                                   int opac_per_camera, int width, int height, float eps2d, float near_plane,
-                                   float far_plane, float radius_clip, int cull, int32_t* radii, float* means2d,
-                                   float* depths, float* conics, int32_t* tiles_per_gauss, int32_t* cum_tiles,
-                                   int32_t* tile_offsets, int32_t* tile_order, int64_t* stats_dev,
-                                   int capacity_box, int32_t* keep_scan, void* scratch, int64_t capacity_listed,
-                                   int32_t* flatten_ids, uint64_t* sort_keys, int seg_stride,
-                                   const int32_t* enum_order, uint64_t* isect_ids,
-                                   int64_t max_tile_len_hint, int64_t* stats_host_pinned, int64_t stats_seq,
-                                   const float* pack_colors, int colors_per_camera, int pack_channels,
-                                   float* pack_records, const MobgsTuning* tuning, void* stream,
-                                   const MobgsPrepInputs* prep = nullptr) {
-    hipStream_t st = (hipStream_t)stream;
-    const int tile_w = (width + MOBGS_TILE - 1) / MOBGS_TILE, tile_h = (height + MOBGS_TILE - 1) / MOBGS_TILE;
-    if (!stats_host_pinned || capacity_listed < 1) {
-        set_error("mobgs_project_and_bin_speculative: stats_host_pinned and capacity_listed are required");
-        return MOBGS_E_INVALID;
-    }
-    // two launches fewer on the critical path: project_fwd clears the binning counters on the way, and tile_scan
-    // writes the host's copy of the counts itself when the pinned slot is mapped into the device address space
-    int32_t* zero_ptr = nullptr;
-    size_t zero_n = 0;
-    const long long n_all = (long long)C * N, nt_all = (long long)C * tile_w * tile_h;
-    const bool fuse_zero = N > 0 && capacity_box >= 1 && n_all < (1ll << 31) - 1 && nt_all < (1ll << 31) - 1 &&
-                           ((uintptr_t)scratch & 7) == 0;
-    if (fuse_zero) mobgs::isect_zeroed_region(scratch, (size_t)n_all, (size_t)nt_all, (size_t)capacity_box, &zero_ptr, &zero_n);
-    PackArgs pack{nullptr, nullptr, nullptr, 0, 0, 0, 0};
-    if (pack_records) {
-        if ((!pack_colors && !prep) || !opacities || pack_channels < 0) {
-            set_error("mobgs_project_and_bin_speculative: pack_records needs pack_colors and opacities");
-            return MOBGS_E_INVALID;
-        }
-        pack = PackArgs{opacities, pack_colors, pack_records, opac_per_camera, colors_per_camera, pack_channels,
-                        mobgs_record_stride(pack_channels + 1)};
-    }
-    BinArgs bin{nullptr, nullptr, 0, 0};
-    if (seg_stride > 0) {
-        if (!fuse_zero || !opacities || (long long)capacity_box < 4 * n_all + 2 || ((uintptr_t)scratch & 127) != 0) {
-            set_error("mobgs_project_and_bin_fused: needs N > 0, opacities, a 128-byte aligned scratch and capacity_box >= 4 C N + 2");
-            return MOBGS_E_INVALID;
-        }
-        bin = BinArgs{mobgs::isect_bin_records(scratch, (size_t)n_all, (size_t)nt_all, (size_t)capacity_box), opacities,
-                      opac_per_camera, cull};
-    }
-    int rc = mobgs::project_fwd_launch(C, N, means, quats, scales, viewmats, Ks, width, height, eps2d, near_plane, far_plane,
-                                       radius_clip, radii, means2d, depths, conics, tiles_per_gauss, zero_ptr, zero_n, pack,
-                                       stream, tuning_geometry_per_camera(tuning), bin, prep);
-    if (rc != MOBGS_OK) return rc;
-    // the binning variant follows the caller's expectation of the longest list (max_tile_len_hint)
-    MobgsTuning tn = tuning ? *tuning : MobgsTuning{-1, -1, -1, -1, -1, 0, -1, 0, 0};
-    tn.longest_list_hint = (int32_t)(max_tile_len_hint > 0x7fffffff ? 0x7fffffff : max_tile_len_hint);
-    void* mirror = nullptr;
-    if (hipHostGetDevicePointer(&mirror, stats_host_pinned, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        mirror = nullptr;
-    }
-    if (seg_stride > 0)
-        rc = mobgs::isect_fused_launch(C, N, tile_w, tile_h, width, height, capacity_box, tiles_per_gauss, cum_tiles,
-                                       keep_scan, tile_offsets, tile_order, capacity_listed, stats_dev, scratch,
-                                       (int64_t*)mirror, mirror ? stats_seq : 0, sort_keys, seg_stride, flatten_ids,
-                                       isect_ids, max_tile_len_hint, enum_order, &tn, stream);
-    else
-        rc = mobgs::isect_offsets_launch(C, N, tile_w, tile_h, width, height, cull, capacity_box, tiles_per_gauss, means2d,
-                                         radii, conics, opacities, opac_per_camera, cum_tiles, keep_scan, tile_offsets,
-                                         tile_order, capacity_listed, stats_dev, scratch, fuse_zero, (int64_t*)mirror,
-                                         mirror ? stats_seq : 0, &tn, stream);
-    if (rc != MOBGS_OK) return rc;
-    if (!mirror) {
-        hipError_t e = hipMemcpyAsync(stats_host_pinned, stats_dev, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, st);
-        if (e != hipSuccess) {
-            set_error("mobgs_project_and_bin_speculative: statistics copy failed: %s", hipGetErrorString(e));
-            return MOBGS_E_LAUNCH;
-        }
-    }
-    if (seg_stride == 0) {
-        rc = mobgs_isect_emit_sort_speculative(C, N, tile_w, tile_h, capacity_box, capacity_listed, max_tile_len_hint,
-                                               depths, cum_tiles, tile_offsets, stats_dev, scratch, sort_keys,
-                                               flatten_ids, isect_ids, stream);
-        if (rc != MOBGS_OK) return rc;
-    }
-    // 1: the counts travel by an ordinary asynchronous copy (or no sequence number was asked for) -- the caller
-    // records an event behind this call and waits on it; 0: poll stats_host_pinned[3] for stats_seq instead
-    return (mirror && stats_seq) ? MOBGS_OK : 1;
+    return emit_sort(g, lo, depths, stats_host[1], stats_host[2], /*counts_on_device=*/false, stream);
 }
 
 int mobgs_project_and_bin_speculative(int C, int N, const float* means, const float* quats, const float* scales,
@@ -153,12 +137,18 @@ int mobgs_project_and_bin_speculative(int C, int N, const float* means, const fl
                                       int64_t max_tile_len_hint, int64_t* stats_host_pinned, int64_t stats_seq,
                                       const float* pack_colors, int colors_per_camera, int pack_channels,
                                       float* pack_records, const MobgsTuning* tuning, void* stream) {
-    return project_and_bin_enqueue(C, N, means, quats, scales, viewmats, Ks, opacities, opac_per_camera, width, height,
-                                   eps2d, near_plane, far_plane, radius_clip, cull, radii, means2d, depths, conics,
-                                   tiles_per_gauss, cum_tiles, tile_offsets, tile_order, stats_dev, capacity_box,
-                                   keep_scan, scratch, capacity_listed, flatten_ids, sort_keys, 0, nullptr, isect_ids,
-                                   max_tile_len_hint, stats_host_pinned, stats_seq, pack_colors, colors_per_camera,
-                                   pack_channels, pack_records, tuning, stream);
+    const ProjectIn in{.means = means, .quats = quats, .scales = scales, .viewmats = viewmats, .Ks = Ks,
+                       .opacities = opacities, .opac_per_camera = opac_per_camera, .eps2d = eps2d,
+                       .near_plane = near_plane, .far_plane = far_plane, .radius_clip = radius_clip, .cull = cull};
+    const ProjectOut po{.radii = radii, .means2d = means2d, .depths = depths, .conics = conics,
+                        .tiles_per_gauss = tiles_per_gauss};
+    const ListsOut lo{.cum_tiles = cum_tiles, .keep_scan = keep_scan, .tile_offsets = tile_offsets, .tile_order = tile_order,
+                      .stats_dev = stats_dev, .scratch = scratch, .capacity_listed = capacity_listed,
+                      .flatten_ids = flatten_ids, .keys = sort_keys, .isect_ids = isect_ids};
+    const PackArgs pack{.colors = pack_colors, .records = pack_records, .colors_per_camera = colors_per_camera,
+                        .channels = pack_channels};
+    return project_and_bin_enqueue(bin_grid(C, N, width, height, capacity_box), in, po, lo, FusedLists{0, nullptr},
+                                   max_tile_len_hint, stats_host_pinned, stats_seq, pack, tuning, stream);
 }
 
 int mobgs_project_and_bin_fused(int C, int N, const float* means, const float* quats, const float* scales,
@@ -176,12 +166,18 @@ int mobgs_project_and_bin_fused(int C, int N, const float* means, const float* q
         set_error("mobgs_project_and_bin_fused: seg_stride >= 1 and seg_keys are required");
         return MOBGS_E_INVALID;
     }
-    return project_and_bin_enqueue(C, N, means, quats, scales, viewmats, Ks, opacities, opac_per_camera, width, height,
-                                   eps2d, near_plane, far_plane, radius_clip, cull, radii, means2d, depths, conics,
-                                   tiles_per_gauss, cum_tiles, tile_offsets, tile_order, stats_dev, capacity_box,
-                                   keep_scan, scratch, capacity_listed, flatten_ids, seg_keys, seg_stride, enum_order,
-                                   isect_ids, max_tile_len_hint, stats_host_pinned, stats_seq, pack_colors, colors_per_camera,
-                                   pack_channels, pack_records, tuning, stream);
+    const ProjectIn in{.means = means, .quats = quats, .scales = scales, .viewmats = viewmats, .Ks = Ks,
+                       .opacities = opacities, .opac_per_camera = opac_per_camera, .eps2d = eps2d,
+                       .near_plane = near_plane, .far_plane = far_plane, .radius_clip = radius_clip, .cull = cull};
+    const ProjectOut po{.radii = radii, .means2d = means2d, .depths = depths, .conics = conics,
+                        .tiles_per_gauss = tiles_per_gauss};
+    const ListsOut lo{.cum_tiles = cum_tiles, .keep_scan = keep_scan, .tile_offsets = tile_offsets, .tile_order = tile_order,
+                      .stats_dev = stats_dev, .scratch = scratch, .capacity_listed = capacity_listed,
+                      .flatten_ids = flatten_ids, .keys = seg_keys, .isect_ids = isect_ids};
+    const PackArgs pack{.colors = pack_colors, .records = pack_records, .colors_per_camera = colors_per_camera,
+                        .channels = pack_channels};
+    return project_and_bin_enqueue(bin_grid(C, N, width, height, capacity_box), in, po, lo, FusedLists{seg_stride, enum_order},
+                                   max_tile_len_hint, stats_host_pinned, stats_seq, pack, tuning, stream);
 }
 
 int mobgs_prep_project_and_bin_fused(const MobgsPrepInputs* prep, float* means, float* quats, float* scales,
@@ -202,13 +198,20 @@ int mobgs_prep_project_and_bin_fused(const MobgsPrepInputs* prep, float* means, 
         set_error("mobgs_prep_project_and_bin_fused: bad sizes Ns=%d Nd=%d", prep->Ns, prep->Nd);
         return MOBGS_E_INVALID;
     }
-    // seg_stride 0: the two-pass lists (first frame of a workload, or the caller's choice)
-    return project_and_bin_enqueue(1, prep->Ns + prep->Nd, means, quats, scales, viewmats, Ks, opacities, 0, width, height,
-                                   eps2d, near_plane, far_plane, radius_clip, cull, radii, means2d, depths, conics,
-                                   tiles_per_gauss, cum_tiles, tile_offsets, tile_order, stats_dev, capacity_box,
-                                   keep_scan, scratch, capacity_listed, flatten_ids, seg_keys, seg_stride, enum_order,
-                                   isect_ids, max_tile_len_hint, stats_host_pinned, stats_seq, nullptr, 0, 9, pack_records,
-                                   tuning, stream, prep);
+    const ProjectIn in{.means = means, .quats = quats, .scales = scales, .viewmats = viewmats, .Ks = Ks,
+                       .opacities = opacities, .opac_per_camera = 0, .eps2d = eps2d, .near_plane = near_plane,
+                       .far_plane = far_plane, .radius_clip = radius_clip, .cull = cull, .prep = prep};
+    const ProjectOut po{.radii = radii, .means2d = means2d, .depths = depths, .conics = conics,
+                        .tiles_per_gauss = tiles_per_gauss};
+    const ListsOut lo{.cum_tiles = cum_tiles, .keep_scan = keep_scan, .tile_offsets = tile_offsets, .tile_order = tile_order,
+                      .stats_dev = stats_dev, .scratch = scratch, .capacity_listed = capacity_listed,
+                      .flatten_ids = flatten_ids, .keys = seg_keys, .isect_ids = isect_ids};
+    // the colours are built in the projection kernel: 9 channels; seg_stride 0: the two-pass lists (first frame of a
+    // workload, or the caller's choice)
+    const PackArgs pack{.records = pack_records, .channels = 9};
+    return project_and_bin_enqueue(bin_grid(1, prep->Ns + prep->Nd, width, height, capacity_box), in, po, lo,
+                                   FusedLists{seg_stride, enum_order}, max_tile_len_hint, stats_host_pinned, stats_seq, pack,
+                                   tuning, stream);
 }
 
 }  // extern "C"

@@ -8,7 +8,7 @@
 // 100 B in + 40 B out backward.  HBM-bound; the camera (R, t, K) is wave-uniform and lives in SGPRs.
 #include <stdarg.h>
 
-#include "common.h"
+#include "isect_launch.h"
 #include "prep_shared.h"
 
 namespace mobgs {
@@ -578,30 +578,31 @@ int mobgs_project_fwd(int C, int N, const float* means, const float* quats, cons
                       const float* viewmats, const float* Ks, int width, int height, float eps2d,
                       float near_plane, float far_plane, float radius_clip, int32_t* radii, float* means2d,
                       float* depths, float* conics, int32_t* tiles_per_gauss, void* stream) {
-    return mobgs::project_fwd_launch(C, N, means, quats, scales, viewmats, Ks, width, height, eps2d, near_plane, far_plane,
-                                     radius_clip, radii, means2d, depths, conics, tiles_per_gauss, nullptr, 0,
-                                     PackArgs{nullptr, nullptr, nullptr, 0, 0, 0, 0}, stream);
+    const ProjectIn in{.means = means, .quats = quats, .scales = scales, .viewmats = viewmats, .Ks = Ks, .eps2d = eps2d,
+                       .near_plane = near_plane, .far_plane = far_plane, .radius_clip = radius_clip};
+    const ProjectOut out{.radii = radii, .means2d = means2d, .depths = depths, .conics = conics,
+                         .tiles_per_gauss = tiles_per_gauss};
+    return mobgs::project_fwd_launch(bin_grid(C, N, width, height, /*no arena*/ 0), in, out, IntSpan{nullptr, 0},
+                                     PackArgs{nullptr, nullptr, nullptr, 0, 0, 0, 0}, BinArgs{nullptr, nullptr, 0, 0}, 0,
+                                     stream);
 }
 
 }  // extern "C"
 
-int mobgs::project_fwd_launch(int C, int N, const float* means, const float* quats, const float* scales,
-                              const float* viewmats, const float* Ks, int width, int height, float eps2d,
-                              float near_plane, float far_plane, float radius_clip, int32_t* radii, float* means2d,
-                              float* depths, float* conics, int32_t* tiles_per_gauss, int32_t* zero_ptr, size_t zero_n,
-                              PackArgs pack, void* stream, int geometry_per_camera, BinArgs bin,
-                              const MobgsPrepInputs* prep) {
-    if (C <= 0 || N < 0 || width <= 0 || height <= 0) {
-        set_error("mobgs_project_fwd: bad sizes C=%d N=%d W=%d H=%d", C, N, width, height);
+int mobgs::project_fwd_launch(const BinGrid& g, const ProjectIn& in, const ProjectOut& out, IntSpan zero, PackArgs pack,
+                              BinArgs bin, int geometry_per_camera, void* stream) {
+    const int C = g.C, N = g.N;
+    if (C <= 0 || N < 0 || g.width <= 0 || g.height <= 0) {
+        set_error("mobgs_project_fwd: bad sizes C=%d N=%d W=%d H=%d", C, N, g.width, g.height);
         return MOBGS_E_INVALID;
     }
     if (N == 0) {
-        if (zero_ptr && zero_n) hipMemsetAsync(zero_ptr, 0, sizeof(int32_t) * zero_n, (hipStream_t)stream);
+        if (zero.ptr && zero.count) hipMemsetAsync(zero.ptr, 0, sizeof(int32_t) * zero.count, (hipStream_t)stream);
         return MOBGS_OK;
     }
-    const int tile_w = (width + MOBGS_TILE - 1) / MOBGS_TILE, tile_h = (height + MOBGS_TILE - 1) / MOBGS_TILE;
     constexpr int T = MOBGS_PROJ_FWD_THREADS;
     dim3 grid((N + T - 1) / T, C);
+    const MobgsPrepInputs* prep = in.prep;
     if (prep) {
         // the state is built in-kernel: means / quats / scales / pack.opacities are OUTPUT arrays here
         if (C != 1 || geometry_per_camera || prep->Ns + prep->Nd != N || !pack.records || pack.channels != 9 ||
@@ -614,19 +615,20 @@ int mobgs::project_fwd_launch(int C, int N, const float* means, const float* qua
                               prep->s_opacity, prep->s_fdc, prep->s_ft, prep->d_control,
                               (const long long*)prep->d_ncp, prep->d_scaling, prep->d_rotation, prep->d_omega,
                               prep->d_opacity, prep->d_fdc, prep->d_ft, prep->d_trbf};
-        pf.means = const_cast<float*>(means);
-        pf.quats = const_cast<float*>(quats);
-        pf.scales = const_cast<float*>(scales);
+        pf.means = const_cast<float*>(in.means);
+        pf.quats = const_cast<float*>(in.quats);
+        pf.scales = const_cast<float*>(in.scales);
         pf.opac = const_cast<float*>(pack.opacities);
-        hipLaunchKernelGGL(project_fwd_kernel<true>, grid, dim3(T), 0, (hipStream_t)stream, N, means, quats, scales,
-                           viewmats, Ks, width, height, eps2d, near_plane, far_plane, radius_clip, tile_w, tile_h,
-                           radii, means2d, depths, conics, tiles_per_gauss, zero_ptr, (unsigned)zero_n, pack, 0, bin, pf);
+        hipLaunchKernelGGL(project_fwd_kernel<true>, grid, dim3(T), 0, (hipStream_t)stream, N, in.means, in.quats, in.scales,
+                           in.viewmats, in.Ks, g.width, g.height, in.eps2d, in.near_plane, in.far_plane, in.radius_clip,
+                           g.tile_w, g.tile_h, out.radii, out.means2d, out.depths, out.conics, out.tiles_per_gauss,
+                           zero.ptr, (unsigned)zero.count, pack, 0, bin, pf);
         return check_launch("project_fwd_kernel<prep>");
     }
-    hipLaunchKernelGGL(project_fwd_kernel<false>, grid, dim3(T), 0, (hipStream_t)stream, N, means, quats, scales,
-                       viewmats, Ks, width, height, eps2d, near_plane, far_plane, radius_clip, tile_w, tile_h,
-                       radii, means2d, depths, conics, tiles_per_gauss, zero_ptr, (unsigned)zero_n, pack,
-                       geometry_per_camera ? N : 0, bin, PrepFused{});
+    hipLaunchKernelGGL(project_fwd_kernel<false>, grid, dim3(T), 0, (hipStream_t)stream, N, in.means, in.quats, in.scales,
+                       in.viewmats, in.Ks, g.width, g.height, in.eps2d, in.near_plane, in.far_plane, in.radius_clip,
+                       g.tile_w, g.tile_h, out.radii, out.means2d, out.depths, out.conics, out.tiles_per_gauss, zero.ptr,
+                       (unsigned)zero.count, pack, geometry_per_camera ? N : 0, bin, PrepFused{});
     return check_launch("project_fwd_kernel");
 }
 

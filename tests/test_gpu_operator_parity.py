@@ -434,6 +434,44 @@ def test_long_tile_lists_sort_exactly(hip_device, n, w, h, scale, quant):
     assert torch.equal(meta["isect_ids"].cpu(), torch.from_numpy(ids))
 
 
+@pytest.mark.parametrize("n,w,h,scale,quant,arm", [(12000, 64, 48, 3.0, 2048, 2048), (40000, 64, 48, 3.0, 4, 12288)])
+def test_long_tile_lists_sort_exactly_on_a_speculative_second_frame(hip_device, n, w, h, scale, quant, arm):
+    """The speculative emit + sort (counts still on the device) with a hint beyond the one-launch sort: the second frame of
+    a workload whose first frame had lists > 2048 entries takes the long-list launch, and with lists > 3/4 x 16384 the
+    chunk + merge passes sized from the ARENA (the count is not known on the host).  12 tiles; the lists must be the
+    synchronous path's, entry for entry."""
+    from mobgs_amd import rendering
+    from mobgs_amd.rendering import rasterization
+    s, _ = _scene(n, w, h, 5, 3)
+    s["scales"] = s["scales"] * scale
+    s["means"][:, 2] = torch.round(s["means"][:, 2] * quant) / quant + 1.0  # exact depth ties -> index tie-break
+    d = _to(s, hip_device)
+    key = rendering._workload_key(hip_device, 1, n, w, h)
+    res = {}
+    rendering.set_tile_culling(False)
+    try:
+        for spec in (True, False):
+            rendering.SPECULATIVE_BINNING = spec
+            for table in (rendering._capacity, rendering._cap_listed, rendering._len_hint, rendering._seg_sticky):
+                table.clear()
+            for frame in range(2 if spec else 1):
+                if frame:  # what the first frame left selects the arm of the second
+                    assert rendering._len_hint.get(key, 0) > arm, rendering._len_hint
+                before = (rendering.list_rebuilds[0], rendering.fused_calls[0])
+                _, _, meta = rasterization(d["means"], d["quats"], d["scales"], d["opacities"], d["colors"], d["viewmats"],
+                                           d["Ks"], w, h, packed=False)
+                if frame:  # ... whose lists are the speculative two-pass call's own: no synchronous rebuild, no segments
+                    assert (rendering.list_rebuilds[0], rendering.fused_calls[0]) == before
+            res[spec] = {k: meta[k].cpu() for k in ("isect_offsets", "flatten_ids", "isect_ids")}
+    finally:
+        rendering.SPECULATIVE_BINNING = True
+        rendering.set_tile_culling(True)
+    offs = res[False]["isect_offsets"].reshape(-1).tolist() + [res[False]["flatten_ids"].numel()]
+    assert max(b - a_ for a_, b in zip(offs[:-1], offs[1:])) > arm
+    for k in res[False]:
+        assert torch.equal(res[True][k], res[False][k]), k
+
+
 def test_two_cameras_forward_backward(hip_device):
     """C = 2 cameras in one call (gsplat's batched-camera form): lists, images and all gradients incl. both viewmats."""
     from mobgs_amd import rendering
