@@ -178,6 +178,15 @@ class DeblurTrainer:
                                       time=i / (n - 1.0), world_view_transform=view_pose(i).transpose(0, 1).contiguous())
                 for i in range(n)]
 
+    def estimate_exposure(self):
+        """train.py:474-492 for every view of the batch: exposure_time_expo[uid] from the static flow between the view's
+        neighbours and the static flow over its own exposure, halved for the first and the last view (:490).  Device
+        work only; -> the per-view stats tensors."""
+        cams, last = self.cams, len(self.cams) - 1
+        return [self.blce.estimate_exposure_time(c, cams[max(i - 1, 0)], cams[min(i + 1, last)], self.stat, self.dyn,
+                                                 None, self.bg, edge=(c.uid == 0 or c.uid == last))
+                for i, c in enumerate(cams)]
+
     def _iteration_sharded(self) -> torch.Tensor:
         """N > 1: the same iteration with its loss kept apart per view, so that the backward pass runs view by view and
         each view's gradient message (with its densification statistics) is all-reduced on the communication stream while
@@ -372,7 +381,7 @@ class DeblurTrainer:
 
 
 def train(dev="cuda:0", iters=40, ns=4000, nd=2000, width=256, height=192, n_views=2, seed=0, lambda_flow=1e-2,
-          shard=None, log=None, graph=False, prune_control_every=0, from_views=False):
+          shard=None, log=None, graph=False, prune_control_every=0, from_views=False, estimate_exposure=0):
     """graph=True (single process): forward + losses + backward of the iteration recorded ONCE as a HIP graph
     (mobgs_amd.graphed.GraphedCallable) and replayed, the Adam step outside -- for small images / few Gaussians, where an
     iteration is ~1400 launches and bound by the host (the reference's own 512x288 / 30 k operating point: 9.5 -> 7.5 ms).
@@ -381,12 +390,17 @@ def train(dev="cuda:0", iters=40, ns=4000, nd=2000, width=256, height=192, n_vie
     (TrainableGaussians.onedown_control_pts; in place, so a recorded iteration stays valid) and the smallest count is
     logged as train.py:734 does (MinCtrl).
     from_views=True: both sets are built by scene_init.scene_initialization from synthetic views (sets_from_views)
-    instead of being sampled directly."""
+    instead of being sampled directly.
+    estimate_exposure=N > 0: before every N-th iteration each view's exposure_time_expo entry is re-estimated from rendered
+    static flow (DeblurTrainer.estimate_exposure; train.py:474-492 does it every 10th).  In place and on the device, so a
+    recorded iteration reads the new values."""
     t = DeblurTrainer(dev, ns, nd, width, height, n_views, seed, lambda_flow, shard, iters, from_views)
     history = []
     prune_views = t.prune_viewpoints() if prune_control_every else None
     fb, pending = None, []
     for it in range(1, iters + 1):
+        if estimate_exposure and it % estimate_exposure == 0:
+            t.estimate_exposure()
         if graph and it == 2 and not t.shard.collective:   # (iteration 1 ran eagerly: arenas and hints exist)
             from mobgs_amd.graphed import GraphedCallable
             fb = GraphedCallable(t.forward_backward, warmup=0)
@@ -433,6 +447,8 @@ if __name__ == "__main__":
                     help="every K iterations drop one spline control point where the trajectory moves <= 1 px (0 = never)")
     ap.add_argument("--from-views", action="store_true",
                     help="build both sets through scene_initialization from synthetic views instead of sampling them")
+    ap.add_argument("--estimate-exposure", type=int, default=0, metavar="N",
+                    help="every N iterations re-estimate each view's exposure time from rendered static flow (0 = never)")
     a = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -441,4 +457,4 @@ if __name__ == "__main__":
         torch.cuda.set_device(local)
         dist.init_process_group("nccl", device_id=torch.device("cuda", local))
     train(dev=f"cuda:{local}", iters=a.iters, ns=a.ns, nd=a.nd, width=a.width, height=a.height, log=10, graph=a.graph,
-          prune_control_every=a.prune_control_every, from_views=a.from_views)
+          prune_control_every=a.prune_control_every, from_views=a.from_views, estimate_exposure=a.estimate_exposure)

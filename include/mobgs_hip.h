@@ -147,7 +147,7 @@ int mobgs_cotangent_probe(int n_arrays, const float* const* arrays, const size_t
  * points changes (round 4 inserted `records` into mobgs_raster_bwd_reduce and changed the gradient-slot format without
  * one: a stale host extension would have passed shifted pointers).  Bindings compare it with the MOBGS_ABI_VERSION
  * they were built against and refuse to run on a mismatch (mobgs_amd/_lib.py, csrc/fastpath.cpp). */
-#define MOBGS_ABI_VERSION 12
+#define MOBGS_ABI_VERSION 13
 int mobgs_abi_version(void);
 /* Text of the last error raised on the calling thread ("" if none). */
 const char* mobgs_last_error(void);
@@ -914,6 +914,27 @@ int mobgs_seed_classify(int V, int H, int W, const float* accum_error, const voi
                         uint8_t* inconsistent, uint8_t* cls, float* points, float* mean, void* stream);
 int mobgs_seed_trajectories(int N, int T, int M, int V, int H, int W, const float* coords, const float* tracklet,
                             const float* points, int32_t* track_index, float* trajectory, void* stream);
+
+/* ---- K20: exposure-time estimate from two rendered flow maps ------------------------------------------------------
+ * What /root/reference/train.py:482-492 computes from its two get_flow_static images, on the caller's stream, without a
+ * sort, a read-back or a float atomic (csrc/exposure.hip: radix select on the fp32 bit patterns).  cam_flow and
+ * latent_flow are [n,2] (8-byte aligned), 1 <= n <= 2^30.  In fp32, every operation as written and correctly rounded:
+ *   cam_mag = sqrt(x x + y y), lat_mag likewise; ratio = lat_mag / cam_mag;
+ *   threshold = torch.quantile(cam_mag, q), linear: pos = q * float(n - 1) (fp32), lo = floor(pos), hi = ceil(pos),
+ *     w = pos - lo, a / b = the order statistics of rank lo / hi, threshold = w < 0.5 ? a + w (b - a)
+ *     : b - (b - a)(1 - w);
+ *   valid = cam_mag > threshold, n_valid = its count;
+ *   *slot = scale * (the LOWER median of ratio over the valid pixels: rank (n_valid - 1) / 2, as torch.median).
+ * stats (device, 4 x int32) = {n_valid, n_nonfinite, updated, 0}; n_nonfinite counts inf / NaN magnitudes of both maps.
+ * Unlike the reference, which would store NaN: if n_valid == 0 or n_nonfinite > 0, *slot is left untouched and
+ * updated = 0 (n_valid is then the count against whatever threshold the non-finite keys produced).
+ * scratch: mobgs_exposure_scratch_bytes(n) bytes, 4-byte aligned, contents irrelevant on entry (the call zeroes what it
+ * accumulates into); 0 is returned for an n outside the range.  The inputs are only read.
+ * Refused with MOBGS_E_INVALID before any launch: n outside the range, a NULL or misaligned pointer, q outside [0, 1]
+ * (NaN included). */
+size_t mobgs_exposure_scratch_bytes(int64_t n);
+int mobgs_exposure_estimate(int64_t n, const float* cam_flow, const float* latent_flow, float q, float scale,
+                            float* slot, int32_t* stats, void* scratch, void* stream);
 
 #ifdef __cplusplus
 }

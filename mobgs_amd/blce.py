@@ -423,6 +423,41 @@ class blceKernel(nn.Module):
                       for w2c_i, c2w_i in zip(warped_w2c.unbind(0), warped_c2w.unbind(0))]
         return cams, exposure_time
 
+    @torch.no_grad()
+    def estimate_exposure_time(self, view_cam, bwd_cam, fwd_cam, stat_pc, dyn_pc, pipe, bg, *, edge=None, quantile=0.01,
+                               warped_cams=None):
+        """/root/reference/train.py:474-492 for one view: the static flow between the previous and the next view and the
+        static flow between the first and the last latent camera of the exposure, both rendered through `view_cam`
+        (gaussian_renderer.get_flow_static_pair: one projection batch, one 4-channel pass), and
+
+            exposure_time_expo[view_cam.uid] = median(latent / camera flow magnitude over the pixels whose camera flow is
+                                                      above its `quantile`)          (halved when `edge`)
+
+        stored ON THE DEVICE by the selection kernels (loss_utils.exposure_ratio, csrc/exposure.hip): no .item(), no
+        boolean indexing, no synchronisation.  `edge`: the view is the first or the last of its batch (train.py:490).
+        `warped_cams`: the list get_warped_cams returned for this view, when the caller has it already.
+        -> the int32 stats tensor {n_valid, n_nonfinite, updated, 0}.  Where the reference would store NaN (no valid pixel,
+        a non-finite flow) the entry keeps its value and updated = 0."""
+        from .gaussian_renderer import get_flow_static_pair
+        from .loss_utils import exposure_ratio
+        expo = self.model.exposure_time_expo
+        if not expo.is_cuda:
+            raise RuntimeError("blceKernel.estimate_exposure_time: the model must live on a HIP device (device='cuda'); "
+                               "there is no CPU path")
+        if expo.dtype != torch.float32 or not expo.is_contiguous():
+            raise ValueError("blceKernel.estimate_exposure_time: exposure_time_expo must be a contiguous float32 tensor")
+        uid = int(view_cam.uid)
+        if not 0 <= uid < expo.shape[0]:
+            raise IndexError(f"BLCE: camera uid {uid} outside the {expo.shape[0]} views of the model")
+        if warped_cams is None:
+            warped_cams, _ = self.get_warped_cams(view_cam, fwd_cam, bwd_cam)
+        cam_flow, latent_flow = get_flow_static_pair(bwd_cam, fwd_cam, warped_cams[0], warped_cams[-1], view_cam, stat_pc,
+                                                     dyn_pc, pipe, bg)
+        # (a view that shares the parameter's version counter: exposure_ratio moves it after the raw-pointer store, so
+        # that what is cached against exposure_time_expo._version -- gaussian_renderer._times -- is rebuilt)
+        _, stats = exposure_ratio(cam_flow, latent_flow, q=quantile, scale=0.5 if edge else 1.0, out=expo.detach()[uid])
+        return stats
+
     def _exposure_steps(self, dev):
         t = self._steps.get(str(dev))
         if t is None:

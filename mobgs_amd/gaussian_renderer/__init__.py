@@ -26,7 +26,7 @@ from ..ops import PrepSplats, decode, decode_with_channels
 from . import network_gui  # noqa: F401  (train.py imports it from here)
 
 __all__ = ["render", "render_many", "viewspace_grad", "get_flow", "get_flow_many", "get_flow_static",
-           "interpolate_cubic_hermite", "network_gui"]
+           "get_flow_static_pair", "interpolate_cubic_hermite", "network_gui"]
 
 # True: the static-only / dynamic-only images of a train-mode render() come from one layered compositing pass over
 # the lists of the combined render (csrc/raster_layers.hip); False: one rasterization per set, call for call like
@@ -910,3 +910,30 @@ def get_flow_static(source_camera, target_camera, splat_camera, stat_pc, dyn_pc,
 
 get_flow_static = _scoped(get_flow_static, stat_at=3)
 
+
+@torch.no_grad()
+def get_flow_static_pair(source_a, target_a, source_b, target_b, splat_camera, stat_pc, dyn_pc, pipe, bg_color):
+    """The rendered flows of get_flow_static(source_a, target_a, splat_camera, ...) and get_flow_static(source_b, target_b,
+    splat_camera, ...) -- the camera flow and the latent flow of the exposure-time estimate, /root/reference/train.py:479-480
+    -- from ONE projection of the static set through the four cameras (a batch of C = 4) and ONE 4-channel binning, sort and
+    compositing pass through the splat camera, instead of four projections and two 2-channel passes over the same lists.
+    Channels accumulate independently and in list order, so each map is the one its own call returns.  Forward only.  All
+    five cameras share one image size; intrinsics are read from the source cameras, the splat pass uses source_a's (as
+    get_flow_static(source_a, ...) does).  -> (flow_a [1,H,W,2], flow_b [1,H,W,2])."""
+    means, scales = stat_pc.get_xyz, stat_pc.get_scaling
+    quats, opac = stat_pc._rotation, stat_pc.get_opacity.squeeze(-1)
+    cams = (source_a, target_a, source_b, target_b)
+    W, H = int(source_a.image_width), int(source_a.image_height)
+    if any((int(c.image_width), int(c.image_height)) != (W, H) for c in cams + (splat_camera,)):
+        raise ValueError("get_flow_static_pair: all cameras must share one image size")
+    Ka, Kb = source_a.K, source_b.K
+    m2d = _R.fully_fused_projection(means=means, covars=None, quats=quats, scales=scales,
+                                    viewmats=torch.stack([c.world_view_transform.transpose(0, 1) for c in cams]),
+                                    Ks=torch.stack([Ka, Ka, Kb, Kb]), width=W, height=H)[1]   # [4,Ns,2]
+    flow_2d = torch.cat([m2d[0] - m2d[1], m2d[2] - m2d[3]], dim=-1)
+    img = _R.rasterization(means=means, quats=quats, scales=scales, opacities=opac, colors=flow_2d, backgrounds=None,
+                           viewmats=splat_camera.world_view_transform.transpose(0, 1)[None], Ks=Ka[None], width=W,
+                           height=H, packed=False, render_mode="RGB")[0]
+    return img[..., :2].contiguous(), img[..., 2:].contiguous()
+
+get_flow_static_pair = _scoped(get_flow_static_pair, stat_at=5)

@@ -9,6 +9,7 @@ Gradients flow to the first argument (the rendered image); the second (ground tr
 in every reference call.  The masked L1 exists in the reference only inside the flow-consistency loss
 (train.py:651-671): `flow_warp_loss` below is that whole block -- coordinate normalisation, both grid_sample warps and
 both masked L1 terms -- as one forward and one backward kernel (csrc/flowloss.hip), differentiable in all six inputs.
+`exposure_ratio` is the statistic of train.py:482-491 on two flow maps (csrc/exposure.hip): no sort, no read-back.
 """
 from __future__ import annotations
 
@@ -169,3 +170,45 @@ def psnr(img1, img2, mask=None):
         raise NotImplementedError("masked psnr is not on the training path")
     mse = ((img1 - img2) ** 2).reshape(img1.shape[0], -1).mean(1, keepdim=True)
     return 20 * torch.log10(1.0 / torch.sqrt(mse.float()))
+
+
+@torch.no_grad()
+def exposure_ratio(cam_flow, latent_flow, q=0.01, scale=1.0, out=None):
+    """/root/reference/train.py:482-491 on two flow maps of equal size [...,2] (include/mobgs_hip.h K20):
+
+        scale * median((|latent_flow| / |cam_flow|)[|cam_flow| > quantile(|cam_flow|, q)])
+
+    bit-equal to torch.quantile / torch.median on the magnitudes sqrt(x x + y y), computed by radix select on the device:
+    no sort, no boolean indexing, no host synchronisation.  -> (value, stats): stats is the int32 tensor {n_valid,
+    n_nonfinite, updated, 0}.  With `out` (one fp32 element on the device, e.g. a view into a parameter) the value is
+    stored there and `out` is returned as value.  Where the reference would store NaN -- no pixel above the threshold, or
+    an inf / NaN magnitude in either map -- nothing is stored and updated = 0: `out` keeps its value (without `out`, value
+    is NaN)."""
+    lib = _lib.load()
+    for name, t in (("cam_flow", cam_flow), ("latent_flow", latent_flow)):
+        if not torch.is_tensor(t) or t.dim() < 1 or t.shape[-1] != 2 or t.numel() == 0:
+            raise ValueError(f"exposure_ratio: {name} must be a non-empty [...,2] tensor")
+        if not t.is_cuda:
+            raise RuntimeError("exposure_ratio: tensors must live on a HIP device (device='cuda'); there is no CPU path")
+    if cam_flow.numel() != latent_flow.numel() or cam_flow.device != latent_flow.device:
+        raise ValueError("exposure_ratio: the two flow maps must have the same number of pixels and share a device")
+    if not 0.0 <= float(q) <= 1.0:
+        raise ValueError(f"exposure_ratio: quantile {q} outside [0, 1]")
+    cam, lat = f32c(cam_flow.detach()), f32c(latent_flow.detach())
+    dev = cam.device
+    if out is None:
+        value = torch.full((), float("nan"), dtype=torch.float32, device=dev)
+    else:
+        if not (torch.is_tensor(out) and out.is_cuda and out.device == dev and out.dtype == torch.float32
+                and out.numel() == 1):
+            raise ValueError("exposure_ratio: out must be one float32 element on the flow maps' device")
+        value = out
+    n = cam.numel() // 2
+    stats = torch.empty(4, dtype=torch.int32, device=dev)
+    scratch = torch.empty(int(lib.mobgs_exposure_scratch_bytes(n)), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.mobgs_exposure_estimate(n, ptr(cam), ptr(lat), float(q), float(scale), ptr(value), ptr(stats),
+                                          ptr(scratch), stream()), "mobgs_exposure_estimate")
+    if out is not None:   # written through a raw pointer: move Tensor._version as an in-place torch op would have
+        torch.autograd.graph.increment_version(out)
+    return value, stats
