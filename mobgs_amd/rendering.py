@@ -150,6 +150,12 @@ class TileLists:
         p, self._pending = self._pending, None
         return p.finish(self) if p is not None else False
 
+    def _fill(self, C, N, tile_w, tile_h, cum_tiles, keep_scan, tile_offsets, tile_order, tiles_per_gauss, order=None):
+        """Geometry and buffers of one binning call (the counts and the count-sized views follow: _set_counts)."""
+        self.C, self.N, self.tile_w, self.tile_h = C, N, tile_w, tile_h
+        self.cum_tiles, self.keep_scan, self.tile_offsets, self.tile_order = cum_tiles, keep_scan, tile_offsets, tile_order
+        self.tiles_per_gauss, self.order = tiles_per_gauss, order
+
     def _set_counts(self, n_box, n_isects, max_len, flatten_arena, isect_arena):
         self._n_box, self._n_isects, self._max_tile_len = n_box, n_isects, max_len
         self.flatten_arena = flatten_arena
@@ -251,10 +257,10 @@ class _PendingCounts:
         _stats_slots.give(self.slot)
         self.slot = None
         key, cap_box, cap_listed, seg_stride = self.caps
+        hints = hint_record(key)
         if n_box <= cap_box and n_isects <= cap_listed and (seg_stride == 0 or max_len <= seg_stride):
             tl._set_counts(n_box, n_isects, max_len, *self.arenas)
-            _note_longest(key, max_len)
-            _last_counts[key] = (n_box, n_isects)
+            hints.resolved(n_box, n_isects, max_len)
             last_stats.update(n_isects=n_isects, n_box=n_box, max_tile_len=max_len,
                               n_tiles=tl.C * tl.tile_w * tl.tile_h)
             return False
@@ -263,14 +269,13 @@ class _PendingCounts:
         # entry points -- the projection outputs do not depend on the arena
         if seg_stride and max_len > seg_stride:
             seg_overflows[0] += 1
-        _capacity[key] = max(_capacity.get(key, 0), int(n_box * 1.25) + 1024)
+        hints.overflowed(n_box)
         fresh = build_tile_lists(*self.rebuild_args)
-        for name in ("cum_tiles", "keep_scan", "tile_offsets", "tile_order", "tiles_per_gauss"):
-            setattr(tl, name, getattr(fresh, name))
-        tl.order = None  # (the two-pass rebuild enumerates in splat order)
+        # (order = None: the two-pass rebuild enumerates in splat order)
+        tl._fill(tl.C, tl.N, tl.tile_w, tl.tile_h, fresh.cum_tiles, fresh.keep_scan, fresh.tile_offsets, fresh.tile_order,
+                 fresh.tiles_per_gauss)
         tl._set_counts(fresh._n_box, fresh._n_isects, fresh._max_tile_len, fresh.flatten_arena, fresh._isect_ids)
-        _cap_listed[key] = max(_cap_listed.get(key, 0), int(fresh._n_isects * 1.25) + 1024)
-        _note_longest(key, fresh._max_tile_len)
+        hints.rebuilt(fresh._n_isects, fresh._max_tile_len)
         tl.rebuilds += 1
         list_rebuilds[0] += 1
         return True
@@ -292,41 +297,106 @@ FUSED_ARENA_BYTES = int(float(os.environ.get("MOBGS_FUSED_ARENA_MB", "2048")) * 
 _FUSED_COPIES = 8  # counter copies of the binning kernel (csrc/isect.hip TC_COPIES)
 
 
-def _note_longest(key, max_len):
-    """The longest list of the frame just resolved becomes the next frame's hint; it decays slowly (5 % per frame), so
-    that a camera path whose longest list fluctuates does not overflow its segments every other frame."""
-    _len_hint[key] = max(int(max_len), int(_len_hint.get(key, 0) * 0.95))
+class _Hints:
+    """What one workload (_workload_key) carries from frame to frame: arena capacities, the longest tile list (selects the
+    binning / sort variant and sizes the key segments), the last resolved counts (StaticCapacity sizes from them) and the
+    key-segment stride in use.  Performance only -- a wrong hint costs a rebuild, never a result.  The methods below are
+    the only code of this module that writes the fields, one method per event (DESIGN.md has the table).
+    cap_box: capacity of the keep-flag buffer (grows geometrically, never shrinks); cap_listed: of the listed-intersection
+    buffers; longest: longest per-tile list of the previous frames; last_counts: (I_box, I_listed) of the most recent
+    resolved frame; seg_stride: key-segment stride of the single-pass path (sticky, see stride())."""
 
+    __slots__ = ("cap_box", "cap_listed", "longest", "last_counts", "seg_stride")
 
-_seg_sticky = {}  # workload key -> the key-segment stride in use (see _fused_seg_stride)
+    def __init__(self):
+        self.cap_box = self.cap_listed = self.longest = self.seg_stride = 0
+        self.last_counts = (0, 0)
 
+    def caps(self, C, N):
+        """-> (cap_box, cap_listed, len_hint) a call takes by default."""
+        box = max(self.cap_box, 16 * (C * N) + 1024)
+        return box, max(self.cap_listed, box // 2), self.longest
 
-def _fused_seg_stride(len_hint, C, N, nt, cap_box, key=None) -> int:
-    """Key-segment capacity per tile for the single-pass path, or 0 = use the two-pass path.
-    The stride is STICKY per workload: the hint follows the longest list of the previous frames (it breathes by a few
-    per cent from view to view), and an arena whose size changes with it defeats the caching allocator -- a block of a
-    slightly larger size than any cached one is a fresh hipMalloc, which synchronises the device: at 1352x1014 the
-    8-camera batches' 1.3-GB arenas grew twice in the first iterations of a training run, one of them inside the driver's
-    three timed iterations (BENCH_r05: 61.7 ms mean against a 48.3 ms median; VERDICT r5 item 4, found with
-    scripts/r06/train_iter_probe.py).  A needed stride within [prev / 2, prev] keeps `prev`; a larger one grows with 25 %
-    headroom; only a workload that shrank to less than half gives memory back."""
-    if not FUSED_LISTS or N <= 0 or len_hint <= 0 or cap_box < 4 * C * N + 2:
-        return 0
-    stride = max(64, (int(len_hint * SEG_SLACK) + 15) // 16 * 16)
-    limit = _lib_().mobgs_fused_max_seg_stride()
-    if key is not None:
-        prev = _seg_sticky.get(key, 0)
+    def static_caps(self, C, N, margin):
+        """... and under StaticCapacity(margin): the last resolved frame's counts times `margin`, once there is one."""
+        box, listed, _ = self.caps(C, N)
+        seen_box, seen_listed = self.last_counts
+        if seen_box:
+            box = max(int(seen_box * margin) + 1024, 4096)
+            listed = max(int(seen_listed * margin) + 1024, 4096)
+        return box, listed, int(self.longest * margin)
+
+    def stride(self, len_hint, C, N, nt, cap_box) -> int:
+        """Key-segment capacity per tile for the single-pass path, or 0 = use the two-pass path.
+        The stride is STICKY per workload: the hint breathes by a few per cent from view to view, and an arena whose size
+        changes with it defeats the caching allocator (a slightly larger block is a fresh hipMalloc, which synchronises the
+        device; DESIGN.md has the measurement).  A needed stride within [prev / 2, prev] keeps `prev`; a larger one grows
+        with 25 % headroom; only a workload that shrank to less than half gives memory back."""
+        if not FUSED_LISTS or N <= 0 or len_hint <= 0 or cap_box < 4 * C * N + 2:
+            return 0
+        stride = max(64, (int(len_hint * SEG_SLACK) + 15) // 16 * 16)
+        limit = _lib_().mobgs_fused_max_seg_stride()
+        prev = self.seg_stride
         if prev >= stride > prev // 2:
             stride = prev
         else:
             grown = (int(stride * 1.25) + 15) // 16 * 16 if prev else stride
             if grown <= limit and nt * _FUSED_COPIES * grown * 8 <= FUSED_ARENA_BYTES:
                 stride = grown
-    if stride > limit or nt * _FUSED_COPIES * stride * 8 > FUSED_ARENA_BYTES:
-        return 0
-    if key is not None:
-        _seg_sticky[key] = stride
-    return stride
+        if stride > limit or nt * _FUSED_COPIES * stride * 8 > FUSED_ARENA_BYTES:
+            return 0
+        self.seg_stride = stride
+        return stride
+
+    def keep_caps(self, cap_box, cap_listed):
+        """The capacities a call was issued with (speculative: before its counts are known) or ended with (synchronous)."""
+        self.cap_box, self.cap_listed = cap_box, cap_listed
+
+    def _decay_to(self, max_len):
+        # the hint decays slowly (5 % per frame), so that a camera path whose longest list fluctuates does not overflow
+        # its segments every other frame
+        self.longest = max(int(max_len), int(self.longest * 0.95))
+
+    def resolved(self, n_box, n_isects, max_len):
+        """A speculative frame resolved within its arenas."""
+        self._decay_to(max_len)
+        self.last_counts = (n_box, n_isects)
+
+    def overflowed(self, n_box):
+        """A speculative frame overflowed: grow the box arena BEFORE the synchronous rebuild (which sizes from it) ..."""
+        self.cap_box = max(self.cap_box, int(n_box * 1.25) + 1024)
+
+    def rebuilt(self, n_isects, max_len):
+        """... and the listed arena from what the rebuild counted."""
+        self.cap_listed = max(self.cap_listed, int(n_isects * 1.25) + 1024)
+        self._decay_to(max_len)
+
+    def measured(self, cap_box, max_len):
+        """A synchronous build_tile_lists ended with this arena and this longest list (the hint is overwritten, no decay)."""
+        self.cap_box, self.longest = cap_box, max_len
+
+    def observed(self, n_box, n_isects, max_len):
+        """StaticCapacity.check() read these counts from a landing row: running maxima."""
+        self.last_counts = (max(n_box, self.last_counts[0]), max(n_isects, self.last_counts[1]))
+        self.longest = max(max_len, self.longest)
+
+
+_hints = {}  # workload key -> _Hints
+
+
+def hint_record(key) -> _Hints:
+    """The record of a workload key (created empty on first use)."""
+    rec = _hints.get(key)
+    if rec is None:
+        rec = _hints[key] = _Hints()
+    return rec
+
+
+def forget_hints() -> None:
+    """Tests / experiments: every workload starts afresh (first-frame guesses, two-pass lists)."""
+    _hints.clear()
+
+
 _tile_culling = True
 # Caller-side policy handed to the library with every call (include/mobgs_hip.h MobgsTuning; the library itself keeps
 # no state).  tuning.heavy_tile_len / tuning.quadrant_culling / tuning.block_walk may be changed by tests and
@@ -338,7 +408,7 @@ if os.environ.get("MOBGS_BWD_MFMA") is not None:  # A/B arm of the round-4 backw
 
 def _tuning_with_hint(key):
     """`tuning` plus the longest list the previous frame on this device had (selects the dense binning variant)."""
-    t = tuning.copy(longest_list_hint=_len_hint.get(key, 0), geometry_per_camera=0)
+    t = tuning.copy(longest_list_hint=hint_record(key).longest, geometry_per_camera=0)
     _tuning_keepalive.append(t)
     del _tuning_keepalive[:-8]
     return t.ref()
@@ -461,34 +531,23 @@ class StaticCapacity:
         return False
 
     def caps(self, key, C, N):
-        box = max(_capacity.get(key, 0), 16 * (C * N) + 1024)
-        listed = max(_cap_listed.get(key, 0), box // 2)
-        seen_box, seen_listed = _last_counts.get(key, (0, 0))
-        if seen_box:
-            box = max(int(seen_box * self.margin) + 1024, 4096)
-            listed = max(int(seen_listed * self.margin) + 1024, 4096)
-        hint = int(_len_hint.get(key, 0) * self.margin)
-        return box, listed, hint
+        return hint_record(key).static_caps(C, N, self.margin)
 
     def check(self) -> bool:
         """True when every binning call issued under this context fitted its arenas (call after a synchronisation)."""
         ok = True
         for row, _, cap_box, cap_listed, key, seg_stride in self.rows:
             n_box, n_isects, max_len = (int(v) for v in row[:3])
-            _last_counts[key] = (max(n_box, _last_counts.get(key, (0, 0))[0]), max(n_isects, _last_counts.get(key, (0, 0))[1]))
-            _len_hint[key] = max(max_len, _len_hint.get(key, 0))
+            hint_record(key).observed(n_box, n_isects, max_len)
             ok = ok and n_box <= cap_box and n_isects <= cap_listed and (seg_stride == 0 or max_len <= seg_stride)
         return ok
 
 
 _static = None
-_last_counts = {}  # workload key -> (I_box, I_listed) of the most recent resolved frame
 # True: the projection/binning call does not wait for the intersection counts (see TileLists); False: it does
 SPECULATIVE_BINNING = True
-_len_hint = {}  # workload key -> longest per-tile list of the previous frame (selects the sort variant)
 # True: the compositing kernels take tiles heaviest-list-first (TileLists.tile_order); False: raster order
 TILE_SCHEDULE = os.environ.get("MOBGS_TILE_SCHEDULE", "1") != "0"
-_capacity = {}  # workload key -> current capacity of the keep-flag buffer (grows geometrically, never shrinks)
 
 
 # Whose hints: the renderer's entry points (gaussian_renderer.render & co) run inside hint_scope(scene token) -- a small
@@ -568,39 +627,37 @@ def build_tile_lists(means2d: Tensor, radii: Tensor, depths: Tensor, conics: Ten
     tile_w, tile_h = math.ceil(width / TILE), math.ceil(height / TILE)
     nt = C * tile_w * tile_h
     tl = TileLists()
-    tl.C, tl.N, tl.tile_w, tl.tile_h = C, N, tile_w, tile_h
-    tl.tiles_per_gauss = tiles_per_gauss
-    tl.cum_tiles = torch.empty(C * N + 1, dtype=torch.int32, device=dev)
-    tl.tile_offsets = torch.empty(nt + 1, dtype=torch.int32, device=dev)
-    tl.tile_order = (torch.empty(lib.mobgs_tile_order_len(nt), dtype=torch.int32, device=dev)
-                     if TILE_SCHEDULE else None)
+    cum_tiles = torch.empty(C * N + 1, dtype=torch.int32, device=dev)
+    tile_offsets = torch.empty(nt + 1, dtype=torch.int32, device=dev)
+    tile_order = torch.empty(lib.mobgs_tile_order_len(nt), dtype=torch.int32, device=dev) if TILE_SCHEDULE else None
     stats = torch.empty(3, dtype=torch.int64, device=dev)
     opac = f32c(opacities)
     key = _workload_key(dev, C, N, width, height)
-    cap = max(_capacity.get(key, 0), 16 * (C * N) + 1024)
+    hints = hint_record(key)
+    cap = hints.caps(C, N)[0]
     while True:
-        tl.keep_scan = torch.empty(lib.mobgs_keep_scan_len(cap), dtype=torch.int32, device=dev)
+        keep_scan = torch.empty(lib.mobgs_keep_scan_len(cap), dtype=torch.int32, device=dev)
         scratch = torch.empty(lib.mobgs_isect_scratch_bytes(C * N, nt, cap), dtype=torch.uint8, device=dev)
         check(lib.mobgs_isect_offsets(C, N, tile_w, tile_h, width, height, int(_tile_culling), cap,
                                       ptr(tiles_per_gauss), ptr(means2d), ptr(radii), ptr(conics), ptr(opac),
-                                      1 if opac.dim() == 2 else 0, ptr(tl.cum_tiles), ptr(tl.keep_scan),
-                                      ptr(tl.tile_offsets), ptr(tl.tile_order), 0, ptr(stats), ptr(scratch),
+                                      1 if opac.dim() == 2 else 0, ptr(cum_tiles), ptr(keep_scan),
+                                      ptr(tile_offsets), ptr(tile_order), 0, ptr(stats), ptr(scratch),
                                       _tuning_with_hint(key), stream()),
               "mobgs_isect_offsets")
         n_box, n_isects, max_len = (int(v) for v in stats.tolist())  # the pipeline's one host sync (as in gsplat)
         if n_box <= cap:
             break
         cap = int(n_box * 1.25) + 1024  # first call on a denser scene: grow and redo (rare)
-    _capacity[key] = cap
+    hints.measured(cap, max_len)  # (the hint: dense-region variant of the next frame's binning when lists are long)
+    tl._fill(C, N, tile_w, tile_h, cum_tiles, keep_scan, tile_offsets, tile_order, tiles_per_gauss)
     last_stats.update(n_isects=n_isects, n_box=n_box, max_tile_len=max_len, n_tiles=nt)
-    _len_hint[key] = max_len  # next frame: dense-region variant of the binning when lists are long
     flatten_ids = torch.empty(n_isects, dtype=torch.int32, device=dev)
     isect_ids = torch.empty(n_isects, dtype=torch.int64, device=dev) if want_isect_ids else None
     tl._set_counts(n_box, n_isects, max_len, flatten_ids, isect_ids)
     if n_isects > 0:
         keys = torch.empty(n_isects, dtype=torch.int64, device=dev)
-        check(lib.mobgs_isect_emit_sort(C, N, tile_w, tile_h, cap, n_isects, max_len, ptr(depths), ptr(tl.cum_tiles),
-                                        ptr(tl.tile_offsets), ptr(scratch), ptr(keys), ptr(flatten_ids),
+        check(lib.mobgs_isect_emit_sort(C, N, tile_w, tile_h, cap, n_isects, max_len, ptr(depths), ptr(cum_tiles),
+                                        ptr(tile_offsets), ptr(scratch), ptr(keys), ptr(flatten_ids),
                                         ptr(isect_ids), stream()), "mobgs_isect_emit_sort")
     return tl
 
@@ -1295,7 +1352,190 @@ class _RasterizeClasses(torch.autograd.Function):
                 _fold_cameras(v_opac, opac_per_camera, C), v_extra, None, None, None, None, None, None, None, None, None)
 
 
-_cap_listed = {}  # workload key -> capacity of the listed-intersection buffers
+def _project_and_bin(means, quats, scales, viewmats, Ks, opacities, tl, width, height, eps2d, near_plane, far_plane,
+                     radius_clip, want_isect_ids, pack_colors=None, order=None, prep=None):
+    """Projection + tile lists of one call: fills `tl`, -> ((radii, means2d, depths, conics, tiles_per_gauss), the tensors
+    the projection backward needs).  The host body of _ProjectAndBin and _PrepProjectAndBin.
+    order (optional): int32 [C*N], a permutation of the flat splat ids -- the enumeration order of the bounding-box
+    intersections (include/mobgs_hip.h, enum_order).  Only the single-pass path takes it; results do not depend on it.
+    prep (internal, _PrepProjectAndBin): the 16 raw inputs of ops.PrepSplats -- the projection kernel builds the
+    per-splat state itself; means / quats / scales / opacities are then uninitialised OUTPUT buffers."""
+    means, quats, scales, viewmats, Ks, opac = map(f32c, (means, quats, scales, viewmats, Ks, opacities))
+    F = _fast.get() if SPECULATIVE_BINNING else None
+    if prep is not None and F is None:
+        raise RuntimeError("fused prep needs the C++ host fast path and speculative binning")
+    C = viewmats.shape[0]
+    # means [C,N,3] / quats [C,N,4]: every camera has its own positions / rotations of the N splats (the K sub-frames
+    # of a blurry view as ONE batch; MobgsTuning.geometry_per_camera).  Speculative path only.
+    if means.dim() == 3:
+        if not (quats.dim() == 3 and means.shape[0] == C and quats.shape[0] == C and SPECULATIVE_BINNING):
+            raise ValueError("per-camera geometry: means [C,N,3] and quats [C,N,4] with C = number of cameras")
+        call_tuning = tuning.copy(geometry_per_camera=1)
+    else:
+        call_tuning = tuning
+    if isinstance(order, str):  # COHERENT: the splats are STORED in a spatially coherent order (no indirection)
+        if order == COHERENT:
+            call_tuning = call_tuning if call_tuning is not tuning else tuning.copy()
+            call_tuning.coherent_order = 1
+        order = None
+    if call_tuning is not tuning:
+        _tuning_keepalive.append(call_tuning)
+        del _tuning_keepalive[:-8]
+    args = (means, quats, scales, viewmats, Ks, opac, width, height, eps2d, near_plane, far_plane, radius_clip)
+    if F is None and _static is not None:
+        # what is left reads the frame's counts back on the host (an event wait or a poll of the pinned sequence
+        # word) -- inside a StaticCapacity context (HIP-graph capture: no kernel runs) that would raise a capture
+        # error or spin forever (ADVICE r3).  Say what is missing instead.
+        raise RuntimeError("StaticCapacity needs the C++ host fast path and speculative binning: "
+                           f"fast path {'loaded' if _fast.get() is not None else 'NOT loaded (MOBGS_FASTPATH=0 or the build failed)'}, "
+                           f"SPECULATIVE_BINNING = {SPECULATIVE_BINNING}")
+    if SPECULATIVE_BINNING:  # allocations + the orchestrator call in C++ (csrc/fastpath.cpp), or their twin in Python
+        outs = _bin_speculative(F.project_and_bin_speculative if F is not None else _project_and_bin_speculative, tl, args,
+                                want_isect_ids, pack_colors, order, prep, call_tuning)
+    else:
+        outs = _bin_synchronous(tl, args, want_isect_ids)
+    radii, conics = outs[0], outs[3]
+    return outs, (means, quats, scales, viewmats, Ks, radii, conics)
+
+
+def _bin_speculative(callee, tl, args, want_isect_ids, pack_colors, order, prep, call_tuning):
+    """The speculative binning call: capacities, hint and stride from the workload's record (or from the StaticCapacity
+    context), a landing row for the counts, the call, and `tl` filled with buffers whose counts are still on their way
+    (tl._pending; under StaticCapacity nobody waits: the capacities stand in).  callee: F.project_and_bin_speculative or
+    its Python twin below."""
+    global _stats_slots
+    if _stats_slots is None:
+        _stats_slots = _StatsSlots()
+    means, opac, viewmats, width, height = args[0], args[5], args[3], args[6], args[7]
+    C, N = viewmats.shape[0], means.shape[-2]
+    tile_w, tile_h = math.ceil(width / TILE), math.ceil(height / TILE)
+    tl.records = None
+    pack = f32c(pack_colors) if pack_colors is not None else None
+    key = _workload_key(means.device, C, N, width, height)
+    hints = hint_record(key)
+    if _static is not None:  # fixed capacities, no read-back (StaticCapacity)
+        cap_box, cap_listed, len_hint = _static.caps(key, C, N)
+        row, row_addr = _static.take_row()  # this call's own landing row (kept for the context's lifetime)
+        slot, owner = None, _static.pool
+    else:
+        cap_box, cap_listed, len_hint = hints.caps(C, N)
+        row, slot, row_addr, owner = _stats_slots.take()
+    seq = _stats_slots.next_seq()
+    row[3] = 0
+    seg_stride = hints.stride(len_hint, C, N, C * tile_w * tile_h, cap_box)
+    fused_calls[0] += 1 if seg_stride else 0
+    if order is not None and (not seg_stride or order.numel() != C * N or order.dtype != torch.int32):
+        order = None  # (the two-pass path enumerates in splat order)
+    rc, outs, tile_order, isect_ids, tl.records = callee(
+        *args, int(_tile_culling), bool(want_isect_ids), bool(TILE_SCHEDULE), pack, cap_box, cap_listed, len_hint, row_addr,
+        seq, call_tuning.address(), stream_int(), seg_stride, order, prep if prep is not None else [])
+    radii, means2d, depths, conics, tiles_per_gauss, cum_tiles, tile_offsets, keep_scan, flatten_ids = outs
+    event = None
+    if rc == 1 and _static is None:  # counts by asynchronous copy: wait on an event (0: poll the sequence word)
+        event = torch.cuda.Event()
+        event.record()
+    tl._fill(C, N, tile_w, tile_h, cum_tiles, keep_scan, tile_offsets, tile_order, tiles_per_gauss, order)
+    tl.flatten_arena = flatten_ids
+    if _static is not None:
+        _static.rows.append((row, owner, cap_box, cap_listed, key, seg_stride))
+        tl._pending = None
+        tl._set_counts(cap_box, cap_listed, len_hint, flatten_ids, isect_ids)
+    else:
+        tl._pending = _PendingCounts(row, slot, event, (key, cap_box, cap_listed, seg_stride), (flatten_ids, isect_ids),
+                                     (means2d, radii, depths, conics, opac, tiles_per_gauss, width, height, want_isect_ids),
+                                     seq, owner)
+        hints.keep_caps(cap_box, cap_listed)
+    return radii, means2d, depths, conics, tiles_per_gauss
+
+
+def _alloc_outputs(lib, C, N, nt, dev, tile_schedule):
+    """What a binning call allocates whatever its arenas: -> (radii, means2d, depths, conics, tiles_per_gauss, cum_tiles,
+    tile_offsets, tile_order | None, stats_dev)."""
+    i32, f32 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float32, device=dev)
+    return (torch.empty(C, N, **i32), torch.empty(C, N, 2, **f32), torch.empty(C, N, **f32), torch.empty(C, N, 3, **f32),
+            torch.empty(C, N, **i32), torch.empty(C * N + 1, **i32), torch.empty(nt + 1, **i32),
+            torch.empty(lib.mobgs_tile_order_len(nt), **i32) if tile_schedule else None,
+            torch.empty(3, dtype=torch.int64, device=dev))
+
+
+def _alloc_arenas(lib, C, N, nt, dev, cap_box, cap_listed, seg_stride, want_isect_ids):
+    """... and its arenas: -> (keep_scan, scratch, flatten_ids, sort_keys, isect_ids | None)."""
+    return (torch.empty(lib.mobgs_keep_scan_len(cap_box), dtype=torch.int32, device=dev),
+            torch.empty(lib.mobgs_isect_scratch_bytes(C * N, nt, cap_box), dtype=torch.uint8, device=dev),
+            torch.empty(cap_listed, dtype=torch.int32, device=dev),
+            torch.empty(lib.mobgs_fused_seg_keys_len(nt, seg_stride) if seg_stride else cap_listed, dtype=torch.int64,
+                        device=dev),
+            torch.empty(cap_listed, dtype=torch.int64, device=dev) if want_isect_ids else None)
+
+
+def _bin_head(args, tile_culling, outs, cap_box, cap_listed, arenas):
+    """The 31 leading arguments mobgs_project_and_bin, _speculative and _fused share (C .. sort_keys)."""
+    means, quats, scales, viewmats, Ks, opac, width, height, eps2d, near_plane, far_plane, radius_clip = args
+    keep_scan, scratch, flatten_ids, sort_keys, _ = arenas
+    return (viewmats.shape[0], means.shape[-2], ptr(means), ptr(quats), ptr(scales), ptr(viewmats), ptr(Ks), ptr(opac),
+            1 if opac.dim() == 2 else 0, width, height, eps2d, near_plane, far_plane, radius_clip, tile_culling,
+            *map(ptr, outs), cap_box, ptr(keep_scan), ptr(scratch), cap_listed, ptr(flatten_ids), ptr(sort_keys))
+
+
+def _project_and_bin_speculative(means, quats, scales, viewmats, Ks, opac, width, height, eps2d, near_plane, far_plane,
+                                 radius_clip, tile_culling, want_isect_ids, tile_schedule, pack, cap_box, cap_listed, len_hint,
+                                 row_addr, seq, tuning_addr, stream_addr, seg_stride, order, prep):
+    """F.project_and_bin_speculative (csrc/fastpath.cpp) with the allocations in Python and the call through ctypes: same
+    arguments, same return tuple (rc, the nine outputs, tile_order, isect_ids, records)."""
+    if prep:
+        raise RuntimeError("fused prep needs the C++ host fast path and speculative binning")
+    lib = _lib_()
+    C, N, dev = viewmats.shape[0], means.shape[-2], means.device
+    nt = C * math.ceil(width / TILE) * math.ceil(height / TILE)
+    outs = _alloc_outputs(lib, C, N, nt, dev, tile_schedule)
+    # optional: the projection kernel also writes the compositor's packed records (colours + depth channel)
+    records = None
+    if pack is not None and lib.mobgs_raster_channels_supported(pack.shape[-1] + 1):
+        records = torch.empty(C * N, lib.mobgs_record_stride(pack.shape[-1] + 1), dtype=torch.float32, device=dev)
+    arenas = _alloc_arenas(lib, C, N, nt, dev, cap_box, cap_listed, seg_stride, want_isect_ids)
+    head = _bin_head((means, quats, scales, viewmats, Ks, opac, width, height, eps2d, near_plane, far_plane, radius_clip),
+                     tile_culling, outs, cap_box, cap_listed, arenas)
+    tail = (ptr(arenas[4]), len_hint, ctypes.c_void_p(row_addr), seq, ptr(pack) if records is not None else None,
+            1 if (records is not None and pack.dim() == 3) else 0, pack.shape[-1] if records is not None else 0, ptr(records),
+            ctypes.c_void_p(tuning_addr), ctypes.c_void_p(stream_addr))
+    if seg_stride:  # single-pass lists (see FUSED_LISTS)
+        rc = lib.mobgs_project_and_bin_fused(*head, seg_stride, ptr(order), *tail)
+    else:
+        rc = lib.mobgs_project_and_bin_speculative(*head, *tail)
+    if rc not in (0, 1):
+        check(rc, "mobgs_project_and_bin_speculative")
+    return rc, (*outs[:7], arenas[0], arenas[2]), outs[7], arenas[4], records
+
+
+def _bin_synchronous(tl, args, want_isect_ids):
+    """mobgs_project_and_bin: one C call that reads the counts back itself (SPECULATIVE_BINNING off); on MOBGS_E_CAPACITY
+    the arenas grow and the call is redone."""
+    lib = _lib_()
+    means, viewmats, width, height = args[0], args[3], args[6], args[7]
+    C, N, dev = viewmats.shape[0], means.shape[-2], means.device
+    tile_w, tile_h = math.ceil(width / TILE), math.ceil(height / TILE)
+    nt = C * tile_w * tile_h
+    outs = _alloc_outputs(lib, C, N, nt, dev, TILE_SCHEDULE)
+    stats_host = (ctypes.c_int64 * 3)()
+    tl.records = None
+    key = _workload_key(dev, C, N, width, height)
+    hints = hint_record(key)
+    cap_box, cap_listed, _ = hints.caps(C, N)
+    while True:
+        arenas = _alloc_arenas(lib, C, N, nt, dev, cap_box, cap_listed, 0, want_isect_ids)
+        rc = lib.mobgs_project_and_bin(*_bin_head(args, int(_tile_culling), outs, cap_box, cap_listed, arenas), ptr(arenas[4]),
+                                       stats_host, _tuning_with_hint(key), stream())
+        if rc != -4:  # MOBGS_E_CAPACITY: grow the arena (first call on a denser scene) and redo
+            check(rc, "mobgs_project_and_bin")
+            break
+        cap_box = max(cap_box, int(stats_host[0] * 1.25) + 1024)
+        cap_listed = max(cap_listed, int(stats_host[1] * 1.25) + 1024)
+    hints.keep_caps(cap_box, cap_listed)
+    n_box, n_isects, max_len = int(stats_host[0]), int(stats_host[1]), int(stats_host[2])
+    tl._fill(C, N, tile_w, tile_h, outs[5], arenas[0], outs[6], outs[7], outs[4])
+    tl._set_counts(n_box, n_isects, max_len, arenas[2], arenas[4])
+    last_stats.update(n_isects=n_isects, n_box=n_box, max_tile_len=max_len, n_tiles=nt)
+    return outs[:5]
 
 
 class _ProjectAndBin(torch.autograd.Function):
@@ -1304,206 +1544,19 @@ class _ProjectAndBin(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means, quats, scales, viewmats, Ks, opacities, tl, width, height, eps2d, near_plane, far_plane,
-                radius_clip, want_isect_ids, pack_colors=None, order=None, prep=None):
-        """order (optional): int32 [C*N], a permutation of the flat splat ids -- the enumeration order of the bounding-box
-        intersections (include/mobgs_hip.h, enum_order).  Only the single-pass path takes it; results do not depend on it.
-        prep (internal, _PrepProjectAndBin): the 16 raw inputs of ops.PrepSplats -- the projection kernel builds the
-        per-splat state itself; means / quats / scales / opacities are then uninitialised OUTPUT buffers."""
-        lib = _lib_()
-        means, quats, scales, viewmats, Ks, opac = map(f32c, (means, quats, scales, viewmats, Ks, opacities))
-        if prep is not None and not (SPECULATIVE_BINNING and _fast.get() is not None):
-            raise RuntimeError("fused prep needs the C++ host fast path and speculative binning")
-        C, N = viewmats.shape[0], means.shape[-2]
-        dev = means.device
-        tile_w, tile_h = math.ceil(width / TILE), math.ceil(height / TILE)
-        nt = C * tile_w * tile_h
-        # means [C,N,3] / quats [C,N,4]: every camera has its own positions / rotations of the N splats (the K sub-frames
-        # of a blurry view as ONE batch; MobgsTuning.geometry_per_camera).  Speculative path only.
-        per_cam = means.dim() == 3
-        if per_cam:
-            if not (quats.dim() == 3 and means.shape[0] == C and quats.shape[0] == C and SPECULATIVE_BINNING):
-                raise ValueError("per-camera geometry: means [C,N,3] and quats [C,N,4] with C = number of cameras")
-            call_tuning = tuning.copy(geometry_per_camera=1)
-        else:
-            call_tuning = tuning
-        if isinstance(order, str):  # COHERENT: the splats are STORED in a spatially coherent order (no indirection)
-            call_tuning = (call_tuning if call_tuning is not tuning else tuning.copy()) if order == COHERENT else call_tuning
-            if order == COHERENT:
-                call_tuning.coherent_order = 1
-            order = None
-        if call_tuning is not tuning:
-            _tuning_keepalive.append(call_tuning)
-            del _tuning_keepalive[:-8]
-        F = _fast.get() if SPECULATIVE_BINNING else None
-        if F is not None:  # allocations + the orchestrator call in C++ (csrc/fastpath.cpp)
-            global _stats_slots
-            if _stats_slots is None:
-                _stats_slots = _StatsSlots()
-            tl.records = None
-            pack = f32c(pack_colors) if pack_colors is not None else None
-            key = _workload_key(dev, C, N, width, height)
-            cap_box = max(_capacity.get(key, 0), 16 * (C * N) + 1024)
-            cap_listed = max(_cap_listed.get(key, 0), cap_box // 2)
-            len_hint = _len_hint.get(key, 0)
-            if _static is not None:  # fixed capacities, no read-back (StaticCapacity)
-                cap_box, cap_listed, len_hint = _static.caps(key, C, N)
-                row, row_addr = _static.take_row()  # this call's own landing row (kept for the context's lifetime)
-                slot, owner = None, _static.pool
-            else:
-                row, slot, row_addr, owner = _stats_slots.take()
-            seq = _stats_slots.next_seq()
-            row[3] = 0
-            seg_stride = _fused_seg_stride(len_hint, C, N, nt, cap_box, key)
-            fused_calls[0] += 1 if seg_stride else 0
-            if order is not None and (not seg_stride or order.numel() != C * N or order.dtype != torch.int32):
-                order = None  # (the two-pass path enumerates in splat order)
-            rc, outs, tile_order, isect_ids, records = F.project_and_bin_speculative(
-                means, quats, scales, viewmats, Ks, opac, width, height, eps2d, near_plane, far_plane, radius_clip,
-                int(_tile_culling), bool(want_isect_ids), bool(TILE_SCHEDULE), pack, cap_box, cap_listed,
-                len_hint, row_addr, seq, call_tuning.address(), stream_int(), seg_stride, order,
-                prep if prep is not None else [])
-            radii, means2d, depths, conics, tiles_per_gauss, cum_tiles, tile_offsets, keep_scan, flatten_ids = outs
-            tl.records = records
-            event = None
-            if rc == 1 and _static is None:  # counts by asynchronous copy: wait on an event (0: poll the sequence word)
-                event = torch.cuda.Event()
-                event.record()
-            tl.C, tl.N, tl.tile_w, tl.tile_h = C, N, tile_w, tile_h
-            tl.cum_tiles, tl.keep_scan, tl.tile_offsets, tl.tile_order = cum_tiles, keep_scan, tile_offsets, tile_order
-            tl.flatten_arena = flatten_ids
-            tl.tiles_per_gauss, tl.order = tiles_per_gauss, order
-            if _static is not None:
-                _static.rows.append((row, owner, cap_box, cap_listed, key, seg_stride))
-                tl._pending = None
-                tl._set_counts(cap_box, cap_listed, len_hint, flatten_ids, isect_ids)
-            else:
-                tl._pending = _PendingCounts(row, slot, event, (key, cap_box, cap_listed, seg_stride), (flatten_ids, isect_ids),
-                                             (means2d, radii, depths, conics, opac, tiles_per_gauss, width, height,
-                                              want_isect_ids), seq, owner)
-                _capacity[key], _cap_listed[key] = cap_box, cap_listed
-            ctx.save_for_backward(means, quats, scales, viewmats, Ks, radii, conics)
-            ctx.dims = (width, height, eps2d)
-            ctx.mark_non_differentiable(radii, tiles_per_gauss)
-            ctx.set_materialize_grads(False)
-            return radii, means2d, depths, conics, tiles_per_gauss
-        radii = torch.empty(C, N, dtype=torch.int32, device=dev)
-        means2d = torch.empty(C, N, 2, dtype=torch.float32, device=dev)
-        depths = torch.empty(C, N, dtype=torch.float32, device=dev)
-        conics = torch.empty(C, N, 3, dtype=torch.float32, device=dev)
-        tiles_per_gauss = torch.empty(C, N, dtype=torch.int32, device=dev)
-        cum_tiles = torch.empty(C * N + 1, dtype=torch.int32, device=dev)
-        tile_offsets = torch.empty(nt + 1, dtype=torch.int32, device=dev)
-        tile_order = (torch.empty(lib.mobgs_tile_order_len(nt), dtype=torch.int32, device=dev)
-                      if TILE_SCHEDULE else None)
-        if _static is not None:
-            # this branch reads the frame's counts back on the host (an event wait or a poll of the pinned sequence
-            # word) -- inside a StaticCapacity context (HIP-graph capture: no kernel runs) that would raise a capture
-            # error or spin forever (ADVICE r3).  Say what is missing instead.
-            raise RuntimeError("StaticCapacity needs the C++ host fast path and speculative binning: "
-                               f"fast path {'loaded' if _fast.get() is not None else 'NOT loaded (MOBGS_FASTPATH=0 or the build failed)'}, "
-                               f"SPECULATIVE_BINNING = {SPECULATIVE_BINNING}")
-        stats_dev = torch.empty(3, dtype=torch.int64, device=dev)
-        stats_host = (ctypes.c_int64 * 3)()
-        # optional: the projection kernel also writes the compositor's packed records (colours + depth channel)
-        tl.records = None
-        records = None
-        if pack_colors is not None and SPECULATIVE_BINNING:
-            pack_colors = f32c(pack_colors)
-            pack_ch = pack_colors.shape[-1]
-            if lib.mobgs_raster_channels_supported(pack_ch + 1):
-                records = torch.empty(C * N, lib.mobgs_record_stride(pack_ch + 1), dtype=torch.float32, device=dev)
-        key = _workload_key(dev, C, N, width, height)
-        cap_box = max(_capacity.get(key, 0), 16 * (C * N) + 1024)
-        cap_listed = max(_cap_listed.get(key, 0), cap_box // 2)
-        while True:
-            keep_scan = torch.empty(lib.mobgs_keep_scan_len(cap_box), dtype=torch.int32, device=dev)
-            scratch = torch.empty(lib.mobgs_isect_scratch_bytes(C * N, nt, cap_box), dtype=torch.uint8, device=dev)
-            flatten_ids = torch.empty(cap_listed, dtype=torch.int32, device=dev)
-            seg_stride = _fused_seg_stride(_len_hint.get(key, 0), C, N, nt, cap_box, key) if SPECULATIVE_BINNING else 0
-            sort_keys = torch.empty(lib.mobgs_fused_seg_keys_len(nt, seg_stride) if seg_stride else cap_listed,
-                                    dtype=torch.int64, device=dev)
-            isect_ids = torch.empty(cap_listed, dtype=torch.int64, device=dev) if want_isect_ids else None
-            if SPECULATIVE_BINNING:
-                if _stats_slots is None:
-                    _stats_slots = _StatsSlots()
-                row, slot, row_addr, owner = _stats_slots.take()
-                seq = _stats_slots.next_seq()
-                row[3] = 0
-                head = (C, N, ptr(means), ptr(quats), ptr(scales), ptr(viewmats), ptr(Ks), ptr(opac),
-                        1 if opac.dim() == 2 else 0, width, height, eps2d, near_plane, far_plane, radius_clip,
-                        int(_tile_culling), ptr(radii), ptr(means2d), ptr(depths), ptr(conics), ptr(tiles_per_gauss),
-                        ptr(cum_tiles), ptr(tile_offsets), ptr(tile_order), ptr(stats_dev), cap_box, ptr(keep_scan),
-                        ptr(scratch), cap_listed, ptr(flatten_ids), ptr(sort_keys))
-                if order is not None and (not seg_stride or order.numel() != C * N or order.dtype != torch.int32):
-                    order = None
-                tail = (ptr(isect_ids), _len_hint.get(key, 0), ctypes.c_void_p(row_addr), seq,
-                        ptr(pack_colors) if records is not None else None,
-                        1 if (records is not None and pack_colors.dim() == 3) else 0,
-                        pack_colors.shape[-1] if records is not None else 0, ptr(records), call_tuning.ref(), stream())
-                if seg_stride:  # single-pass lists (see FUSED_LISTS)
-                    fused_calls[0] += 1
-                    rc = lib.mobgs_project_and_bin_fused(*head, seg_stride, ptr(order), *tail)
-                else:
-                    rc = lib.mobgs_project_and_bin_speculative(*head, *tail)
-                if rc not in (0, 1):
-                    check(rc, "mobgs_project_and_bin_speculative")
-                tl.records = records
-                event = None
-                if rc == 1:  # counts by asynchronous copy: wait on an event (0: poll the sequence word)
-                    event = torch.cuda.Event()
-                    event.record()
-                tl.C, tl.N, tl.tile_w, tl.tile_h = C, N, tile_w, tile_h
-                tl.cum_tiles, tl.keep_scan, tl.tile_offsets, tl.tile_order = cum_tiles, keep_scan, tile_offsets, tile_order
-                tl.flatten_arena = flatten_ids
-                tl.tiles_per_gauss, tl.order = tiles_per_gauss, (order if seg_stride else None)
-                tl._pending = _PendingCounts(row, slot, event, (key, cap_box, cap_listed, seg_stride),
-                                             (flatten_ids, isect_ids),
-                                             (means2d, radii, depths, conics, opac, tiles_per_gauss, width, height,
-                                              want_isect_ids), seq, owner)
-                break
-            rc = lib.mobgs_project_and_bin(C, N, ptr(means), ptr(quats), ptr(scales), ptr(viewmats), ptr(Ks), ptr(opac),
-                                           1 if opac.dim() == 2 else 0, width, height, eps2d, near_plane, far_plane,
-                                           radius_clip, int(_tile_culling), ptr(radii), ptr(means2d), ptr(depths),
-                                           ptr(conics), ptr(tiles_per_gauss), ptr(cum_tiles), ptr(tile_offsets),
-                                           ptr(tile_order), ptr(stats_dev), cap_box, ptr(keep_scan), ptr(scratch), cap_listed,
-                                           ptr(flatten_ids), ptr(sort_keys), ptr(isect_ids), stats_host,
-                                           _tuning_with_hint(key), stream())
-            if rc != -4:  # MOBGS_E_CAPACITY: grow the arena (first call on a denser scene) and redo
-                check(rc, "mobgs_project_and_bin")
-                break
-            cap_box = max(cap_box, int(stats_host[0] * 1.25) + 1024)
-            cap_listed = max(cap_listed, int(stats_host[1] * 1.25) + 1024)
-        _capacity[key], _cap_listed[key] = cap_box, cap_listed
-        if not tl.pending:
-            n_box, n_isects, max_len = int(stats_host[0]), int(stats_host[1]), int(stats_host[2])
-            tl.C, tl.N, tl.tile_w, tl.tile_h = C, N, tile_w, tile_h
-            tl.cum_tiles, tl.keep_scan, tl.tile_offsets, tl.tile_order = cum_tiles, keep_scan, tile_offsets, tile_order
-            tl.tiles_per_gauss = tiles_per_gauss
-            tl._set_counts(n_box, n_isects, max_len, flatten_ids, isect_ids)
-            last_stats.update(n_isects=n_isects, n_box=n_box, max_tile_len=max_len, n_tiles=nt)
-        ctx.save_for_backward(means, quats, scales, viewmats, Ks, radii, conics)
+                radius_clip, want_isect_ids, pack_colors=None, order=None):
+        outs, saved = _project_and_bin(means, quats, scales, viewmats, Ks, opacities, tl, width, height, eps2d, near_plane,
+                                       far_plane, radius_clip, want_isect_ids, pack_colors, order)
+        ctx.save_for_backward(*saved)
         ctx.dims = (width, height, eps2d)
-        ctx.mark_non_differentiable(radii, tiles_per_gauss)
+        ctx.mark_non_differentiable(outs[0], outs[4])
         ctx.set_materialize_grads(False)  # no zero tensors for the outputs nothing back-propagates through
-        return radii, means2d, depths, conics, tiles_per_gauss
+        return outs
 
     @staticmethod
     def backward(ctx, _v_radii, v_means2d, v_depths, v_conics, _v_tpg):
         return (*_project_bwd(ctx.saved_tensors, ctx.dims, v_means2d, v_depths, v_conics), None, None, None, None, None, None,
                 None, None, None, None, None, None)
-
-
-class _CtxShim:
-    """What _ProjectAndBin.forward asks of its ctx, for callers that are not its autograd node."""
-
-    def save_for_backward(self, *ts):
-        self.saved_tensors = ts
-
-    def mark_non_differentiable(self, *ts):
-        pass
-
-    def set_materialize_grads(self, v):
-        pass
 
 
 # _PrepProjectAndBin.backward as one launch (A/B: MOBGS_FUSE_PREP_BWD=0 runs the projection backward and the prep
@@ -1534,12 +1587,11 @@ class _PrepProjectAndBin(torch.autograd.Function):
         times_c, d_trbf_c = prep[0], prep[15]
         Ns, Nd = s_xyz.shape[0], d_control.shape[0]
         means, quats, scales, opac, cols = _fast.get().prep_state_buffers(Ns + Nd, s_xyz)
-        shim = _CtxShim()
-        radii, means2d, depths, conics, tiles_per_gauss = _ProjectAndBin.forward(
-            shim, means, quats, scales, viewmats, Ks, opac, tl, width, height, eps2d, near_plane, far_plane, radius_clip,
-            False, None, order, prep)
-        ctx.save_for_backward(*shim.saved_tensors, times_c, d_ncp_c, d_trbf_c, opac)
-        ctx.dims = shim.dims
+        (radii, means2d, depths, conics, tiles_per_gauss), saved = _project_and_bin(
+            means, quats, scales, viewmats, Ks, opac, tl, width, height, eps2d, near_plane, far_plane, radius_clip, False,
+            None, order, prep)
+        ctx.save_for_backward(*saved, times_c, d_ncp_c, d_trbf_c, opac)
+        ctx.dims = (width, height, eps2d)
         ctx.sizes = (Ns, Nd)
         ctx.leaf_inputs = leaf_inputs
         ctx.mark_non_differentiable(radii, tiles_per_gauss)

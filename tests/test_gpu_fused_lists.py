@@ -29,8 +29,9 @@ def _project(s, dev, W, H, fused, hint=None, C=1, order=None):
         Ks = t["Ks"].expand(C, 3, 3).contiguous()
         if hint is not None:
             key = R._workload_key(dev, C, t["means"].shape[0], W, H)
-            R._len_hint[key] = hint
-            R._seg_sticky.pop(key, None)   # (the stride is sticky per workload: a test that dictates the hint starts afresh)
+            rec = R.hint_record(key)
+            rec.longest = hint
+            rec.seg_stride = 0   # (the stride is sticky per workload: a test that dictates the hint starts afresh)
         before = R.fused_calls[0]
         sp = R.SharedProjection(t["means"], t["quats"], t["scales"], t["opacities"], vm, Ks, W, H, want_isect_ids=True,
                                 order=order)

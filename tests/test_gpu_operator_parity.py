@@ -452,11 +452,10 @@ def test_long_tile_lists_sort_exactly_on_a_speculative_second_frame(hip_device, 
     try:
         for spec in (True, False):
             rendering.SPECULATIVE_BINNING = spec
-            for table in (rendering._capacity, rendering._cap_listed, rendering._len_hint, rendering._seg_sticky):
-                table.clear()
+            rendering.forget_hints()
             for frame in range(2 if spec else 1):
                 if frame:  # what the first frame left selects the arm of the second
-                    assert rendering._len_hint.get(key, 0) > arm, rendering._len_hint
+                    assert rendering.hint_record(key).longest > arm, rendering.hint_record(key).longest
                 before = (rendering.list_rebuilds[0], rendering.fused_calls[0])
                 _, _, meta = rasterization(d["means"], d["quats"], d["scales"], d["opacities"], d["colors"], d["viewmats"],
                                            d["Ks"], w, h, packed=False)
@@ -531,9 +530,7 @@ def test_speculative_arena_overflow_is_transparent(hip_device):
     res = {}
     for spec in (True, False):
         rendering.SPECULATIVE_BINNING = spec
-        rendering._capacity.clear()
-        rendering._cap_listed.clear()
-        rendering._len_hint.clear()
+        rendering.forget_hints()
         try:
             t = {k: v.to(hip_device).clone().requires_grad_(k in names) for k, v in s.items()}
             sp = rendering.SharedProjection(t["means"], t["quats"], t["scales"], t["opacities"], t["viewmats"],
