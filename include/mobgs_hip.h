@@ -147,7 +147,7 @@ int mobgs_cotangent_probe(int n_arrays, const float* const* arrays, const size_t
  * points changes (round 4 inserted `records` into mobgs_raster_bwd_reduce and changed the gradient-slot format without
  * one: a stale host extension would have passed shifted pointers).  Bindings compare it with the MOBGS_ABI_VERSION
  * they were built against and refuse to run on a mismatch (mobgs_amd/_lib.py, csrc/fastpath.cpp). */
-#define MOBGS_ABI_VERSION 13
+#define MOBGS_ABI_VERSION 14
 int mobgs_abi_version(void);
 /* Text of the last error raised on the calling thread ("" if none). */
 const char* mobgs_last_error(void);
@@ -935,6 +935,46 @@ int mobgs_seed_trajectories(int N, int T, int M, int V, int H, int W, const floa
 size_t mobgs_exposure_scratch_bytes(int64_t n);
 int mobgs_exposure_estimate(int64_t n, const float* cam_flow, const float* latent_flow, float q, float scale,
                             float* slot, int32_t* stats, void* scratch, void* stream);
+
+/* ---- K21: depth, entropy and sparsity terms of the training loss, and the PSNR next to them ------------------------
+ * /root/reference/train.py:651-655 with utils/loss_utils.py:233-239 (l1_loss, mask=None), :264-276 (entropy_loss),
+ * :285-295 (sparsity_loss), and train.py:622 with utils/image_utils.py:17-38 (psnr, mask=None), on the caller's stream,
+ * without a float atomic (csrc/regterms.hip: per-workgroup partial rows, a one-workgroup finishing launch).  All maps are
+ * flattened fp32, 4-byte aligned (16-byte alignment is NOT needed: heads and tails are handled), at most 2^40 elements.
+ * Every term is evaluated in fp32 as written below; the terms are ADDED in float64 and each sum is rounded to fp32 once:
+ *   S_d = sum |depth - gt_depth|                                        depth_loss = S_d / n_d
+ *   S_e = sum [a log(a + eps) + (1 - a) log(1 - a + eps)], eps = 1e-6   entropy    = -S_e
+ *   S_s = sum a a                                                       sparsity   = S_s
+ *   mask_loss = w_e entropy + w_s sparsity;   reg_loss = (0 + w_d depth_loss) + mask_loss
+ *   psnr[b]   = 20 log10(1 / sqrt(sum (image[b] - gt_image[b])^2 / (3 H W)))      (fp32 squares; the rest in float64,
+ *                                                                                   rounded to fp32 at the end)
+ * Nothing is clamped: an alpha outside [-eps, 1 + eps] gives NaN, as in the reference.
+ * terms: MOBGS_REG_ENTROPY | MOBGS_REG_SPARSITY, the alpha terms that are evaluated; one that is not contributes a sum
+ *   of 0 (and no NaN), forward and backward.
+ * fwd: depth and gt_depth [n_d] may both be NULL (n_d = 0: depth_loss = 0); alpha [n_a] may be NULL (n_a = 0, terms = 0);
+ *   not both.  image and gt_image [B,3,H,W] may both be NULL (B = 0; H, W ignored), else 1 <= B <= MOBGS_REG_MAX_IMAGES.
+ *   partial: scratch, [mobgs_reg_terms_blocks(max(n_d, n_a, 3 H W)), 3 + B] doubles, contents irrelevant on entry.
+ *   out [5 + B] (device) = {reg_loss, depth_loss, mask_loss, entropy, sparsity, psnr[0..B)}.  Two launches; the result is
+ *   bit-identical from run to run.  The inputs are only read.
+ * bwd: v_loss = device scalar, d L / d reg_loss.  Recomputed from the inputs (forward saves nothing):
+ *   v_depth [n_d] = v_loss w_d sgn(depth - gt_depth) / n_d                                  (sgn(0) = 0)
+ *   v_alpha [n_a] = v_loss (-w_e [log(a + eps) + a / (a + eps) - log(1 - a + eps) - (1 - a) / (1 - a + eps)] + w_s 2 a)
+ *   Either may be NULL (that side is not computed; not both); what is given is fully written.  One launch.
+ * mobgs_reg_terms_blocks(n): workgroups of the streaming launch for a largest map of n elements (a host computation:
+ *   no device is touched); 0 for an n outside [1, 2^40].
+ * Refused with MOBGS_E_INVALID before any launch: a size <= 0 with a non-NULL map or != 0 with a NULL one, one of a pair
+ * of maps without the other, no map at all, terms that do not match alpha, images without B, H, W >= 1, a gradient for a
+ * map that is not given, a NULL partial / out / v_loss, a misaligned pointer. */
+#define MOBGS_REG_ENTROPY 1
+#define MOBGS_REG_SPARSITY 2
+#define MOBGS_REG_MAX_IMAGES 64
+int mobgs_reg_terms_blocks(int64_t n);
+int mobgs_reg_terms_fwd(int64_t n_d, const float* depth, const float* gt_depth, int64_t n_a, const float* alpha,
+                        int terms, float w_d, float w_e, float w_s, int B, int H, int W, const float* image,
+                        const float* gt_image, double* partial, float* out, void* stream);
+int mobgs_reg_terms_bwd(int64_t n_d, const float* depth, const float* gt_depth, int64_t n_a, const float* alpha,
+                        int terms, float w_d, float w_e, float w_s, const float* v_loss, float* v_depth,
+                        float* v_alpha, void* stream);
 
 #ifdef __cplusplus
 }

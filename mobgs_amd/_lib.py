@@ -52,7 +52,7 @@ class MobgsPrepInputs(ctypes.Structure):
 
 
 P = c_void_p
-ABI_VERSION = 13  # include/mobgs_hip.h MOBGS_ABI_VERSION
+ABI_VERSION = 14  # include/mobgs_hip.h MOBGS_ABI_VERSION
 _SIGS = {
     "mobgs_version": (c_char_p, []),
     "mobgs_abi_version": (c_int, []),
@@ -160,6 +160,10 @@ _SIGS = {
     "mobgs_seed_trajectories": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P]),
     "mobgs_exposure_scratch_bytes": (c_size_t, [c_int64]),
     "mobgs_exposure_estimate": (c_int, [c_int64, P, P, c_float, c_float, P, P, P, P]),
+    "mobgs_reg_terms_blocks": (c_int, [c_int64]),
+    "mobgs_reg_terms_fwd": (c_int, [c_int64, P, P, c_int64, P, c_int, c_float, c_float, c_float, c_int, c_int, c_int, P, P,
+                                    P, P, P]),
+    "mobgs_reg_terms_bwd": (c_int, [c_int64, P, P, c_int64, P, c_int, c_float, c_float, c_float, P, P, P, P]),
 }
 # entry points added by later translation units (bound if present in the header AND the library)
 _OPTIONAL_SIGS = {}

@@ -13,7 +13,7 @@ from pathlib import Path
 CSRC = Path(__file__).resolve().parent / "csrc"
 # MOBGS_LIB: load another build of the same library instead (A/B timing of kernel variants on one GPU box)
 LIB_PATH = Path(os.environ["MOBGS_LIB"]).resolve() if os.environ.get("MOBGS_LIB") else CSRC / "libmobgs_hip.so"
-SOURCES = ["project.hip", "isect.hip", "raster.hip", "raster_bwd_mfma.hip", "raster_layers.hip", "pipeline.hip", "prep.hip", "decoder.hip", "deform.hip", "deform_bwd.hip", "hexplane_bwd.hip", "blce.hip", "loss.hip", "flowloss.hip", "densify.hip", "normals.hip", "knn.hip", "control_prune.hip", "scene_seed.hip", "exposure.hip"]
+SOURCES = ["project.hip", "isect.hip", "raster.hip", "raster_bwd_mfma.hip", "raster_layers.hip", "pipeline.hip", "prep.hip", "decoder.hip", "deform.hip", "deform_bwd.hip", "hexplane_bwd.hip", "blce.hip", "loss.hip", "flowloss.hip", "densify.hip", "normals.hip", "knn.hip", "control_prune.hip", "scene_seed.hip", "exposure.hip", "regterms.hip"]
 ARCH = "gfx950"
 # host fast path (csrc/fastpath.cpp): a plain C++ torch extension, no device code, no link against libmobgs_hip.so
 FAST_SRC = CSRC / "fastpath.cpp"
@@ -40,6 +40,9 @@ EXTRA_FLAGS["scene_seed.hip"] = EXTRA_FLAGS.get("scene_seed.hip", []) + ["-ffp-c
 # exposure.hip: the same for the flow magnitudes sqrt(x x + y y) and the quantile's interpolation a + w (b - a): evaluated
 # as written they are bit-equal with torch on the CPU, and the selected order statistics are exact (csrc/exposure.hip).
 EXTRA_FLAGS["exposure.hip"] = EXTRA_FLAGS.get("exposure.hip", []) + ["-ffp-contract=off"]
+# regterms.hip: the same for the loss terms a log(a + eps) + (1 - a) log(1 - a + eps), w_e E + w_s S and the depth
+# gradient (g w_d) / n: each operation is rounded as the reference's torch statements round it (csrc/regterms.hip).
+EXTRA_FLAGS["regterms.hip"] = EXTRA_FLAGS.get("regterms.hip", []) + ["-ffp-contract=off"]
 # raster.hip: top-down pre-RA machine scheduling.  The compositing loops are long straight-line blocks bound by VALU
 # issue; of ten scheduler settings swept in round 4 (scripts/ab/build_variant_raster.sh + kernel_ab2.sh, three A/B
 # repetitions on one box) this is the only one outside the noise: raster_bwd<10> 512 -> 506 us, raster_fwd_blocks<10>

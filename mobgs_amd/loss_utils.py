@@ -10,8 +10,13 @@ in every reference call.  The masked L1 exists in the reference only inside the 
 (train.py:651-671): `flow_warp_loss` below is that whole block -- coordinate normalisation, both grid_sample warps and
 both masked L1 terms -- as one forward and one backward kernel (csrc/flowloss.hip), differentiable in all six inputs.
 `exposure_ratio` is the statistic of train.py:482-491 on two flow maps (csrc/exposure.hip): no sort, no read-back.
+`entropy_loss` and `sparsity_loss` (utils/loss_utils.py:264-295) and `regularisation_terms` -- the depth, entropy and
+sparsity terms of train.py:651-655 with the PSNR of :622 next to them -- are one forward launch pair and one backward
+launch of csrc/regterms.hip.
 """
 from __future__ import annotations
+
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -212,3 +217,111 @@ def exposure_ratio(cam_flow, latent_flow, q=0.01, scale=1.0, out=None):
     if out is not None:   # written through a raw pointer: move Tensor._version as an in-place torch op would have
         torch.autograd.graph.increment_version(out)
     return value, stats
+
+
+REG_ENTROPY, REG_SPARSITY = 1, 2   # include/mobgs_hip.h MOBGS_REG_ENTROPY / MOBGS_REG_SPARSITY
+
+
+def _numel_or_zero(t):
+    return 0 if t is None else t.numel()
+
+
+class _RegTerms(torch.autograd.Function):
+    """(depth | None, gt_depth | None, alpha | None, image | None, gt_image | None, terms, w_d, w_e, w_s) -> (reg_loss,
+    rest): reg_loss differentiable in depth and alpha, rest = {depth_loss, mask_loss, entropy, sparsity, psnr[B]} without
+    a graph (include/mobgs_hip.h K21).  Backward recomputes from the inputs."""
+
+    @staticmethod
+    def forward(ctx, depth, gt_depth, alpha, image, gt_image, terms, w_d, w_e, w_s):
+        lib = _lib.load()
+        depth, gt_depth, alpha, image, gt_image = (None if t is None else f32c(t)
+                                                   for t in (depth, gt_depth, alpha, image, gt_image))
+        B, H, W = (image.shape[0], image.shape[2], image.shape[3]) if image is not None else (0, 0, 0)
+        n_d, n_a = _numel_or_zero(depth), _numel_or_zero(alpha)
+        dev = (depth if depth is not None else alpha).device
+        nb = lib.mobgs_reg_terms_blocks(max(n_d, n_a, 3 * H * W))
+        partial = torch.empty(nb, 3 + B, dtype=torch.float64, device=dev)
+        out = torch.empty(5 + B, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            check(lib.mobgs_reg_terms_fwd(n_d, ptr(depth), ptr(gt_depth), n_a, ptr(alpha), terms, w_d, w_e, w_s, B, H, W,
+                                          ptr(image), ptr(gt_image), ptr(partial), ptr(out), stream()),
+                  "mobgs_reg_terms_fwd")
+        ctx.save_for_backward(depth, gt_depth, alpha)
+        ctx.scalars = (terms, w_d, w_e, w_s)
+        rest = out[1:]
+        ctx.mark_non_differentiable(rest)
+        return out[0], rest
+
+    @staticmethod
+    def backward(ctx, v_reg, _v_rest):
+        lib = _lib.load()
+        depth, gt_depth, alpha = ctx.saved_tensors
+        terms, w_d, w_e, w_s = ctx.scalars
+        v = f32c(v_reg).reshape(1)
+        v_depth = torch.empty_like(depth) if depth is not None and ctx.needs_input_grad[0] else None
+        v_alpha = torch.empty_like(alpha) if alpha is not None and ctx.needs_input_grad[2] else None
+        with torch.cuda.device(v.device):
+            check(lib.mobgs_reg_terms_bwd(_numel_or_zero(depth), ptr(depth), ptr(gt_depth), _numel_or_zero(alpha),
+                                          ptr(alpha), terms, w_d, w_e, w_s, ptr(v), ptr(v_depth), ptr(v_alpha),
+                                          stream()), "mobgs_reg_terms_bwd")
+        return v_depth, None, v_alpha, None, None, None, None, None, None
+
+
+def _reg_map(what, name, t):
+    if not torch.is_tensor(t) or t.numel() == 0:
+        raise ValueError(f"{what}: {name} must be a non-empty tensor")
+    if not t.is_cuda:
+        raise RuntimeError(f"{what}: tensors must live on a HIP device (device='cuda'); there is no CPU path")
+    return t
+
+
+def entropy_loss(alpha):
+    """utils/loss_utils.py:264-276: -sum(alpha log(alpha + 1e-6) + (1 - alpha) log(1 - alpha + 1e-6)) over a map of any
+    shape, differentiable in alpha; NaN for a value outside [-1e-6, 1 + 1e-6], as the reference (nothing is clamped)."""
+    _reg_map("entropy_loss", "alpha", alpha)
+    return _RegTerms.apply(None, None, alpha, None, None, REG_ENTROPY, 0.0, 1.0, 0.0)[0]
+
+
+def sparsity_loss(alpha):
+    """utils/loss_utils.py:285-295: sum(alpha ** 2) over a map of any shape, differentiable in alpha."""
+    _reg_map("sparsity_loss", "alpha", alpha)
+    return _RegTerms.apply(None, None, alpha, None, None, REG_SPARSITY, 0.0, 0.0, 1.0)[0]
+
+
+class RegularisationTerms(NamedTuple):
+    reg_loss: torch.Tensor               # differentiable in depth and d_alpha
+    depth_loss: torch.Tensor             # the three below: device tensors without a graph
+    mask_loss: torch.Tensor
+    psnr: Optional[torch.Tensor]         # [B,1], or None without images
+
+
+def regularisation_terms(depth, gt_depth, d_alpha, *, depth_weight=0.2, entropy_weight=1e-7, sparsity_weight=1e-7,
+                         image=None, gt_image=None):
+    """/root/reference/train.py:651-655, and :622 when the images are given, as ONE autograd node:
+
+        depth_loss = l1_loss(depth, gt_depth);  reg_loss = 0 + depth_weight * depth_loss
+        mask_loss  = entropy_weight * entropy_loss(d_alpha) + sparsity_weight * sparsity_loss(d_alpha)
+        reg_loss  += mask_loss
+        psnr       = psnr(image, gt_image)                     # [B,1]: per image, as utils/image_utils.py:30-31
+
+    depth and gt_depth share a shape; d_alpha has any shape; image and gt_image are [B,3,H,W].  One forward launch pair,
+    one backward launch; no synchronisation, no read-back, no allocation whose size depends on the data (it can be
+    recorded into a graph).  Gradients flow to depth and d_alpha; gt_depth is a constant, the images are only measured."""
+    what = "regularisation_terms"
+    for name, t in (("depth", depth), ("gt_depth", gt_depth), ("d_alpha", d_alpha)):
+        _reg_map(what, name, t)
+    if depth.shape != gt_depth.shape:
+        raise ValueError(f"{what}: depth {tuple(depth.shape)} and gt_depth {tuple(gt_depth.shape)} differ in shape")
+    if gt_depth.requires_grad:
+        raise NotImplementedError("mobgs_amd.loss_utils: only depth and d_alpha receive a gradient, gt_depth does not")
+    if (image is None) != (gt_image is None):
+        raise ValueError(f"{what}: image and gt_image go together")
+    if image is not None:
+        for name, t in (("image", image), ("gt_image", gt_image)):
+            _reg_map(what, name, t)
+        if image.dim() != 4 or image.shape[1] != 3 or image.shape != gt_image.shape:
+            raise ValueError(f"{what}: image and gt_image must both be [B,3,H,W]")
+        image, gt_image = image.detach(), gt_image.detach()
+    reg, rest = _RegTerms.apply(depth, gt_depth, d_alpha, image, gt_image, REG_ENTROPY | REG_SPARSITY,
+                                float(depth_weight), float(entropy_weight), float(sparsity_weight))
+    return RegularisationTerms(reg, rest[0], rest[1], rest[4:].reshape(-1, 1) if image is not None else None)
