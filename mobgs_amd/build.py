@@ -43,6 +43,10 @@ EXTRA_FLAGS["exposure.hip"] = EXTRA_FLAGS.get("exposure.hip", []) + ["-ffp-contr
 # regterms.hip: the same for the loss terms a log(a + eps) + (1 - a) log(1 - a + eps), w_e E + w_s S and the depth
 # gradient (g w_d) / n: each operation is rounded as the reference's torch statements round it (csrc/regterms.hip).
 EXTRA_FLAGS["regterms.hip"] = EXTRA_FLAGS.get("regterms.hip", []) + ["-ffp-contract=off"]
+# normals.hip: the same for the back-projected differences d_r z_r - d_l z_l: fused into fma(d_r, z_r, -(d_l z_l)) the
+# difference of two equal products is one product's rounding error, not 0, and the normals of a flat patch or of a depth
+# hole get components of 1e-8 where the reference's are exactly 0 (tests/test_gpu_loss_kernels.py).  15 us kernels.
+EXTRA_FLAGS["normals.hip"] = EXTRA_FLAGS.get("normals.hip", []) + ["-ffp-contract=off"]
 # raster.hip: top-down pre-RA machine scheduling.  The compositing loops are long straight-line blocks bound by VALU
 # issue; of ten scheduler settings swept in round 4 (scripts/ab/build_variant_raster.sh + kernel_ab2.sh, three A/B
 # repetitions on one box) this is the only one outside the noise: raster_bwd<10> 512 -> 506 us, raster_fwd_blocks<10>

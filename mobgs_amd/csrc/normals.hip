@@ -30,6 +30,9 @@ __device__ __forceinline__ void centre_vectors(const NormalCam& c, const float* 
     view_dir(c, i + 1, j, db);
     const float zr = z[(size_t)i * W + j + 1], zl = z[(size_t)i * W + j - 1];
     const float zt = z[(size_t)(i - 1) * W + j], zb = z[(size_t)(i + 1) * W + j];
+    // built without FMA contraction (build.py): contracted into fma(a, b, -(c d)) the difference of two equal products is
+    // the rounding error of one of them instead of 0, and a flat patch or a hole (equal depths along a row: l2r =
+    // (x, 0, 0) exactly) gets normals with components of 1e-8 where the reference has exact zeros
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         l2r[k] = dr[k] * zr - dl[k] * zl;
