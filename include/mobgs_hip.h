@@ -147,7 +147,7 @@ int mobgs_cotangent_probe(int n_arrays, const float* const* arrays, const size_t
  * points changes (round 4 inserted `records` into mobgs_raster_bwd_reduce and changed the gradient-slot format without
  * one: a stale host extension would have passed shifted pointers).  Bindings compare it with the MOBGS_ABI_VERSION
  * they were built against and refuse to run on a mismatch (mobgs_amd/_lib.py, csrc/fastpath.cpp). */
-#define MOBGS_ABI_VERSION 14
+#define MOBGS_ABI_VERSION 15
 int mobgs_abi_version(void);
 /* Text of the last error raised on the calling thread ("" if none). */
 const char* mobgs_last_error(void);
@@ -168,20 +168,15 @@ int mobgs_project_fwd(int C, int N, const float* means, const float* quats, cons
 /* ---- K2: projection backward (replaces gsplat fully_fused_projection bwd, incl. v_viewmats) ------------
  * v_viewmats_partial: scratch [ceil(C*N/256), 16] floats; v_viewmats [C,4,4] is fully written.
  * v_means/v_quats/v_scales are [N,3]/[N,4]/[N,3], summed over cameras, fully written by the call.
+ * geometry_per_camera (see MobgsTuning) = 1: means / v_means [C,N,3] and quats / v_quats [C,N,4] (every camera's rows
+ * written once, nothing summed over cameras), v_scales [N,3] summed over cameras.
  * Any of v_means2d / v_depths / v_conics may be NULL (treated as zeros). */
 size_t mobgs_project_bwd_scratch_floats(int C, int N);
-int mobgs_project_bwd(int C, int N, const float* means, const float* quats, const float* scales,
-                      const float* viewmats, const float* Ks, int width, int height, float eps2d,
-                      const int32_t* radii, const float* conics, const float* v_means2d,
+int mobgs_project_bwd(int C, int N, int geometry_per_camera, const float* means, const float* quats,
+                      const float* scales, const float* viewmats, const float* Ks, int width, int height,
+                      float eps2d, const int32_t* radii, const float* conics, const float* v_means2d,
                       const float* v_depths, const float* v_conics, float* v_means, float* v_quats,
                       float* v_scales, float* v_viewmats, float* v_viewmats_partial, void* stream);
-/* The same with geometry_per_camera (see MobgsTuning): means / v_means [C,N,3] and quats / v_quats [C,N,4] when the
- * flag is 1 (every camera's rows written once, nothing summed over cameras), v_scales [N,3] summed over cameras. */
-int mobgs_project_bwd_ex(int C, int N, int geometry_per_camera, const float* means, const float* quats,
-                         const float* scales, const float* viewmats, const float* Ks, int width, int height,
-                         float eps2d, const int32_t* radii, const float* conics, const float* v_means2d,
-                         const float* v_depths, const float* v_conics, float* v_means, float* v_quats,
-                         float* v_scales, float* v_viewmats, float* v_viewmats_partial, void* stream);
 /* Projection backward + prep backward of ONE camera in one launch (round 5; the backward half of
  * mobgs_prep_project_and_bin_fused): what mobgs_project_bwd would store as v_means / v_quats / v_scales stays in the
  * thread's registers and goes through the arithmetic of mobgs_prep_bwd (bit for bit) to the 13 leaf gradients.
@@ -189,10 +184,15 @@ int mobgs_project_bwd_ex(int C, int N, int geometry_per_camera, const float* mea
  * v_opacities / v_colors (may be NULL): as mobgs_prep_bwd.  accumulate: as mobgs_prep_bwd.  v_viewmats [4,4] is fully
  * written (scratch v_viewmats_partial: mobgs_project_bwd_scratch_floats(1, N) floats); v_viewmats = NULL: the pose needs no
  * gradient (the training loop never optimises it; eval.py's test-time pose optimisation does) -- the per-workgroup partial
- * rows and the reduction launch are skipped.  float32 leaves only. */
+ * rows and the reduction launch are skipped.  float32 leaves only.
+ * MobgsLeafGrads: the 13 leaf-gradient buffers (device pointers; a host struct, read before the call returns).  s_xyz and
+ * d_control are float32; the eleven attribute members are float32 -- or IEEE binary16 where mobgs_prep_bwd is called with
+ * grad_half = 1. */
 typedef struct MobgsLeafGrads {
-    float *s_xyz, *s_scaling, *s_rotation, *s_opacity, *s_fdc, *s_ft, *d_control, *d_scaling, *d_rotation, *d_omega,
-        *d_opacity, *d_fdc, *d_ft;
+    float* s_xyz;
+    void *s_scaling, *s_rotation, *s_opacity, *s_fdc, *s_ft;
+    float* d_control;
+    void *d_scaling, *d_rotation, *d_omega, *d_opacity, *d_fdc, *d_ft;
 } MobgsLeafGrads;
 int mobgs_project_prep_bwd_fused(int N, const float* means, const float* quats, const float* scales,
                                  const float* viewmats, const float* Ks, int width, int height, float eps2d,
@@ -354,14 +354,19 @@ int mobgs_project_and_bin_fused(int C, int N, const float* means, const float* q
  * by one launch and read back by the next.  One camera (C = 1), float attributes, N = prep->Ns + prep->Nd.
  * `means` [N,3], `quats` [N,4], `scales` [N,3] and `opacities` [N] are OUTPUTS here (the backward pass and the caller's
  * result dict need them); the 9 colour features only exist inside `pack_records` (stride mobgs_record_stride(10): the
- * depth is the tenth channel), which is required.  All pointers in the struct are device pointers. */
+ * depth is the tenth channel), which is required.
+ * MobgsPrepInputs: the raw parameters of the two sets (see K8, mobgs_prep_fwd).  A host struct, read before the call
+ * returns; all pointers in it are device pointers.  The eleven attribute members are float32 -- or IEEE binary16 where
+ * mobgs_prep_fwd is called with attr_half = 1 (this entry point reads them as float32). */
 typedef struct MobgsPrepInputs {
     int32_t Ns, Nd;
-    const float* times;      /* [2]: {t_feat, t_curve}, as mobgs_prep_fwd */
-    const float *s_xyz, *s_scaling, *s_rotation, *s_opacity, *s_fdc, *s_ft;
+    const float* times;      /* [K,2]: {t_feat, t_curve} per instant (K = 1 here) */
+    const float* s_xyz;
+    const void *s_scaling, *s_rotation, *s_opacity, *s_fdc, *s_ft;
     const float* d_control;
     const int64_t* d_ncp;
-    const float *d_scaling, *d_rotation, *d_omega, *d_opacity, *d_fdc, *d_ft, *d_trbf;
+    const void *d_scaling, *d_rotation, *d_omega, *d_opacity, *d_fdc, *d_ft;
+    const float* d_trbf;
 } MobgsPrepInputs;
 int mobgs_prep_project_and_bin_fused(const MobgsPrepInputs* prep, float* means, float* quats, float* scales,
                                      const float* viewmats, const float* Ks, float* opacities, int width, int height,
@@ -442,7 +447,7 @@ int mobgs_raster_bwd(int C, int N, int channels, int has_extra, int width, int h
  * [helper_model.py:19-28 backward -> gsplat rasterize_to_pixels backward]): 9 feature channels + the depth channel,
  * pinhole rays.  The kernel reads the decoder's inputs -- `render` [C,H,W,10] (the composited image mobgs_raster_fwd[_decode]
  * wrote), `render_alphas`, the cotangents v_rgb [C,3,H,W] of the decoded colour and v_depth [C,H,W] (NULL = none) of the
- * expected depth -- and forms the cotangent of the composited image in registers (bit for bit what mobgs_decoder_bwd
+ * expected depth -- and forms the cotangent of the composited image in registers (bit for bit what mobgs_decoder_bwd_many
  * would have written to v_feat_hw / v_alphas; v_alphas here = an ADDITIONAL cotangent of the alpha output, NULL = none).
  * The weight and pose gradients leave the kernel as ONE row of 102 sums per tile in w_partial (scratch of
  * mobgs_raster_bwd_decode_scratch_floats(C, width, height) floats, contents irrelevant on entry: the rows, then chunk sums
@@ -450,7 +455,7 @@ int mobgs_raster_bwd(int C, int N, int channels, int has_extra, int width, int h
  * (deterministic) into g_w1 [6,12], g_w2 [3,6] (accumulate_wgrad != 0: added to what is there; sums over all images) and
  * g_c2w [C, g_c2w_floats = 12 | 16] (NULL = not wanted; per image, fully written).  Only where the quadrant kernel is the
  * selection ((mobgs_raster_path(10, 0, n_tiles, tuning) & 3) == 0), else MOBGS_E_UNSUPPORTED: callers then run
- * mobgs_decoder_bwd + mobgs_raster_bwd.  Everything else as mobgs_raster_bwd (channels = 9, has_extra = 1). */
+ * mobgs_decoder_bwd_many + mobgs_raster_bwd.  Everything else as mobgs_raster_bwd (channels = 9, has_extra = 1). */
 int mobgs_raster_bwd_decode(int C, int N, int width, int height, const float* records, const float* backgrounds,
                             const int32_t* radii, const int32_t* cum_tiles, const int32_t* keep_scan,
                             const int32_t* tile_offsets, const int32_t* tile_order, const int32_t* flatten_ids,
@@ -595,77 +600,31 @@ int mobgs_raster_path(int total_channels, int class_filter, int n_tiles, const M
  * /root/reference/gaussian_renderer/__init__.py:23-56 (interpolate_cubic_hermite), :93-125 (time offset,
  * rotation, colour features), :181-185 (cat static|dynamic); scene/gaussian_model.py:209-254 (activations).
  * Rows [0,Ns) of every output are the static splats, [Ns,Ns+Nd) the dynamic ones.
- * times (device, 2 floats): {t_feat = time + delta/max_time, t_curve = clamp(t_feat,0,1)}.
- * static leaves : xyz [Ns,3], scaling [Ns,3] (log), rotation [Ns,4], opacity [Ns] (logit), f_dc [Ns,6], f_t [Ns,3]
- * dynamic leaves: control [Nd,12,3] (x100 units), ncp [Nd] int64 active knots (4..12), scaling, rotation,
- *                 omega [Nd,4], opacity, f_dc, f_t, trbf [Nd]
- * out: means [N,3], quats [N,4] (un-normalised; the projection normalises), scales [N,3], opacities [N],
- *      colors [N,9]. */
-int mobgs_prep_fwd(int Ns, int Nd, const float* times, const float* s_xyz, const float* s_scaling,
-                   const float* s_rotation, const float* s_opacity, const float* s_fdc, const float* s_ft,
-                   const float* d_control, const int64_t* d_ncp, const float* d_scaling,
-                   const float* d_rotation, const float* d_omega, const float* d_opacity, const float* d_fdc,
-                   const float* d_ft, const float* d_trbf, float* means, float* quats, float* scales,
+ * K time instants in ONE launch (K = 1: a plain render; K > 1: the K sub-frames of a blurry view, train.py:502-518 --
+ * the same Gaussians at K exposure times), 1 <= K <= 65535.
+ * in (host struct, see MobgsPrepInputs; read before the call returns):
+ *   times (device, [K,2] floats): per instant {t_feat = time + delta/max_time, t_curve = clamp(t_feat,0,1)}.
+ *   static leaves : xyz [Ns,3], scaling [Ns,3] (log), rotation [Ns,4], opacity [Ns] (logit), f_dc [Ns,6], f_t [Ns,3]
+ *   dynamic leaves: control [Nd,12,3] (x100 units), ncp [Nd] int64 active knots (4..12), scaling, rotation,
+ *                   omega [Nd,4], opacity, f_dc, f_t, trbf [Nd]
+ * attr_half = 1: the ATTRIBUTES (scaling, rotation, omega, opacity, f_dc, f_t) are stored as IEEE binary16 (BASELINE
+ *   config #5; no such mode exists in the reference, whose GaussianModel keeps fp32 nn.Parameters,
+ *   scene/gaussian_model.py:1044-1090): the kernels read the halves from HBM and widen them in registers, arithmetic and
+ *   outputs stay fp32.  xyz / control / trbf stay fp32.  0: float32.
+ * out: means [K,N,3], quats [K,N,4] (un-normalised; the projection normalises), colors [K,N,9] (row block k = instant
+ *      k); scales [N,3] and opacities [N] do not depend on time and exist once. */
+int mobgs_prep_fwd(int K, const MobgsPrepInputs* in, int attr_half, float* means, float* quats, float* scales,
                    float* opacities, float* colors, void* stream);
-/* Backward of mobgs_prep_fwd.  Cotangent pointers may be NULL (zeros).  Every gradient buffer is fully
- * written.  trbf and the times get no gradient (the reference detaches the time offset, :102). */
-int mobgs_prep_bwd(int Ns, int Nd, const float* times, const int64_t* d_ncp, const float* d_trbf,
-                   const float* scales, const float* opacities, const float* v_means, const float* v_quats,
-                   const float* v_scales, const float* v_opacities, const float* v_colors, float* g_s_xyz,
-                   float* g_s_scaling, float* g_s_rotation, float* g_s_opacity, float* g_s_fdc, float* g_s_ft,
-                   float* g_d_control, float* g_d_scaling, float* g_d_rotation, float* g_d_omega,
-                   float* g_d_opacity, float* g_d_fdc, float* g_d_ft, int accumulate, void* stream);
-/* The same two entry points for Gaussian sets whose ATTRIBUTES (scaling, rotation, omega, opacity, f_dc, f_t) are
- * stored as IEEE binary16 (BASELINE config #5; no such mode exists in the reference, whose GaussianModel keeps
- * fp32 nn.Parameters, scene/gaussian_model.py:1044-1090): the kernels read the halves from HBM and widen them in
- * registers, arithmetic and outputs stay fp32.  xyz / control / trbf stay fp32.  mobgs_prep_bwd_f16 writes the
- * attribute gradients as binary16 (what a half leaf's .grad must be); accumulation across renders in fp32 buffers
- * goes through mobgs_prep_bwd, which does not read the attributes. */
-int mobgs_prep_fwd_f16(int Ns, int Nd, const float* times, const float* s_xyz, const uint16_t* s_scaling,
-                       const uint16_t* s_rotation, const uint16_t* s_opacity, const uint16_t* s_fdc,
-                       const uint16_t* s_ft, const float* d_control, const int64_t* d_ncp,
-                       const uint16_t* d_scaling, const uint16_t* d_rotation, const uint16_t* d_omega,
-                       const uint16_t* d_opacity, const uint16_t* d_fdc, const uint16_t* d_ft, const float* d_trbf,
-                       float* means, float* quats, float* scales, float* opacities, float* colors, void* stream);
-int mobgs_prep_bwd_f16(int Ns, int Nd, const float* times, const int64_t* d_ncp, const float* d_trbf,
-                       const float* scales, const float* opacities, const float* v_means, const float* v_quats,
-                       const float* v_scales, const float* v_opacities, const float* v_colors, float* g_s_xyz,
-                       uint16_t* g_s_scaling, uint16_t* g_s_rotation, uint16_t* g_s_opacity, uint16_t* g_s_fdc,
-                       uint16_t* g_s_ft, float* g_d_control, uint16_t* g_d_scaling, uint16_t* g_d_rotation,
-                       uint16_t* g_d_omega, uint16_t* g_d_opacity, uint16_t* g_d_fdc, uint16_t* g_d_ft,
-                       int accumulate, void* stream);
-
-/* The four entry points above for K time instants in ONE launch (the K sub-frames of a blurry view, train.py:502-518: the
- * same Gaussians at K exposure times): times [K,2]; means [K,N,3], quats [K,N,4], colors [K,N,9] (row block k = instant
- * k); scales [N,3] and opacities [N] do not depend on time and exist once.  Backward: v_means / v_quats / v_colors
- * [K,...], v_scales / v_opacities once; the leaf gradients are the sums over the instants, accumulated in instant order
- * (the result of K single-instant calls in a row, bit for bit).  K = 1 is the single-instant call. */
-int mobgs_prep_fwd_many(int K, int Ns, int Nd, const float* times, const float* s_xyz, const float* s_scaling,
-                        const float* s_rotation, const float* s_opacity, const float* s_fdc, const float* s_ft,
-                        const float* d_control, const int64_t* d_ncp, const float* d_scaling,
-                        const float* d_rotation, const float* d_omega, const float* d_opacity, const float* d_fdc,
-                        const float* d_ft, const float* d_trbf, float* means, float* quats, float* scales,
-                        float* opacities, float* colors, void* stream);
-int mobgs_prep_bwd_many(int K, int Ns, int Nd, const float* times, const int64_t* d_ncp, const float* d_trbf,
-                        const float* scales, const float* opacities, const float* v_means, const float* v_quats,
-                        const float* v_scales, const float* v_opacities, const float* v_colors, float* g_s_xyz,
-                        float* g_s_scaling, float* g_s_rotation, float* g_s_opacity, float* g_s_fdc, float* g_s_ft,
-                        float* g_d_control, float* g_d_scaling, float* g_d_rotation, float* g_d_omega,
-                        float* g_d_opacity, float* g_d_fdc, float* g_d_ft, int accumulate, void* stream);
-int mobgs_prep_fwd_many_f16(int K, int Ns, int Nd, const float* times, const float* s_xyz, const uint16_t* s_scaling,
-                            const uint16_t* s_rotation, const uint16_t* s_opacity, const uint16_t* s_fdc,
-                            const uint16_t* s_ft, const float* d_control, const int64_t* d_ncp,
-                            const uint16_t* d_scaling, const uint16_t* d_rotation, const uint16_t* d_omega,
-                            const uint16_t* d_opacity, const uint16_t* d_fdc, const uint16_t* d_ft,
-                            const float* d_trbf, float* means, float* quats, float* scales, float* opacities,
-                            float* colors, void* stream);
-int mobgs_prep_bwd_many_f16(int K, int Ns, int Nd, const float* times, const int64_t* d_ncp, const float* d_trbf,
-                            const float* scales, const float* opacities, const float* v_means, const float* v_quats,
-                            const float* v_scales, const float* v_opacities, const float* v_colors, float* g_s_xyz,
-                            uint16_t* g_s_scaling, uint16_t* g_s_rotation, uint16_t* g_s_opacity, uint16_t* g_s_fdc,
-                            uint16_t* g_s_ft, float* g_d_control, uint16_t* g_d_scaling, uint16_t* g_d_rotation,
-                            uint16_t* g_d_omega, uint16_t* g_d_opacity, uint16_t* g_d_fdc, uint16_t* g_d_ft,
-                            int accumulate, void* stream);
+/* Backward of mobgs_prep_fwd.  Of `in`, only Ns, Nd, times, d_ncp and d_trbf are read.  v_means / v_quats / v_colors
+ * [K,...], v_scales / v_opacities once; cotangent pointers may be NULL (zeros).  Every gradient buffer of `grads` (host
+ * struct, see MobgsLeafGrads) is fully written -- or, with accumulate != 0, added to: the leaf gradients are the sums over
+ * the instants, accumulated in instant order (the result of K single-instant calls in a row, bit for bit).  trbf and the
+ * times get no gradient (the reference detaches the time offset, :102).
+ * grad_half = 1: the attribute gradients are written as binary16 (what a half leaf's .grad must be); accumulation across
+ * renders in fp32 buffers uses grad_half = 0 -- the backward pass does not read the attributes. */
+int mobgs_prep_bwd(int K, const MobgsPrepInputs* in, const float* scales, const float* opacities, const float* v_means,
+                   const float* v_quats, const float* v_scales, const float* v_opacities, const float* v_colors,
+                   const MobgsLeafGrads* grads, int grad_half, int accumulate, void* stream);
 
 /* ---- K9: colour decoder + expected-depth normalisation (replaces Sandwich.forward + gsplat's "ED" step) ---
  * /root/reference/helper_model.py:19-28; /root/reference/gaussian_renderer/__init__.py:216-227.
@@ -675,26 +634,16 @@ int mobgs_prep_bwd_many_f16(int K, int Ns, int Nd, const float* times, const int
  *   rays   [6,P] planar (the reference's cam_ray map, /root/reference/scene/cameras.py:132-146), ray_* = NULL;
  *   rays = NULL, ray_intr = device float[4] {fx, fy, cx, cy}, ray_c2w = device float[12] (the first three rows of
  *          the row-major camera-to-world matrix: a [3,4] or a [4,4] array), width = image width: the origin and
- *          the unit view direction through each pixel centre are generated in registers. */
-int mobgs_decoder_fwd(int P, int CF, int has_depth, int width, const float* feat_hw, const float* alphas,
-                      const float* rays, const float* ray_intr, const float* ray_c2w, const float* w1,
-                      const float* w2, float* rgb, float* depth, void* stream);
-/* w_partial: scratch [mobgs_decoder_bwd_blocks(P), 102] floats.  v_depth / v_rays may be NULL.
+ *          the unit view direction through each pixel centre are generated in registers.
+ * Backward: w_partial: scratch [C * mobgs_decoder_bwd_blocks(P), 102] floats.  v_depth / v_rays may be NULL.
  * g_c2w (may be NULL): gradient of ray_c2w (in-kernel-ray mode only), g_c2w_floats = 12 ([3,4]) or 16 ([4,4]: the
  * fourth row is written as zeros).  accumulate_wgrad != 0: the weight gradients are added to g_w1 / g_w2 instead
- * of overwriting them (fixed summation order either way). */
+ * of overwriting them (fixed summation order either way).
+ * A BATCH of C images in one launch (C = 1: one image; C > 1: the K sub-frames of a blurry view): feat_hw [C,P,CF],
+ * alphas [C,P], rgb [C,3,P], depth [C,P] (and the cotangents alike); *_stride = floats between consecutive images' ray
+ * maps / intrinsics / poses, 0 = shared by all images.  The weight gradients are sums over all images (one fixed-order
+ * reduction); g_c2w [C, g_c2w_floats].  A shared ray map / pose cannot receive a gradient when C > 1. */
 int mobgs_decoder_bwd_blocks(int P);
-int mobgs_decoder_bwd(int P, int CF, int has_depth, int width, const float* feat_hw, const float* alphas,
-                      const float* rays, const float* ray_intr, const float* ray_c2w, const float* w1,
-                      const float* w2, const float* v_rgb, const float* v_depth, float* v_feat_hw, float* v_alphas,
-                      float* v_rays, float* w_partial, float* g_w1, float* g_w2, float* g_c2w, int g_c2w_floats,
-                      int accumulate_wgrad, void* stream);
-
-/* The decoder for a BATCH of C images in one launch (the K sub-frames of a blurry view): feat_hw [C,P,CF], alphas [C,P],
- * rgb [C,3,P], depth [C,P] (and the cotangents alike); *_stride = floats between consecutive images' ray maps /
- * intrinsics / poses, 0 = shared by all images.  The weight gradients are sums over all images (one fixed-order
- * reduction); g_c2w [C, g_c2w_floats], w_partial [C * mobgs_decoder_bwd_blocks(P), 102].  A shared ray map / pose
- * cannot receive a gradient when C > 1.  C = 1 is the single-image call. */
 int mobgs_decoder_fwd_many(int C, int P, int CF, int has_depth, int width, const float* feat_hw, const float* alphas,
                            const float* rays, int64_t rays_stride, const float* ray_intr, int intr_stride,
                            const float* ray_c2w, int c2w_stride, const float* w1, const float* w2, float* rgb,

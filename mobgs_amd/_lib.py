@@ -6,7 +6,9 @@ the call raises.  PyTorch is used only for device memory and the current stream.
 from __future__ import annotations
 
 import ctypes
-from ctypes import c_char_p, c_float, c_int, c_int64, c_size_t, c_void_p
+import re
+from ctypes import c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
+from pathlib import Path
 from typing import Optional
 
 import torch
@@ -14,22 +16,105 @@ import torch
 from .build import LIB_PATH, build_extension, is_stale
 
 _lib: Optional[ctypes.CDLL] = None
+# always the repository's own header, also when MOBGS_LIB names a foreign build of the library: load() compares
+# mobgs_abi_version() with the header's MOBGS_ABI_VERSION and refuses a mismatch
+HEADER = Path(__file__).resolve().parent.parent / "include" / "mobgs_hip.h"
+_SCALARS = {"int": c_int, "int32_t": c_int32, "int64_t": c_int64, "size_t": c_size_t, "float": c_float,
+            "double": c_double}
+_RETURNS = {"const char*": c_char_p, **_SCALARS}
+
+
+def _scalar(type_text: str, where: str):
+    if type_text not in _SCALARS:
+        raise ValueError(f"mobgs_hip.h: unknown scalar type {type_text!r} in {where!r}")
+    return _SCALARS[type_text]
+
+
+def _parse_header(text: str):
+    """include/mobgs_hip.h -> (defines {name: int}, structs {name: [(field, ctype)]}, sigs {name: (restype, [argtypes])}).
+
+    The bindings have no table of their own: every signature, struct layout and constant is read from the header, so a
+    changed declaration cannot be driven with shifted arguments.  Conventions of the header this relies on:
+      - one declaration per `;`, every function named mobgs_* and returning int, size_t or const char*;
+      - no function-pointer parameters and no macros in parameter lists (parameters are split at commas);
+      - a declarator containing `*` is a pointer (c_void_p: device and host pointers travel as integers), anything else
+        a scalar whose type must be in _SCALARS; `(void)` is an empty list;
+      - structs are `typedef struct Name { ... } Name;` with plain fields, several declarators per type allowed
+        (`const float *a, *b;`), no bit-fields, arrays or nested structs;
+      - every `#define` with a value is an integer constant (optionally parenthesised).
+    Anything else raises with the offending text; nothing is skipped."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    defines = {}
+    for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+(\S.*?)[ \t]*$", text, re.M):  # (not the include guard)
+        if not re.fullmatch(r"\(?-?\d+\)?", m[2]):
+            raise ValueError(f"mobgs_hip.h: #define {m[1]} {m[2]!r} is not an integer constant")
+        defines[m[1]] = int(m[2].strip("()"))
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)                   # preprocessor lines
+    text = re.sub(r'extern\s+"C"\s*\{(.*)\}', r"\1", text, flags=re.S)    # the linkage block's braces
+    structs = {}
+
+    def take_struct(m):
+        if m[1] != m[3]:
+            raise ValueError(f"mobgs_hip.h: struct {m[1]} is typedef'd as {m[3]}")
+        fields = []
+        for decl in filter(None, (d.strip() for d in m[2].split(";"))):
+            d = re.fullmatch(r"(?:const\s+)?(\w+)\b\s*(.*)", decl, flags=re.S)
+            names = [re.fullmatch(r"(\*?)\s*(\w+)", n.strip()) for n in d[2].split(",")] if d else [None]
+            if not all(names):
+                raise ValueError(f"mobgs_hip.h: cannot read the field declaration {decl!r} of struct {m[1]}")
+            fields += [(n[2], c_void_p if n[1] else _scalar(d[1], decl)) for n in names]
+        structs[m[1]] = fields
+        return " "
+
+    text = re.sub(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*(\w+)\s*;", take_struct, text, flags=re.S)
+    sigs = {}
+    for decl in filter(None, (" ".join(d.split()) for d in text.split(";"))):
+        m = re.fullmatch(r"(.*?)\s*\b(mobgs_\w+) ?\((.*)\)", decl)
+        if not m or m[1].replace(" *", "*") not in _RETURNS:
+            raise ValueError(f"mobgs_hip.h: cannot read the declaration {decl!r}")
+        argtypes = []
+        for param in ([] if m[3].strip() in ("", "void") else m[3].split(",")):
+            if "(" in param or ")" in param:
+                raise ValueError(f"mobgs_hip.h: cannot read the parameter {param.strip()!r} of {m[2]}")
+            if "*" in param:
+                argtypes.append(c_void_p)
+            else:
+                words = [w for w in param.split() if w != "const"]
+                if len(words) != 2:
+                    raise ValueError(f"mobgs_hip.h: cannot read the parameter {param.strip()!r} of {m[2]}")
+                argtypes.append(_scalar(words[0], decl))
+        sigs[m[2]] = (_RETURNS[m[1].replace(" *", "*")], argtypes)
+    return defines, structs, sigs
+
+
+_DEFINES, _STRUCTS, _SIGS = _parse_header(HEADER.read_text())
+ABI_VERSION = _DEFINES["MOBGS_ABI_VERSION"]
+
+
+def _tuning_defaults(structs) -> list:
+    """MobgsTuning's defaults (-1 = library default; see the header's comment on each field), in the header's field
+    order.  A field of the header without a default here raises."""
+    defaults = dict(heavy_tile_len=-1, longest_list_hint=-1, quadrant_culling=-1, block_walk=-1, bwd_block_walk=-1,
+                    geometry_per_camera=0, bwd_mfma=-1, gate_zero_cotangent=0, coherent_order=0, static_rows=0,
+                    cover_slots=0)
+    names = [n for n, _ in structs["MobgsTuning"]]
+    if set(names) != set(defaults):
+        raise ValueError(f"mobgs_hip.h: MobgsTuning's fields {names} and the defaults in mobgs_amd/_lib.py "
+                         f"{list(defaults)} differ: every field needs a default")
+    return [(n, defaults[n]) for n in names]
+
+
+_TUNING_DEFAULTS = _tuning_defaults(_STRUCTS)
 
 
 class MobgsTuning(ctypes.Structure):
     """include/mobgs_hip.h MobgsTuning: per-call policy (-1 = library default).  The library keeps no state; a
     caller-side instance (mobgs_amd.rendering.tuning) is passed by pointer with every call that consults it."""
-    _fields_ = [("heavy_tile_len", ctypes.c_int32), ("longest_list_hint", ctypes.c_int32),
-                ("quadrant_culling", ctypes.c_int32), ("block_walk", ctypes.c_int32),
-                ("bwd_block_walk", ctypes.c_int32), ("geometry_per_camera", ctypes.c_int32),
-                ("bwd_mfma", ctypes.c_int32), ("gate_zero_cotangent", ctypes.c_int32),
-                ("coherent_order", ctypes.c_int32), ("static_rows", ctypes.c_int32), ("cover_slots", ctypes.c_int32)]
+    _fields_ = _STRUCTS["MobgsTuning"]
 
-    def __init__(self, heavy_tile_len=-1, longest_list_hint=-1, quadrant_culling=-1, block_walk=-1, bwd_block_walk=-1,
-                 geometry_per_camera=0, bwd_mfma=-1, gate_zero_cotangent=0, coherent_order=0, static_rows=0,
-                 cover_slots=0):
-        super().__init__(heavy_tile_len, longest_list_hint, quadrant_culling, block_walk, bwd_block_walk,
-                         geometry_per_camera, bwd_mfma, gate_zero_cotangent, coherent_order, static_rows, cover_slots)
+    def __init__(self, *args, **fields):
+        super().__init__(*args, **{**dict(_TUNING_DEFAULTS[len(args):]), **fields})
 
     def copy(self, **overrides):
         """A per-call copy with some fields replaced."""
@@ -44,135 +129,15 @@ class MobgsTuning(ctypes.Structure):
     def address(self) -> int:
         return ctypes.addressof(self)
 
+
 class MobgsPrepInputs(ctypes.Structure):
     """include/mobgs_hip.h MobgsPrepInputs: the raw parameters of the two sets (device pointers)."""
-    _fields_ = [("Ns", ctypes.c_int32), ("Nd", ctypes.c_int32)] + [(n, c_void_p) for n in (
-        "times", "s_xyz", "s_scaling", "s_rotation", "s_opacity", "s_fdc", "s_ft", "d_control", "d_ncp", "d_scaling",
-        "d_rotation", "d_omega", "d_opacity", "d_fdc", "d_ft", "d_trbf")]
+    _fields_ = _STRUCTS["MobgsPrepInputs"]
 
 
-P = c_void_p
-ABI_VERSION = 14  # include/mobgs_hip.h MOBGS_ABI_VERSION
-_SIGS = {
-    "mobgs_version": (c_char_p, []),
-    "mobgs_abi_version": (c_int, []),
-    "mobgs_last_error": (c_char_p, []),
-    "mobgs_record_stride": (c_int, [c_int]),
-    "mobgs_raster_channels_supported": (c_int, [c_int]),
-    "mobgs_raster_path": (c_int, [c_int, c_int, c_int, P]),
-    "mobgs_project_fwd": (c_int, [c_int, c_int, P, P, P, P, P, c_int, c_int, c_float, c_float, c_float, c_float,
-                                  P, P, P, P, P, P]),
-    "mobgs_project_bwd_scratch_floats": (c_size_t, [c_int, c_int]),
-    "mobgs_project_bwd": (c_int, [c_int, c_int, P, P, P, P, P, c_int, c_int, c_float, P, P, P, P, P, P, P, P, P,
-                                  P, P]),
-    "mobgs_project_bwd_ex": (c_int, [c_int, c_int, c_int, P, P, P, P, P, c_int, c_int, c_float, P, P, P, P, P, P, P,
-                                     P, P, P, P]),
-    "mobgs_isect_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "mobgs_keep_scan_len": (c_size_t, [c_int]),
-    "mobgs_tile_order_len": (c_size_t, [c_int]),
-    "mobgs_isect_offsets": (c_int, [c_int] * 8 + [P] * 5 + [c_int] + [P] * 4 + [c_int64] + [P] * 2 + [P, P]),
-    "mobgs_isect_emit_sort": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int64, c_int64] + [P] * 7 + [P]),
-    "mobgs_raster_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, c_int, P, c_int, P, P, P, P, P, P, P,
-                                 P, P, P, P, P, P]),
-    "mobgs_raster_fwd_decode": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, c_int, P, c_int, P, P, P, P, P, P, P,
-                                        P, P, P, P, P, c_int, P, c_int, P, P, P, P, P, P]),
-    "mobgs_raster_bwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int] + [P] * 16 + [P, P]),
-    "mobgs_raster_bwd_decode": (c_int, [c_int, c_int, c_int, c_int] + [P] * 15 + [c_int, P, c_int] + [P] * 6 + [P, P]),
-    "mobgs_raster_bwd_decode_finish": (c_int, [c_int, c_int, c_int, P, c_int, P, P, P, c_int, c_int, P]),
-    "mobgs_raster_bwd_reduce_decode": (c_int, [c_int, c_int] + [P] * 11 + [c_int, c_int, P, c_int, P, P, P, c_int, c_int, P]),
-    "mobgs_raster_bwd_decode_scratch_floats": (ctypes.c_size_t, [c_int, c_int, c_int]),
-    "mobgs_cotangent_probe": (c_int, [c_int, P, P, P, P]),
-    "mobgs_raster_bwd_reduce": (c_int, [c_int, c_int, c_int, c_int] + [P] * 11 + [P]),
-    "mobgs_project_and_bin": (c_int, [c_int, c_int, P, P, P, P, P, P, c_int, c_int, c_int, c_float, c_float, c_float,
-                                      c_float, c_int, P, P, P, P, P, P, P, P, P, c_int, P, P, c_int64, P, P, P, P, P,
-                                      P]),
-    "mobgs_isect_emit_sort_speculative": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int64, c_int64] + [P] * 8 + [P]),
-    "mobgs_project_and_bin_speculative": (c_int, [c_int, c_int, P, P, P, P, P, P, c_int, c_int, c_int, c_float,
-                                                  c_float, c_float, c_float, c_int, P, P, P, P, P, P, P, P, P, c_int,
-                                                  P, P, c_int64, P, P, P, c_int64, P, c_int64, P, c_int, c_int, P, P,
-                                                  P]),
-    "mobgs_fused_seg_keys_len": (c_size_t, [c_int, c_int]),
-    "mobgs_fused_max_seg_stride": (c_int, []),
-    "mobgs_project_and_bin_fused": (c_int, [c_int, c_int, P, P, P, P, P, P, c_int, c_int, c_int, c_float, c_float, c_float,
-                                            c_float, c_int, P, P, P, P, P, P, P, P, P, c_int, P, P, c_int64, P, P, c_int,
-                                            P, P, c_int64, P, c_int64, P, c_int, c_int, P, P, P]),
-    "mobgs_prep_project_and_bin_fused": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_float, c_float, c_float, c_float,
-                                                 c_int, P, P, P, P, P, P, P, P, P, c_int, P, P, c_int64, P, P, c_int, P,
-                                                 P, c_int64, P, c_int64, P, P, P]),
-    "mobgs_project_prep_bwd_fused": (c_int, [c_int, P, P, P, P, P, c_int, c_int, c_float] + [P] * 10 + [c_int, c_int] +
-                                     [P] * 7 + [c_int, P]),
-    "mobgs_densify_stats": (c_int, [c_int, P, c_int, P, P, P, P, P, P]),
-    "mobgs_densify_select": (c_int, [c_int, c_int, P, P, P, c_float, c_float, P, P, P]),
-    "mobgs_mask_indices": (c_int, [c_int, P, c_int, P, P, P]),
-    "mobgs_rows_gather": (c_int, [c_int, P, P, P, P, P, c_int, c_int, P]),
-    "mobgs_split_children": (c_int, [c_int, c_int, c_int, P, P, P, P, P]),
-    "mobgs_normals_fwd": (c_int, [c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float, P, P, P]),
-    "mobgs_normals_bwd": (c_int, [c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float, P, P, P, P]),
-    "mobgs_raster_class_fwd": (c_int, [c_int] * 7 + [P] * 9 + [P, P]),
-    "mobgs_raster_class_bwd": (c_int, [c_int] * 7 + [P] * 15 + [P, P]),
-    "mobgs_pack_records": (c_int, [c_int, c_int, c_int, P, P, P, c_int, P, c_int, P, P, P, P]),
-    "mobgs_raster_layers_fwd": (c_int, [c_int] * 7 + [P] * 8 + [P]),
-    "mobgs_raster_layers_bwd": (c_int, [c_int] * 8 + [P] * 21 + [P]),  # incl. 7 host pointer arrays of length 3
-    "mobgs_prep_fwd": (c_int, [c_int, c_int] + [P] * 21 + [P]),
-    "mobgs_prep_bwd": (c_int, [c_int, c_int] + [P] * 23 + [c_int, P]),
-    "mobgs_prep_fwd_f16": (c_int, [c_int, c_int] + [P] * 21 + [P]),
-    "mobgs_prep_bwd_f16": (c_int, [c_int, c_int] + [P] * 23 + [c_int, P]),
-    "mobgs_prep_fwd_many": (c_int, [c_int, c_int, c_int] + [P] * 21 + [P]),
-    "mobgs_prep_bwd_many": (c_int, [c_int, c_int, c_int] + [P] * 23 + [c_int, P]),
-    "mobgs_prep_fwd_many_f16": (c_int, [c_int, c_int, c_int] + [P] * 21 + [P]),
-    "mobgs_prep_bwd_many_f16": (c_int, [c_int, c_int, c_int] + [P] * 23 + [c_int, P]),
-    "mobgs_decoder_fwd": (c_int, [c_int, c_int, c_int, c_int] + [P] * 9 + [P]),
-    "mobgs_decoder_bwd_blocks": (c_int, [c_int]),
-    "mobgs_decoder_bwd": (c_int, [c_int, c_int, c_int, c_int] + [P] * 16 + [c_int, c_int, P]),
-    "mobgs_decoder_fwd_many": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, c_int64, P, c_int, P, c_int, P, P, P, P,
-                                       P]),
-    "mobgs_decoder_bwd_many": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, c_int64, P, c_int, P, c_int] + [P] * 11
-                               + [c_int, c_int, P]),
-    "mobgs_decoder_fwd_channels": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, c_int64, P, c_int, P, c_int, P, P, P,
-                                           P, P, c_int, c_int, P]),
-    "mobgs_decoder_bwd_channels": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, c_int64, P, c_int, P, c_int] +
-                                   [P] * 11 + [c_int, c_int, P, c_int, c_int, P]),
-    "mobgs_ssim_l1_blocks": (c_int, [c_int, c_int, c_int]),
-    "mobgs_ssim_l1_fwd": (c_int, [c_int, c_int, c_int, P, P, P, P, P]),
-    "mobgs_ssim_l1_bwd": (c_int, [c_int, c_int, c_int, P, P, P, P, P, P]),
-    "mobgs_flow_warp_loss_blocks": (c_int, [c_int, c_int, c_int]),
-    "mobgs_flow_warp_loss_fwd": (c_int, [c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P]),
-    "mobgs_flow_warp_loss_bwd": (c_int, [c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_int, P]),
-    "mobgs_flow_warp_loss_bwd_scratch_floats": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "mobgs_hexplane_fwd": (c_int, [c_int] + [P] * 7 + [P]),
-    "mobgs_hexplane_bwd": (c_int, [c_int] + [P] * 11 + [P]),
-    "mobgs_hexplane_bwd_scratch_bytes": (c_size_t, [c_int, P, P]),
-    "mobgs_deform_mlp_fwd": (c_int, [c_int] + [P] * 14 + [P]),
-    "mobgs_blce_saved_floats": (c_size_t, []),
-    "mobgs_blce_fwd": (c_int, [P, c_int, c_int, P, P, P, P, P, P]),
-    "mobgs_adam_step": (c_int, [c_int, P, ctypes.c_double, ctypes.c_double, ctypes.c_double, P]),
-    "mobgs_blce_bwd": (c_int, [P, P, c_int, c_int, P, P, P, P, P]),
-    "mobgs_deform_mlp_bwd_blocks": (c_int, [c_int]),
-    "mobgs_deform_mlp_grad_floats": (c_size_t, []),
-    "mobgs_deform_mlp_bwd": (c_int, [c_int] + [P] * 20 + [P]),
-    "mobgs_knn3_scratch_bytes": (c_size_t, [c_int]),
-    "mobgs_knn3_mean_dist2": (c_int, [c_int, P, P, P, c_size_t, P]),
-    "mobgs_control_onedown": (c_int, [c_int, c_int, P, P, c_float, c_float, c_float, P, c_float, P, P, P, P, P, c_int,
-                                      P]),
-    "mobgs_seed_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "mobgs_seed_consistency": (c_int, [c_int, c_int, c_int, P, P, P, P, P, c_size_t, P]),
-    "mobgs_seed_classify": (c_int, [c_int, c_int, c_int, P, P, c_size_t, P, P, P, P, P, P, P, P]),
-    "mobgs_seed_trajectories": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P]),
-    "mobgs_exposure_scratch_bytes": (c_size_t, [c_int64]),
-    "mobgs_exposure_estimate": (c_int, [c_int64, P, P, c_float, c_float, P, P, P, P]),
-    "mobgs_reg_terms_blocks": (c_int, [c_int64]),
-    "mobgs_reg_terms_fwd": (c_int, [c_int64, P, P, c_int64, P, c_int, c_float, c_float, c_float, c_int, c_int, c_int, P, P,
-                                    P, P, P]),
-    "mobgs_reg_terms_bwd": (c_int, [c_int64, P, P, c_int64, P, c_int, c_float, c_float, c_float, P, P, P, P]),
-}
-# entry points added by later translation units (bound if present in the header AND the library)
-_OPTIONAL_SIGS = {}
-
-
-def register_optional(name: str, restype, argtypes) -> None:
-    _OPTIONAL_SIGS[name] = (restype, argtypes)
-    if _lib is not None:
-        _bind(_lib, name, restype, argtypes)
+class MobgsLeafGrads(ctypes.Structure):
+    """include/mobgs_hip.h MobgsLeafGrads: the 13 leaf-gradient buffers (device pointers, ops._LEAF_NAMES order)."""
+    _fields_ = _STRUCTS["MobgsLeafGrads"]
 
 
 def _bind(lib, name, restype, argtypes):
@@ -197,15 +162,14 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     if not LIB_PATH.exists():
         raise RuntimeError(f"{LIB_PATH} not found; run `python -m mobgs_amd.build`")
     lib = ctypes.CDLL(str(LIB_PATH))
-    # include/mobgs_hip.h MOBGS_ABI_VERSION these bindings were written against: a stale or foreign build of the
+    # include/mobgs_hip.h MOBGS_ABI_VERSION these bindings were read from: a stale or foreign build of the
     # library (MOBGS_LIB) with other signatures / scratch formats must not be driven with shifted arguments
     got = lib.mobgs_abi_version() if hasattr(lib, "mobgs_abi_version") else 0
     if got != ABI_VERSION:
         raise RuntimeError(f"{LIB_PATH}: mobgs_abi_version() = {got}, these bindings need {ABI_VERSION} "
                            "(rebuild with `python -m mobgs_amd.build`)")
-    for name, (restype, argtypes) in {**_SIGS, **_OPTIONAL_SIGS}.items():
-        if name in _SIGS or hasattr(lib, name):
-            _bind(lib, name, restype, argtypes)
+    for name, (restype, argtypes) in _SIGS.items():
+        _bind(lib, name, restype, argtypes)
     _lib = lib
     return lib
 

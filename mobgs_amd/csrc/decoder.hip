@@ -508,13 +508,6 @@ int mobgs_decoder_fwd_many(int C, int P, int CF, int has_depth, int width, const
                                       ray_c2w, c2w_stride, w1, w2, rgb, depth, nullptr, 0, 0, stream);
 }
 
-int mobgs_decoder_fwd(int P, int CF, int has_depth, int width, const float* feat_hw, const float* alphas,
-                      const float* rays, const float* ray_intr, const float* ray_c2w, const float* w1,
-                      const float* w2, float* rgb, float* depth, void* stream) {
-    return mobgs_decoder_fwd_many(1, P, CF, has_depth, width, feat_hw, alphas, rays, 0, ray_intr, 0, ray_c2w, 0, w1, w2,
-                                  rgb, depth, stream);
-}
-
 int mobgs_decoder_bwd_many(int C, int P, int CF, int has_depth, int width, const float* feat_hw, const float* alphas,
                            const float* rays, int64_t rays_stride, const float* ray_intr, int intr_stride,
                            const float* ray_c2w, int c2w_stride, const float* w1, const float* w2, const float* v_rgb,
@@ -558,16 +551,6 @@ int mobgs_decoder_bwd_channels(int C, int P, int CF, int has_depth, int width, c
     hipLaunchKernelGGL(decoder_wgrad_reduce_kernel, dim3(nred, C), dim3(256), 0, (hipStream_t)stream, g, w_partial, g_w1,
                        g_w2, g_c2w, accumulate_wgrad, g_c2w_floats);
     return check_launch("decoder_bwd_kernel");
-}
-
-int mobgs_decoder_bwd(int P, int CF, int has_depth, int width, const float* feat_hw, const float* alphas,
-                      const float* rays, const float* ray_intr, const float* ray_c2w, const float* w1,
-                      const float* w2, const float* v_rgb, const float* v_depth, float* v_feat_hw, float* v_alphas,
-                      float* v_rays, float* w_partial, float* g_w1, float* g_w2, float* g_c2w, int g_c2w_floats,
-                      int accumulate_wgrad, void* stream) {
-    return mobgs_decoder_bwd_many(1, P, CF, has_depth, width, feat_hw, alphas, rays, 0, ray_intr, 0, ray_c2w, 0, w1, w2,
-                                  v_rgb, v_depth, v_feat_hw, v_alphas, v_rays, w_partial, g_w1, g_w2, g_c2w,
-                                  g_c2w_floats, accumulate_wgrad, stream);
 }
 
 }  // extern "C"

@@ -25,37 +25,30 @@ namespace {
 using at::Tensor;
 using OptT = c10::optional<Tensor>;
 
+// Every include/mobgs_hip.h entry point this file calls, named ONCE (without the mobgs_ prefix): the Api members, the
+// look-ups of bind() and symbols() -- the names mobgs_amd._fast resolves from the ctypes handle -- are generated from it.
+#define MOBGS_FAST_ENTRY_POINTS(X)                                                                                   \
+    X(abi_version) X(last_error) X(record_stride) X(prep_fwd) X(prep_bwd) X(raster_fwd) X(raster_fwd_decode)         \
+    X(raster_bwd) X(raster_bwd_decode) X(raster_bwd_decode_scratch_floats) X(raster_bwd_reduce_decode)               \
+    X(raster_bwd_reduce) X(decoder_fwd_channels) X(decoder_bwd_channels) X(decoder_bwd_blocks) X(project_bwd)        \
+    X(project_bwd_scratch_floats) X(project_and_bin_speculative) X(project_and_bin_fused)                            \
+    X(prep_project_and_bin_fused) X(project_prep_bwd_fused) X(fused_seg_keys_len) X(tile_order_len) X(keep_scan_len) \
+    X(isect_scratch_bytes) X(raster_channels_supported)
+
 struct Api {
-    decltype(&mobgs_last_error) last_error = nullptr;
-    decltype(&mobgs_record_stride) record_stride = nullptr;
-    decltype(&mobgs_prep_fwd_many) prep_fwd = nullptr;
-    decltype(&mobgs_prep_fwd_many_f16) prep_fwd_f16 = nullptr;
-    decltype(&mobgs_prep_bwd_many) prep_bwd = nullptr;
-    decltype(&mobgs_prep_bwd_many_f16) prep_bwd_f16 = nullptr;
-    decltype(&mobgs_raster_fwd) raster_fwd = nullptr;
-    decltype(&mobgs_raster_fwd_decode) raster_fwd_decode = nullptr;
-    decltype(&mobgs_raster_bwd) raster_bwd = nullptr;
-    decltype(&mobgs_raster_bwd_decode) raster_bwd_decode = nullptr;
-    decltype(&mobgs_raster_bwd_decode_scratch_floats) raster_bwd_decode_scratch_floats = nullptr;
-    decltype(&mobgs_raster_bwd_reduce_decode) raster_bwd_reduce_decode = nullptr;
-    decltype(&mobgs_raster_bwd_reduce) raster_bwd_reduce = nullptr;
-    decltype(&mobgs_decoder_fwd_channels) decoder_fwd = nullptr;
-    decltype(&mobgs_decoder_bwd_channels) decoder_bwd = nullptr;
-    decltype(&mobgs_decoder_bwd_blocks) decoder_bwd_blocks = nullptr;
-    decltype(&mobgs_project_bwd) project_bwd = nullptr;
-    decltype(&mobgs_project_bwd_ex) project_bwd_ex = nullptr;
-    decltype(&mobgs_project_bwd_scratch_floats) project_bwd_scratch_floats = nullptr;
-    decltype(&mobgs_project_and_bin_speculative) project_and_bin_speculative = nullptr;
-    decltype(&mobgs_project_and_bin_fused) project_and_bin_fused = nullptr;
-    decltype(&mobgs_prep_project_and_bin_fused) prep_project_and_bin_fused = nullptr;
-    decltype(&mobgs_project_prep_bwd_fused) project_prep_bwd_fused = nullptr;
-    decltype(&mobgs_fused_seg_keys_len) fused_seg_keys_len = nullptr;
-    decltype(&mobgs_tile_order_len) tile_order_len = nullptr;
-    decltype(&mobgs_keep_scan_len) keep_scan_len = nullptr;
-    decltype(&mobgs_isect_scratch_bytes) isect_scratch_bytes = nullptr;
-    decltype(&mobgs_raster_channels_supported) raster_channels_supported = nullptr;
+#define X(name) decltype(&mobgs_##name) name = nullptr;
+    MOBGS_FAST_ENTRY_POINTS(X)
+#undef X
     bool bound = false;
 } api;
+
+std::vector<std::string> symbols() {
+    return {
+#define X(name) "mobgs_" #name,
+        MOBGS_FAST_ENTRY_POINTS(X)
+#undef X
+    };
+}
 
 template <typename F>
 void take(const std::unordered_map<std::string, uint64_t>& m, const char* name, F& slot) {
@@ -66,39 +59,14 @@ void take(const std::unordered_map<std::string, uint64_t>& m, const char* name, 
 
 void bind(const std::unordered_map<std::string, uint64_t>& m) {
     // the header this file was compiled against must be the library's (a stale extension passed shifted pointers)
-    decltype(&mobgs_abi_version) abi = nullptr;
-    take(m, "mobgs_abi_version", abi);
-    if (abi() != MOBGS_ABI_VERSION)
+    take(m, "mobgs_abi_version", api.abi_version);
+    if (api.abi_version() != MOBGS_ABI_VERSION)
         throw std::runtime_error("mobgs fastpath: built against ABI " + std::to_string(MOBGS_ABI_VERSION) +
-                                 ", the library reports " + std::to_string(abi()) + " -- rebuild _mobgs_fast.so");
-    take(m, "mobgs_last_error", api.last_error);
-    take(m, "mobgs_record_stride", api.record_stride);
-    take(m, "mobgs_prep_fwd_many", api.prep_fwd);
-    take(m, "mobgs_prep_fwd_many_f16", api.prep_fwd_f16);
-    take(m, "mobgs_prep_bwd_many", api.prep_bwd);
-    take(m, "mobgs_prep_bwd_many_f16", api.prep_bwd_f16);
-    take(m, "mobgs_raster_fwd", api.raster_fwd);
-    take(m, "mobgs_raster_fwd_decode", api.raster_fwd_decode);
-    take(m, "mobgs_raster_bwd", api.raster_bwd);
-    take(m, "mobgs_raster_bwd_decode", api.raster_bwd_decode);
-    take(m, "mobgs_raster_bwd_decode_scratch_floats", api.raster_bwd_decode_scratch_floats);
-    take(m, "mobgs_raster_bwd_reduce_decode", api.raster_bwd_reduce_decode);
-    take(m, "mobgs_raster_bwd_reduce", api.raster_bwd_reduce);
-    take(m, "mobgs_decoder_fwd_channels", api.decoder_fwd);
-    take(m, "mobgs_decoder_bwd_channels", api.decoder_bwd);
-    take(m, "mobgs_decoder_bwd_blocks", api.decoder_bwd_blocks);
-    take(m, "mobgs_project_bwd", api.project_bwd);
-    take(m, "mobgs_project_bwd_ex", api.project_bwd_ex);
-    take(m, "mobgs_project_bwd_scratch_floats", api.project_bwd_scratch_floats);
-    take(m, "mobgs_project_and_bin_speculative", api.project_and_bin_speculative);
-    take(m, "mobgs_project_and_bin_fused", api.project_and_bin_fused);
-    take(m, "mobgs_prep_project_and_bin_fused", api.prep_project_and_bin_fused);
-    take(m, "mobgs_project_prep_bwd_fused", api.project_prep_bwd_fused);
-    take(m, "mobgs_fused_seg_keys_len", api.fused_seg_keys_len);
-    take(m, "mobgs_tile_order_len", api.tile_order_len);
-    take(m, "mobgs_keep_scan_len", api.keep_scan_len);
-    take(m, "mobgs_isect_scratch_bytes", api.isect_scratch_bytes);
-    take(m, "mobgs_raster_channels_supported", api.raster_channels_supported);
+                                 ", the library reports " + std::to_string(api.abi_version()) +
+                                 " -- rebuild _mobgs_fast.so");
+#define X(name) take(m, "mobgs_" #name, api.name);
+    MOBGS_FAST_ENTRY_POINTS(X)
+#undef X
     api.bound = true;
 }
 
@@ -166,20 +134,12 @@ prep_fwd(const Tensor& times_in, const Tensor& s_xyz_in, const Tensor& d_control
     Tensor means = many ? at::empty({K, N, 3}, opt) : at::empty({N, 3}, opt),
            quats = many ? at::empty({K, N, 4}, opt) : at::empty({N, 4}, opt), scales = at::empty({N, 3}, opt),
            opac = at::empty({N}, opt), colors = many ? at::empty({K, N, 9}, opt) : at::empty({N, 9}, opt);
-    if (half) {
-        auto h = [](const Tensor& t) { return static_cast<const uint16_t*>(dp(t)); };
-        check(api.prep_fwd_f16((int)K, (int)Ns, (int)Nd, fp(times), fp(s_xyz), h(a[0]), h(a[1]), h(a[2]), h(a[3]), h(a[4]),
-                               fp(d_control), static_cast<const int64_t*>(dp(d_ncp)), h(a[5]), h(a[6]), h(a[7]),
-                               h(a[8]), h(a[9]), h(a[10]), fp(d_trbf), fpw(means), fpw(quats), fpw(scales),
-                               fpw(opac), fpw(colors), sp(stream)),
-              "mobgs_prep_fwd");
-    } else {
-        check(api.prep_fwd((int)K, (int)Ns, (int)Nd, fp(times), fp(s_xyz), fp(a[0]), fp(a[1]), fp(a[2]), fp(a[3]), fp(a[4]),
-                           fp(d_control), static_cast<const int64_t*>(dp(d_ncp)), fp(a[5]), fp(a[6]), fp(a[7]),
-                           fp(a[8]), fp(a[9]), fp(a[10]), fp(d_trbf), fpw(means), fpw(quats), fpw(scales), fpw(opac),
-                           fpw(colors), sp(stream)),
-              "mobgs_prep_fwd");
-    }
+    // (the record ops.PrepSplats.forward builds: attribute members as halves when `half`)
+    const MobgsPrepInputs in{(int32_t)Ns, (int32_t)Nd, fp(times), fp(s_xyz), dp(a[0]), dp(a[1]), dp(a[2]), dp(a[3]), dp(a[4]),
+                             fp(d_control), static_cast<const int64_t*>(dp(d_ncp)), dp(a[5]), dp(a[6]), dp(a[7]), dp(a[8]),
+                             dp(a[9]), dp(a[10]), fp(d_trbf)};
+    check(api.prep_fwd((int)K, &in, half ? 1 : 0, fpw(means), fpw(quats), fpw(scales), fpw(opac), fpw(colors), sp(stream)),
+          "mobgs_prep_fwd");
     return {means, quats, scales, opac, colors, times, d_ncp, d_trbf, conversions};
 }
 
@@ -201,20 +161,18 @@ std::vector<Tensor> prep_bwd(int64_t Ns, int64_t Nd, const Tensor& times, const 
     }
     const OptT c0 = f32c(v_means), c1 = f32c(v_quats), c2 = f32c(v_scales), c3 = f32c(v_opac), c4 = f32c(v_colors);
     const int64_t K = times.dim() == 2 ? times.size(0) : 1;
-    if (g_half) {
-        auto h = [](const Tensor& t) { return static_cast<uint16_t*>(dp(t)); };
-        check(api.prep_bwd_f16((int)K, (int)Ns, (int)Nd, fp(times), static_cast<const int64_t*>(dp(d_ncp)), fp(d_trbf),
-                               fp(scales), fp(opac), fp(c0), fp(c1), fp(c2), fp(c3), fp(c4), fpw(g[0]), h(g[1]),
-                               h(g[2]), h(g[3]), h(g[4]), h(g[5]), fpw(g[6]), h(g[7]), h(g[8]), h(g[9]), h(g[10]),
-                               h(g[11]), h(g[12]), (int)accumulate, sp(stream)),
-              "mobgs_prep_bwd");
-    } else {
-        check(api.prep_bwd((int)K, (int)Ns, (int)Nd, fp(times), static_cast<const int64_t*>(dp(d_ncp)), fp(d_trbf),
-                           fp(scales), fp(opac), fp(c0), fp(c1), fp(c2), fp(c3), fp(c4), fpw(g[0]), fpw(g[1]),
-                           fpw(g[2]), fpw(g[3]), fpw(g[4]), fpw(g[5]), fpw(g[6]), fpw(g[7]), fpw(g[8]), fpw(g[9]),
-                           fpw(g[10]), fpw(g[11]), fpw(g[12]), (int)accumulate, sp(stream)),
-              "mobgs_prep_bwd");
-    }
+    // (the two records ops.prep_backward builds: of the inputs the backward pass reads the sizes, times, d_ncp and d_trbf)
+    MobgsPrepInputs in{};
+    in.Ns = (int32_t)Ns;
+    in.Nd = (int32_t)Nd;
+    in.times = fp(times);
+    in.d_ncp = static_cast<const int64_t*>(dp(d_ncp));
+    in.d_trbf = fp(d_trbf);
+    const MobgsLeafGrads lg{fpw(g[0]), dp(g[1]), dp(g[2]), dp(g[3]), dp(g[4]), dp(g[5]), fpw(g[6]),
+                            dp(g[7]), dp(g[8]), dp(g[9]), dp(g[10]), dp(g[11]), dp(g[12])};
+    check(api.prep_bwd((int)K, &in, fp(scales), fp(opac), fp(c0), fp(c1), fp(c2), fp(c3), fp(c4), &lg, g_half ? 1 : 0,
+                       (int)accumulate, sp(stream)),
+          "mobgs_prep_bwd");
     return g;
 }
 
@@ -390,9 +348,9 @@ std::tuple<Tensor, OptT, OptT> decoder_fwd(int64_t H, int64_t W, int64_t CF, boo
         shape.back() = chan_n;
         chan = at::empty(shape, f);
     }
-    check(api.decoder_fwd((int)d.C, (int)(H * W), (int)CF, has_depth ? 1 : 0, (int)W, fp(feat_hw), fp(alphas), fp(rays),
-                          d.rays, fp(intr), (int)d.intr, fp(c2w), (int)d.c2w, fp(w1), fp(w2), fpw(rgb), fpw(depth),
-                          fpw(chan), (int)chan_c0, (int)chan_n, sp(stream)),
+    check(api.decoder_fwd_channels((int)d.C, (int)(H * W), (int)CF, has_depth ? 1 : 0, (int)W, fp(feat_hw), fp(alphas),
+                                   fp(rays), d.rays, fp(intr), (int)d.intr, fp(c2w), (int)d.c2w, fp(w1), fp(w2), fpw(rgb),
+                                   fpw(depth), fpw(chan), (int)chan_c0, (int)chan_n, sp(stream)),
           "mobgs_decoder_fwd");
     return {rgb, depth, chan};
 }
@@ -421,11 +379,11 @@ decoder_bwd(int64_t H, int64_t W, int64_t CF, bool has_depth, const Tensor& feat
     const bool sunk = g_w1_in.has_value() && g_w1_in->defined();
     Tensor g_w1 = sunk ? *g_w1_in : at::empty_like(w1);
     Tensor g_w2 = sunk ? *g_w2_in : at::empty_like(w2);
-    check(api.decoder_bwd((int)d.C, (int)P, (int)CF, has_depth ? 1 : 0, (int)W, fp(feat_hw), fp(alphas), fp(rays), d.rays,
-                          fp(intr), (int)d.intr, fp(c2w), (int)d.c2w, fp(w1), fp(w2), fp(v_rgb), fp(v_depth),
-                          fpw(v_feat), fpw(v_alphas), fpw(v_rays), fpw(partial), fpw(g_w1), fpw(g_w2), fpw(g_c2w),
-                          g_c2w.has_value() ? (int)(g_c2w->numel() / (d.c2w ? d.C : 1)) : 0,
-                          sunk ? (int)accumulate : 0, fp(v_chan), (int)chan_c0, (int)chan_n, sp(stream)),
+    check(api.decoder_bwd_channels((int)d.C, (int)P, (int)CF, has_depth ? 1 : 0, (int)W, fp(feat_hw), fp(alphas), fp(rays),
+                                   d.rays, fp(intr), (int)d.intr, fp(c2w), (int)d.c2w, fp(w1), fp(w2), fp(v_rgb),
+                                   fp(v_depth), fpw(v_feat), fpw(v_alphas), fpw(v_rays), fpw(partial), fpw(g_w1), fpw(g_w2),
+                                   fpw(g_c2w), g_c2w.has_value() ? (int)(g_c2w->numel() / (d.c2w ? d.C : 1)) : 0,
+                                   sunk ? (int)accumulate : 0, fp(v_chan), (int)chan_c0, (int)chan_n, sp(stream)),
           "mobgs_decoder_bwd");
     return {v_feat, v_alphas, v_rays, g_c2w, g_w1, g_w2};
 }
@@ -442,9 +400,9 @@ project_bwd(int64_t width, int64_t height, double eps2d, const Tensor& means, co
            v_viewmats = at::empty_like(viewmats);
     Tensor partial = at::empty({(int64_t)api.project_bwd_scratch_floats((int)C, (int)N)}, means.options());
     const OptT g2 = f32c(v_means2d), gd = f32c(v_depths), gc = f32c(v_conics);
-    check(api.project_bwd_ex((int)C, (int)N, per_cam, fp(means), fp(quats), fp(scales), fp(viewmats), fp(Ks), (int)width,
-                             (int)height, (float)eps2d, ip(radii), fp(conics), fp(g2), fp(gd), fp(gc), fpw(v_means),
-                             fpw(v_quats), fpw(v_scales), fpw(v_viewmats), fpw(partial), sp(stream)),
+    check(api.project_bwd((int)C, (int)N, per_cam, fp(means), fp(quats), fp(scales), fp(viewmats), fp(Ks), (int)width,
+                          (int)height, (float)eps2d, ip(radii), fp(conics), fp(g2), fp(gd), fp(gc), fpw(v_means),
+                          fpw(v_quats), fpw(v_scales), fpw(v_viewmats), fpw(partial), sp(stream)),
           "mobgs_project_bwd");
     return {v_means, v_quats, v_scales, v_viewmats};
 }
@@ -594,6 +552,7 @@ project_and_bin_speculative(const Tensor& means, const Tensor& quats, const Tens
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.doc() = "mobgs_amd host fast path (see csrc/fastpath.cpp)";
+    m.def("symbols", &symbols);
     m.def("bind", &bind);
     m.def("prep_fwd", &prep_fwd);
     m.def("prep_bwd", &prep_bwd);

@@ -129,150 +129,64 @@ prep_bwd_kernel(int Ns, int Nd, int K, const float* __restrict__ times, const lo
 using namespace mobgs;
 
 template <typename A>
-static int prep_fwd_launch(int K, int Ns, int Nd, const float* times, const float* s_xyz, const A* s_scaling,
-                           const A* s_rotation, const A* s_opacity, const A* s_fdc, const A* s_ft,
-                           const float* d_control, const int64_t* d_ncp, const A* d_scaling, const A* d_rotation,
-                           const A* d_omega, const A* d_opacity, const A* d_fdc, const A* d_ft, const float* d_trbf,
-                           float* means, float* quats, float* scales, float* opacities, float* colors, void* stream,
-                           const char* who) {
+static int prep_fwd_launch(int K, const MobgsPrepInputs& p, float* means, float* quats, float* scales, float* opacities,
+                           float* colors, void* stream, const char* who) {
+    const int Ns = p.Ns, Nd = p.Nd;
     if (Ns < 0 || Nd < 0 || K < 1 || K > 65535) {
         set_error("%s: bad sizes K=%d Ns=%d Nd=%d", who, K, Ns, Nd);
         return MOBGS_E_INVALID;
     }
     const int N = Ns + Nd;
     if (N == 0) return MOBGS_OK;
-    const PrepIn<A> in{Ns, Nd, times, s_xyz, s_scaling, s_rotation, s_opacity, s_fdc, s_ft, d_control,
-                       (const long long*)d_ncp, d_scaling, d_rotation, d_omega, d_opacity, d_fdc, d_ft, d_trbf};
-    hipLaunchKernelGGL(prep_fwd_kernel<A>, dim3((N + 255) / 256, K), dim3(256), 0, (hipStream_t)stream, in, means, quats,
-                       scales, opacities, colors);
+    hipLaunchKernelGGL(prep_fwd_kernel<A>, dim3((N + 255) / 256, K), dim3(256), 0, (hipStream_t)stream, prep_in<A>(p), means,
+                       quats, scales, opacities, colors);
     return check_launch("prep_fwd_kernel");
 }
 
 template <typename G>
-static int prep_bwd_launch(int K, int Ns, int Nd, const float* times, const int64_t* d_ncp, const float* d_trbf,
-                           const float* scales, const float* opacities, const float* v_means, const float* v_quats,
-                           const float* v_scales, const float* v_opacities, const float* v_colors, float* g_s_xyz,
-                           G* g_s_scaling, G* g_s_rotation, G* g_s_opacity, G* g_s_fdc, G* g_s_ft, float* g_d_control,
-                           G* g_d_scaling, G* g_d_rotation, G* g_d_omega, G* g_d_opacity, G* g_d_fdc, G* g_d_ft,
-                           int accumulate, void* stream, const char* who) {
+static int prep_bwd_launch(int K, const MobgsPrepInputs& p, const float* scales, const float* opacities,
+                           const float* v_means, const float* v_quats, const float* v_scales, const float* v_opacities,
+                           const float* v_colors, const MobgsLeafGrads& g, int accumulate, void* stream, const char* who) {
+    const int Ns = p.Ns, Nd = p.Nd;
     if (Ns < 0 || Nd < 0 || K < 1) {
         set_error("%s: bad sizes K=%d Ns=%d Nd=%d", who, K, Ns, Nd);
         return MOBGS_E_INVALID;
     }
     const int N = Ns + Nd;
     if (N == 0) return MOBGS_OK;
-    if (accumulate)
-        hipLaunchKernelGGL((prep_bwd_kernel<true, G>), dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, Ns, Nd, K,
-                           times, (const long long*)d_ncp, d_trbf, scales, opacities, v_means, v_quats, v_scales,
-                           v_opacities, v_colors, g_s_xyz, g_s_scaling, g_s_rotation, g_s_opacity, g_s_fdc, g_s_ft,
-                           g_d_control, g_d_scaling, g_d_rotation, g_d_omega, g_d_opacity, g_d_fdc, g_d_ft);
-    else
-        hipLaunchKernelGGL((prep_bwd_kernel<false, G>), dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, Ns,
-                           Nd, K, times, (const long long*)d_ncp, d_trbf, scales, opacities, v_means, v_quats, v_scales,
-                           v_opacities, v_colors, g_s_xyz, g_s_scaling, g_s_rotation, g_s_opacity, g_s_fdc, g_s_ft,
-                           g_d_control, g_d_scaling, g_d_rotation, g_d_omega, g_d_opacity, g_d_fdc, g_d_ft);
+    auto a = [](void* q) { return static_cast<G*>(q); };
+    hipLaunchKernelGGL((accumulate ? prep_bwd_kernel<true, G> : prep_bwd_kernel<false, G>), dim3((N + 255) / 256), dim3(256),
+                       0, (hipStream_t)stream, Ns, Nd, K, p.times, (const long long*)p.d_ncp, p.d_trbf, scales, opacities,
+                       v_means, v_quats, v_scales, v_opacities, v_colors, g.s_xyz, a(g.s_scaling), a(g.s_rotation),
+                       a(g.s_opacity), a(g.s_fdc), a(g.s_ft), g.d_control, a(g.d_scaling), a(g.d_rotation), a(g.d_omega),
+                       a(g.d_opacity), a(g.d_fdc), a(g.d_ft));
     return check_launch("prep_bwd_kernel");
 }
 
 extern "C" {
 
-int mobgs_prep_fwd_many(int K, int Ns, int Nd, const float* times, const float* s_xyz, const float* s_scaling,
-                   const float* s_rotation, const float* s_opacity, const float* s_fdc, const float* s_ft,
-                   const float* d_control, const int64_t* d_ncp, const float* d_scaling, const float* d_rotation,
-                   const float* d_omega, const float* d_opacity, const float* d_fdc, const float* d_ft,
-                   const float* d_trbf, float* means, float* quats, float* scales, float* opacities, float* colors,
-                   void* stream) {
-    return prep_fwd_launch<float>(K, Ns, Nd, times, s_xyz, s_scaling, s_rotation, s_opacity, s_fdc, s_ft, d_control, d_ncp,
-                                  d_scaling, d_rotation, d_omega, d_opacity, d_fdc, d_ft, d_trbf, means, quats, scales,
-                                  opacities, colors, stream, "mobgs_prep_fwd");
+int mobgs_prep_fwd(int K, const MobgsPrepInputs* in, int attr_half, float* means, float* quats, float* scales,
+                   float* opacities, float* colors, void* stream) {
+    if (!in) {
+        set_error("mobgs_prep_fwd: NULL inputs record");
+        return MOBGS_E_INVALID;
+    }
+    if (!attr_half) return prep_fwd_launch<float>(K, *in, means, quats, scales, opacities, colors, stream, "mobgs_prep_fwd");
+    return prep_fwd_launch<__half>(K, *in, means, quats, scales, opacities, colors, stream, "mobgs_prep_fwd");
 }
 
-int mobgs_prep_fwd_many_f16(int K, int Ns, int Nd, const float* times, const float* s_xyz, const uint16_t* s_scaling,
-                       const uint16_t* s_rotation, const uint16_t* s_opacity, const uint16_t* s_fdc,
-                       const uint16_t* s_ft, const float* d_control, const int64_t* d_ncp, const uint16_t* d_scaling,
-                       const uint16_t* d_rotation, const uint16_t* d_omega, const uint16_t* d_opacity,
-                       const uint16_t* d_fdc, const uint16_t* d_ft, const float* d_trbf, float* means, float* quats,
-                       float* scales, float* opacities, float* colors, void* stream) {
-    auto H = [](const uint16_t* p) { return reinterpret_cast<const __half*>(p); };
-    return prep_fwd_launch<__half>(K, Ns, Nd, times, s_xyz, H(s_scaling), H(s_rotation), H(s_opacity), H(s_fdc), H(s_ft),
-                                   d_control, d_ncp, H(d_scaling), H(d_rotation), H(d_omega), H(d_opacity), H(d_fdc),
-                                   H(d_ft), d_trbf, means, quats, scales, opacities, colors, stream,
-                                   "mobgs_prep_fwd_f16");
-}
-
-int mobgs_prep_bwd_many(int K, int Ns, int Nd, const float* times, const int64_t* d_ncp, const float* d_trbf,
-                   const float* scales, const float* opacities, const float* v_means, const float* v_quats,
-                   const float* v_scales, const float* v_opacities, const float* v_colors, float* g_s_xyz,
-                   float* g_s_scaling, float* g_s_rotation, float* g_s_opacity, float* g_s_fdc, float* g_s_ft,
-                   float* g_d_control, float* g_d_scaling, float* g_d_rotation, float* g_d_omega, float* g_d_opacity,
-                   float* g_d_fdc, float* g_d_ft, int accumulate, void* stream) {
-    return prep_bwd_launch<float>(K, Ns, Nd, times, d_ncp, d_trbf, scales, opacities, v_means, v_quats, v_scales,
-                                  v_opacities, v_colors, g_s_xyz, g_s_scaling, g_s_rotation, g_s_opacity, g_s_fdc,
-                                  g_s_ft, g_d_control, g_d_scaling, g_d_rotation, g_d_omega, g_d_opacity, g_d_fdc,
-                                  g_d_ft, accumulate, stream, "mobgs_prep_bwd");
-}
-
-int mobgs_prep_bwd_many_f16(int K, int Ns, int Nd, const float* times, const int64_t* d_ncp, const float* d_trbf,
-                       const float* scales, const float* opacities, const float* v_means, const float* v_quats,
-                       const float* v_scales, const float* v_opacities, const float* v_colors, float* g_s_xyz,
-                       uint16_t* g_s_scaling, uint16_t* g_s_rotation, uint16_t* g_s_opacity, uint16_t* g_s_fdc,
-                       uint16_t* g_s_ft, float* g_d_control, uint16_t* g_d_scaling, uint16_t* g_d_rotation,
-                       uint16_t* g_d_omega, uint16_t* g_d_opacity, uint16_t* g_d_fdc, uint16_t* g_d_ft, int accumulate,
-                       void* stream) {
-    auto H = [](uint16_t* p) { return reinterpret_cast<__half*>(p); };
-    return prep_bwd_launch<__half>(K, Ns, Nd, times, d_ncp, d_trbf, scales, opacities, v_means, v_quats, v_scales,
-                                   v_opacities, v_colors, g_s_xyz, H(g_s_scaling), H(g_s_rotation), H(g_s_opacity),
-                                   H(g_s_fdc), H(g_s_ft), g_d_control, H(g_d_scaling), H(g_d_rotation), H(g_d_omega),
-                                   H(g_d_opacity), H(g_d_fdc), H(g_d_ft), accumulate, stream, "mobgs_prep_bwd_f16");
-}
-
-
-// one time instant (K = 1)
-int mobgs_prep_fwd(int Ns, int Nd, const float* times, const float* s_xyz, const float* s_scaling,
-                   const float* s_rotation, const float* s_opacity, const float* s_fdc, const float* s_ft,
-                   const float* d_control, const int64_t* d_ncp, const float* d_scaling, const float* d_rotation,
-                   const float* d_omega, const float* d_opacity, const float* d_fdc, const float* d_ft,
-                   const float* d_trbf, float* means, float* quats, float* scales, float* opacities, float* colors,
-                   void* stream) {
-    return mobgs_prep_fwd_many(1, Ns, Nd, times, s_xyz, s_scaling, s_rotation, s_opacity, s_fdc, s_ft, d_control, d_ncp,
-                               d_scaling, d_rotation, d_omega, d_opacity, d_fdc, d_ft, d_trbf, means, quats, scales,
-                               opacities, colors, stream);
-}
-
-int mobgs_prep_fwd_f16(int Ns, int Nd, const float* times, const float* s_xyz, const uint16_t* s_scaling,
-                       const uint16_t* s_rotation, const uint16_t* s_opacity, const uint16_t* s_fdc,
-                       const uint16_t* s_ft, const float* d_control, const int64_t* d_ncp, const uint16_t* d_scaling,
-                       const uint16_t* d_rotation, const uint16_t* d_omega, const uint16_t* d_opacity,
-                       const uint16_t* d_fdc, const uint16_t* d_ft, const float* d_trbf, float* means, float* quats,
-                       float* scales, float* opacities, float* colors, void* stream) {
-    return mobgs_prep_fwd_many_f16(1, Ns, Nd, times, s_xyz, s_scaling, s_rotation, s_opacity, s_fdc, s_ft, d_control,
-                                   d_ncp, d_scaling, d_rotation, d_omega, d_opacity, d_fdc, d_ft, d_trbf, means, quats,
-                                   scales, opacities, colors, stream);
-}
-
-int mobgs_prep_bwd(int Ns, int Nd, const float* times, const int64_t* d_ncp, const float* d_trbf,
-                   const float* scales, const float* opacities, const float* v_means, const float* v_quats,
-                   const float* v_scales, const float* v_opacities, const float* v_colors, float* g_s_xyz,
-                   float* g_s_scaling, float* g_s_rotation, float* g_s_opacity, float* g_s_fdc, float* g_s_ft,
-                   float* g_d_control, float* g_d_scaling, float* g_d_rotation, float* g_d_omega, float* g_d_opacity,
-                   float* g_d_fdc, float* g_d_ft, int accumulate, void* stream) {
-    return mobgs_prep_bwd_many(1, Ns, Nd, times, d_ncp, d_trbf, scales, opacities, v_means, v_quats, v_scales,
-                               v_opacities, v_colors, g_s_xyz, g_s_scaling, g_s_rotation, g_s_opacity, g_s_fdc, g_s_ft,
-                               g_d_control, g_d_scaling, g_d_rotation, g_d_omega, g_d_opacity, g_d_fdc, g_d_ft,
-                               accumulate, stream);
-}
-
-int mobgs_prep_bwd_f16(int Ns, int Nd, const float* times, const int64_t* d_ncp, const float* d_trbf,
-                       const float* scales, const float* opacities, const float* v_means, const float* v_quats,
-                       const float* v_scales, const float* v_opacities, const float* v_colors, float* g_s_xyz,
-                       uint16_t* g_s_scaling, uint16_t* g_s_rotation, uint16_t* g_s_opacity, uint16_t* g_s_fdc,
-                       uint16_t* g_s_ft, float* g_d_control, uint16_t* g_d_scaling, uint16_t* g_d_rotation,
-                       uint16_t* g_d_omega, uint16_t* g_d_opacity, uint16_t* g_d_fdc, uint16_t* g_d_ft, int accumulate,
-                       void* stream) {
-    return mobgs_prep_bwd_many_f16(1, Ns, Nd, times, d_ncp, d_trbf, scales, opacities, v_means, v_quats, v_scales,
-                                   v_opacities, v_colors, g_s_xyz, g_s_scaling, g_s_rotation, g_s_opacity, g_s_fdc,
-                                   g_s_ft, g_d_control, g_d_scaling, g_d_rotation, g_d_omega, g_d_opacity, g_d_fdc,
-                                   g_d_ft, accumulate, stream);
+int mobgs_prep_bwd(int K, const MobgsPrepInputs* in, const float* scales, const float* opacities, const float* v_means,
+                   const float* v_quats, const float* v_scales, const float* v_opacities, const float* v_colors,
+                   const MobgsLeafGrads* grads, int grad_half, int accumulate, void* stream) {
+    if (!in || !grads) {
+        set_error("mobgs_prep_bwd: NULL inputs or gradients record");
+        return MOBGS_E_INVALID;
+    }
+    if (!grad_half)
+        return prep_bwd_launch<float>(K, *in, scales, opacities, v_means, v_quats, v_scales, v_opacities, v_colors, *grads,
+                                      accumulate, stream, "mobgs_prep_bwd");
+    return prep_bwd_launch<__half>(K, *in, scales, opacities, v_means, v_quats, v_scales, v_opacities, v_colors, *grads,
+                                   accumulate, stream, "mobgs_prep_bwd");
 }
 
 }  // extern "C"

@@ -73,6 +73,15 @@ struct PrepIn {
     const float* d_trbf;
 };
 
+// the public host record (include/mobgs_hip.h MobgsPrepInputs) with its attribute members read as A
+template <typename A>
+inline PrepIn<A> prep_in(const MobgsPrepInputs& p) {
+    auto a = [](const void* q) { return static_cast<const A*>(q); };
+    return PrepIn<A>{p.Ns, p.Nd, p.times, p.s_xyz, a(p.s_scaling), a(p.s_rotation), a(p.s_opacity), a(p.s_fdc), a(p.s_ft),
+                     p.d_control, (const long long*)p.d_ncp, a(p.d_scaling), a(p.d_rotation), a(p.d_omega),
+                     a(p.d_opacity), a(p.d_fdc), a(p.d_ft), p.d_trbf};
+}
+
 // splat i of the concatenated set -> position, UN-normalised rotation, scales, opacity, 9 colour features
 template <typename A>
 __device__ __forceinline__ void prep_splat(const PrepIn<A>& in, int i, float (&m)[3], float (&q)[4], float (&s)[3],

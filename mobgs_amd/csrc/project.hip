@@ -611,10 +611,7 @@ int mobgs::project_fwd_launch(const BinGrid& g, const ProjectIn& in, const Proje
             return MOBGS_E_INVALID;
         }
         PrepFused pf;
-        pf.in = PrepIn<float>{prep->Ns, prep->Nd, prep->times, prep->s_xyz, prep->s_scaling, prep->s_rotation,
-                              prep->s_opacity, prep->s_fdc, prep->s_ft, prep->d_control,
-                              (const long long*)prep->d_ncp, prep->d_scaling, prep->d_rotation, prep->d_omega,
-                              prep->d_opacity, prep->d_fdc, prep->d_ft, prep->d_trbf};
+        pf.in = prep_in<float>(*prep);  // (float32 leaves only)
         pf.means = const_cast<float*>(in.means);
         pf.quats = const_cast<float*>(in.quats);
         pf.scales = const_cast<float*>(in.scales);
@@ -639,21 +636,11 @@ size_t mobgs_project_bwd_scratch_floats(int C, int N) {
     return (size_t)C * ((N + 255) / 256) * 16 + (C > 1 ? (size_t)C * N * 3 : 0);
 }
 
-int mobgs_project_bwd(int C, int N, const float* means, const float* quats, const float* scales,
-                      const float* viewmats, const float* Ks, int width, int height, float eps2d,
-                      const int32_t* radii, const float* conics, const float* v_means2d, const float* v_depths,
-                      const float* v_conics, float* v_means, float* v_quats, float* v_scales,
-                      float* v_viewmats, float* v_viewmats_partial, void* stream) {
-    return mobgs_project_bwd_ex(C, N, 0, means, quats, scales, viewmats, Ks, width, height, eps2d, radii, conics,
-                                v_means2d, v_depths, v_conics, v_means, v_quats, v_scales, v_viewmats,
-                                v_viewmats_partial, stream);
-}
-
-int mobgs_project_bwd_ex(int C, int N, int geometry_per_camera, const float* means, const float* quats,
-                         const float* scales, const float* viewmats, const float* Ks, int width, int height,
-                         float eps2d, const int32_t* radii, const float* conics, const float* v_means2d,
-                         const float* v_depths, const float* v_conics, float* v_means, float* v_quats,
-                         float* v_scales, float* v_viewmats, float* v_viewmats_partial, void* stream) {
+int mobgs_project_bwd(int C, int N, int geometry_per_camera, const float* means, const float* quats,
+                      const float* scales, const float* viewmats, const float* Ks, int width, int height,
+                      float eps2d, const int32_t* radii, const float* conics, const float* v_means2d,
+                      const float* v_depths, const float* v_conics, float* v_means, float* v_quats,
+                      float* v_scales, float* v_viewmats, float* v_viewmats_partial, void* stream) {
     const size_t gs = geometry_per_camera ? (size_t)N : 0;  // rows of means / quats (and their gradients) per camera
     if (C <= 0 || N < 0) {
         set_error("mobgs_project_bwd: bad sizes C=%d N=%d", C, N);
@@ -719,9 +706,10 @@ int mobgs_project_prep_bwd_fused(int N, const float* means, const float* quats, 
     pb.x_means = x_means;
     pb.x_quats = x_quats;
     pb.x_scales = x_scales;
-    pb.g = LeafGrads{grads->s_xyz, grads->s_scaling, grads->s_rotation, grads->s_opacity, grads->s_fdc, grads->s_ft,
-                     grads->d_control, grads->d_scaling, grads->d_rotation, grads->d_omega, grads->d_opacity,
-                     grads->d_fdc, grads->d_ft};
+    auto F = [](void* p) { return static_cast<float*>(p); };  // (float32 leaves only)
+    pb.g = LeafGrads{grads->s_xyz, F(grads->s_scaling), F(grads->s_rotation), F(grads->s_opacity), F(grads->s_fdc),
+                     F(grads->s_ft), grads->d_control, F(grads->d_scaling), F(grads->d_rotation), F(grads->d_omega),
+                     F(grads->d_opacity), F(grads->d_fdc), F(grads->d_ft)};
     const int nblocks = (N + 255) / 256;
     hipLaunchKernelGGL(project_bwd_kernel<true>, dim3(nblocks, 1), dim3(256), 0, (hipStream_t)stream, N, means, quats,
                        scales, viewmats, Ks, width, height, eps2d, radii, conics, v_means2d, v_depths, v_conics,

@@ -219,7 +219,8 @@ def exposure_ratio(cam_flow, latent_flow, q=0.01, scale=1.0, out=None):
     return value, stats
 
 
-REG_ENTROPY, REG_SPARSITY = 1, 2   # include/mobgs_hip.h MOBGS_REG_ENTROPY / MOBGS_REG_SPARSITY
+# include/mobgs_hip.h MOBGS_REG_ENTROPY / MOBGS_REG_SPARSITY
+REG_ENTROPY, REG_SPARSITY = _lib._DEFINES["MOBGS_REG_ENTROPY"], _lib._DEFINES["MOBGS_REG_SPARSITY"]
 
 
 def _numel_or_zero(t):

@@ -1,6 +1,7 @@
 """autograd wrappers of the fused per-splat and per-pixel kernels (prep.hip, decoder.hip)."""
 from __future__ import annotations
 
+import ctypes
 from typing import Optional
 
 import torch
@@ -167,11 +168,11 @@ class PrepSplats(torch.autograd.Function):
         scales = torch.empty(N, 3, dtype=torch.float32, device=dev)
         opac = torch.empty(N, dtype=torch.float32, device=dev)
         colors = torch.empty(*lead, N, 9, dtype=torch.float32, device=dev)
-        fwd = lib.mobgs_prep_fwd_many_f16 if half else lib.mobgs_prep_fwd_many
-        check(fwd(K, Ns, Nd, ptr(times), ptr(s_xyz), ptr(s_scaling), ptr(s_rotation), ptr(s_opacity), ptr(s_fdc),
-                  ptr(s_ft), ptr(d_control), ptr(d_ncp), ptr(d_scaling), ptr(d_rotation), ptr(d_omega),
-                  ptr(d_opacity), ptr(d_fdc), ptr(d_ft), ptr(d_trbf), ptr(means), ptr(quats), ptr(scales), ptr(opac),
-                  ptr(colors), stream()), "mobgs_prep_fwd")
+        rec = _lib.MobgsPrepInputs(Ns, Nd, *map(ptr, (times, s_xyz, s_scaling, s_rotation, s_opacity, s_fdc, s_ft, d_control,
+                                                      d_ncp, d_scaling, d_rotation, d_omega, d_opacity, d_fdc, d_ft,
+                                                      d_trbf)))
+        check(lib.mobgs_prep_fwd(K, ctypes.byref(rec), int(half), ptr(means), ptr(quats), ptr(scales), ptr(opac),
+                                 ptr(colors), stream()), "mobgs_prep_fwd")
         ctx.save_for_backward(times, d_ncp, d_trbf, scales, opac)
         return means, quats, scales, opac, colors
 
@@ -222,12 +223,11 @@ def prep_backward(saved, sizes, leaf_inputs, half, attr_dtypes, v_means, v_quats
             sink.buffers = g
     if F is None:
         c = [f32c(v) if v is not None else None for v in (v_means, v_quats, v_scales, v_opac, v_colors)]
-        bwd = lib.mobgs_prep_bwd_many_f16 if g_half else lib.mobgs_prep_bwd_many
-        check(bwd(times.shape[0] if times.dim() == 2 else 1, Ns, Nd, ptr(times), ptr(d_ncp), ptr(d_trbf), ptr(scales), ptr(opac), ptr(c[0]), ptr(c[1]),
-                  ptr(c[2]), ptr(c[3]), ptr(c[4]), ptr(g["s_xyz"]), ptr(g["s_scaling"]), ptr(g["s_rotation"]),
-                  ptr(g["s_opacity"]), ptr(g["s_fdc"]), ptr(g["s_ft"]), ptr(g["d_control"]), ptr(g["d_scaling"]),
-                  ptr(g["d_rotation"]), ptr(g["d_omega"]), ptr(g["d_opacity"]), ptr(g["d_fdc"]), ptr(g["d_ft"]),
-                  accumulate, stream()), "mobgs_prep_bwd")
+        rec = _lib.MobgsPrepInputs(Ns=Ns, Nd=Nd, times=ptr(times), d_ncp=ptr(d_ncp), d_trbf=ptr(d_trbf))
+        grads = _lib.MobgsLeafGrads(*[ptr(g[n_]) for n_ in _LEAF_NAMES])
+        check(lib.mobgs_prep_bwd(times.shape[0] if times.dim() == 2 else 1, ctypes.byref(rec), ptr(scales), ptr(opac),
+                                 ptr(c[0]), ptr(c[1]), ptr(c[2]), ptr(c[3]), ptr(c[4]), ctypes.byref(grads), int(g_half),
+                                 accumulate, stream()), "mobgs_prep_bwd")
     if not use_sink and not g_half:  # mixed / other dtypes: autograd wants the leaf's dtype back
         names = ("s_scaling", "s_rotation", "s_opacity", "s_fdc", "s_ft", "d_scaling", "d_rotation", "d_omega",
                  "d_opacity", "d_fdc", "d_ft")

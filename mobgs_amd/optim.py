@@ -20,9 +20,7 @@ from ._lib import check, stream
 
 
 class _AdamTensor(ctypes.Structure):
-    _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p),
-                ("exp_avg_sq", ctypes.c_void_p), ("n", ctypes.c_int64), ("step_size", ctypes.c_float),
-                ("bias2_sqrt", ctypes.c_float)]
+    _fields_ = _lib._STRUCTS["MobgsAdamTensor"]  # read from include/mobgs_hip.h
 
 
 def _fusable(opt: torch.optim.Optimizer, group: dict, p: torch.Tensor) -> bool:

@@ -79,10 +79,10 @@ def _project_bwd(saved, dims, v_means2d, v_depths, v_conics):
     g2 = f32c(v_means2d) if v_means2d is not None else None
     gd = f32c(v_depths) if v_depths is not None else None
     gc = f32c(v_conics) if v_conics is not None else None
-    check(lib.mobgs_project_bwd_ex(C, N, 1 if means.dim() == 3 else 0, ptr(means), ptr(quats), ptr(scales),
-                                   ptr(viewmats), ptr(Ks), width, height, eps2d, ptr(radii), ptr(conics), ptr(g2),
-                                   ptr(gd), ptr(gc), ptr(v_means), ptr(v_quats), ptr(v_scales), ptr(v_viewmats),
-                                   ptr(partial), stream()), "mobgs_project_bwd")
+    check(lib.mobgs_project_bwd(C, N, 1 if means.dim() == 3 else 0, ptr(means), ptr(quats), ptr(scales),
+                                ptr(viewmats), ptr(Ks), width, height, eps2d, ptr(radii), ptr(conics), ptr(g2),
+                                ptr(gd), ptr(gc), ptr(v_means), ptr(v_quats), ptr(v_scales), ptr(v_viewmats),
+                                ptr(partial), stream()), "mobgs_project_bwd")
     return v_means, v_quats, v_scales, v_viewmats
 
 

@@ -14,6 +14,9 @@ ops.LeafGradSink, and half attribute storage.  Compared in full, no flip allowan
   * `accumulate`: the first pass alone equals the non-accumulating run bit for bit, the sum obeys the same rules;
   * `half`: the references are evaluated on the half-rounded values, and a gradient stored as half gets the one rounding
     to half on top: 2^-11 |ref| per element (2^-25 below the normal range).
+  * the two host bodies (csrc/fastpath.cpp and the Python one in ops.py fill MobgsPrepInputs / MobgsLeafGrads each on its
+    own): `k3`, `half` and `accumulate` -- a second workgroup, K > 1, the binary16 flag on both records, accumulate = 1 --
+    run with the fast path on and off; every output and leaf gradient is bit-identical, and obeys the rules above.
 k = 3 (three times the fp32 reference's own gap, a rule that needs no run of the code under test).
 
 Worst k needed on an MI355X per family (docs/MEASUREMENT_LOG.md, "Per-splat kernels against float64"):
@@ -54,32 +57,20 @@ def _compare(case, got, ref64, ref32, keys, family, tag):
         S.rows_close_to_f64(g, r64, r32, S.prep_row_strata(case, key), S.COLS[key], K[family], f"{tag} [{family}] {key}")
 
 
-@pytest.mark.parametrize("name", [n for n in S.PREP_CASES if n != "accumulate"])
-def test_prep_matches_float64(hip_device, name):
+def _single_run(case, dev):
+    """One forward + backward pass -> (the five outputs, the 13 leaf gradients)."""
     from mobgs_amd import ops
-    assert tuple(ops._LEAF_NAMES) == S.LEAVES
-    case = S.prep_case(name)
-    ref64, ref32 = S.prep_reference(name)
-    L, args = _leaves(case, hip_device)
+    L, args = _leaves(case, dev)
     outs = ops.PrepSplats.apply(*args(case.times))
-    torch.autograd.backward(outs, [c.to(hip_device) for c in case.cots])
+    torch.autograd.backward(outs, [c.to(dev) for c in case.cots])
     torch.cuda.synchronize()
-    tag = f"prep {name}"
-    assert all(o.dtype == torch.float32 for o in outs)
-    _compare(case, dict(zip(S.PREP_OUTPUTS, outs)), ref64, ref32, S.PREP_OUTPUTS, "outputs", tag)
-    got = {k: L[k].grad for k in S.LEAVES}
-    if case.half:
-        assert all(got[k].dtype == torch.float16 for k in S.HALF_LEAVES) and got["d_control"].dtype == torch.float32
-    _compare(case, got, ref64, ref32, S.LEAVES, "leaves", tag)
-    if case.K == 1:  # the static positions pass their cotangent on untouched
-        assert torch.equal(got["s_xyz"].cpu(), case.cots[0][:case.Ns])
+    return dict(zip(S.PREP_OUTPUTS, outs)), {k: L[k].grad for k in S.LEAVES}
 
 
-def test_prep_accumulates_two_passes_in_a_sink(hip_device):
+def _sink_run(case, dev):
+    """`accumulate`: the first pass alone, then both passes into one ops.LeafGradSink -> (outputs of the first pass, its
+    gradients from the non-accumulating run, the sink's buffers after the first pass, the leaves' .grad after both)."""
     from mobgs_amd import ops
-    case = S.prep_case("accumulate")
-    ref64, ref32 = S.prep_reference("accumulate")
-    dev = hip_device
     L, args = _leaves(case, dev)
     cots1, cots2 = ([c.to(dev) for c in cs] for cs in (case.cots, case.cots2))
     # the non-accumulating run of the first pass
@@ -99,9 +90,60 @@ def test_prep_accumulates_two_passes_in_a_sink(hip_device):
         first = {k: sink.buffers[k].clone() for k in S.LEAVES}
         torch.autograd.backward(outs2, cots2)
     torch.cuda.synchronize()
+    return dict(zip(S.PREP_OUTPUTS, outs1)), plain, first, {k: L[k].grad for k in S.LEAVES}
+
+
+def _check_single(case, outs, got, ref64, ref32, tag):
+    assert all(o.dtype == torch.float32 for o in outs.values())
+    _compare(case, outs, ref64, ref32, S.PREP_OUTPUTS, "outputs", tag)
+    if case.half:
+        assert all(got[k].dtype == torch.float16 for k in S.HALF_LEAVES) and got["d_control"].dtype == torch.float32
+    _compare(case, got, ref64, ref32, S.LEAVES, "leaves", tag)
+    if case.K == 1:  # the static positions pass their cotangent on untouched
+        assert torch.equal(got["s_xyz"].cpu(), case.cots[0][:case.Ns])
+
+
+def _check_sink(case, outs1, plain, first, total, ref64, ref32, tag):
     for k in S.LEAVES:  # the first pass alone: the non-accumulating run, bit for bit
         assert torch.equal(first[k].view_as(plain[k]), plain[k]), k
-    tag = "prep accumulate"
-    _compare(case, dict(zip(S.PREP_OUTPUTS, outs1)), ref64, ref32, S.PREP_OUTPUTS, "outputs", tag)
+    _compare(case, outs1, ref64, ref32, S.PREP_OUTPUTS, "outputs", tag)
     _compare(case, first, ref64["first"], ref32["first"], S.LEAVES, "leaves", tag + " first pass")
-    _compare(case, {k: L[k].grad for k in S.LEAVES}, ref64, ref32, S.LEAVES, "leaves", tag + " sum")
+    _compare(case, total, ref64, ref32, S.LEAVES, "leaves", tag + " sum")
+
+
+@pytest.mark.parametrize("name", [n for n in S.PREP_CASES if n != "accumulate"])
+def test_prep_matches_float64(hip_device, name):
+    from mobgs_amd import ops
+    assert tuple(ops._LEAF_NAMES) == S.LEAVES
+    case = S.prep_case(name)
+    outs, got = _single_run(case, hip_device)
+    _check_single(case, outs, got, *S.prep_reference(name), f"prep {name}")
+
+
+def test_prep_accumulates_two_passes_in_a_sink(hip_device):
+    case = S.prep_case("accumulate")
+    _check_sink(case, *_sink_run(case, hip_device), *S.prep_reference("accumulate"), "prep accumulate")
+
+
+@pytest.mark.parametrize("name", ["k3", "half", "accumulate"])
+def test_prep_host_bodies_agree_bit_for_bit(hip_device, name):
+    """csrc/fastpath.cpp and the Python body of ops.py each fill MobgsPrepInputs / MobgsLeafGrads themselves: a swapped
+    member in one of them shows here as a difference between the two, not only inside a full render."""
+    from mobgs_amd import _fast
+    case = S.prep_case(name)
+    run, check = (_sink_run, _check_sink) if name == "accumulate" else (_single_run, _check_single)
+    was = _fast.enabled
+    results = {}
+    try:
+        for on in (True, False):
+            _fast.reset(on)
+            assert (_fast.get() is not None) == on, _fast.load_error
+            results[on] = run(case, hip_device)
+    finally:
+        _fast.reset(was)
+    for on in (True, False):
+        check(case, *results[on], *S.prep_reference(name), f"prep {name} [fast path {'on' if on else 'off'}]")
+    for i, (a, b) in enumerate(zip(results[True], results[False])):
+        assert a.keys() == b.keys()
+        for k in a:
+            assert a[k].dtype == b[k].dtype and torch.equal(a[k], b[k]), (i, k)

@@ -59,7 +59,7 @@ def test_render_many_equals_separate_renders(hip_device, size, ns, nd):
 
 
 def test_prep_of_k_instants_in_one_launch_equals_k_launches(hip_device):
-    """ops.PrepSplats with times [K,2] (mobgs_prep_{fwd,bwd}_many): row block k of means / quats / colours is the
+    """ops.PrepSplats with times [K,2] (mobgs_prep_fwd / mobgs_prep_bwd with K > 1): row block k of means / quats / colours is the
     single-instant result bit for bit, and the leaf gradients are those of K single-instant backward passes accumulated
     in instant order -- bit for bit as well (LeafGradSink buffers: instant 0 writes, the others add)."""
     import bench as B
