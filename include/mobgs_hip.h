@@ -147,7 +147,7 @@ int mobgs_cotangent_probe(int n_arrays, const float* const* arrays, const size_t
  * points changes (round 4 inserted `records` into mobgs_raster_bwd_reduce and changed the gradient-slot format without
  * one: a stale host extension would have passed shifted pointers).  Bindings compare it with the MOBGS_ABI_VERSION
  * they were built against and refuse to run on a mismatch (mobgs_amd/_lib.py, csrc/fastpath.cpp). */
-#define MOBGS_ABI_VERSION 15
+#define MOBGS_ABI_VERSION 16
 int mobgs_abi_version(void);
 /* Text of the last error raised on the calling thread ("" if none). */
 const char* mobgs_last_error(void);
@@ -924,6 +924,44 @@ int mobgs_reg_terms_fwd(int64_t n_d, const float* depth, const float* gt_depth, 
 int mobgs_reg_terms_bwd(int64_t n_d, const float* depth, const float* gt_depth, int64_t n_a, const float* alpha,
                         int terms, float w_d, float w_e, float w_s, const float* v_loss, float* v_depth,
                         float* v_alpha, void* stream);
+
+/* ---- K22: evaluation metrics of a batch of image pairs -------------------------------------------------------------
+ * What /root/reference/metrics.py:54-79, :123-125 (scikit-image), dycheck_metrics.py:67-200 (jax) and train.py:918-919
+ * compute per image, for B pairs at once, on the caller's stream, forward only (csrc/metrics.hip: 16x16 tiles, the halo
+ * patch in LDS, a separable window; per-workgroup partial rows and a one-workgroup finishing launch; no float atomic, so
+ * a result is bit-identical from run to run and an image's row does not depend on the batch around it).
+ * pred, gt [B,3,H,W] fp32; mask [B,H,W] fp32 in {0, 1}, or NULL (= all ones).  flags: MOBGS_METRICS_CLAMP clamps both
+ * images to [0, 1] first (train.py:903-907); MOBGS_METRICS_QUANTIZE then replaces pred by floor(clip(pred, 0, 1) * 255)
+ * / 255, evaluated in fp32 (eval.py:162 and the / 255 of metrics.py:100: the 8-bit image without writing it).  All
+ * arithmetic after that is float64.  With d = pred - gt, n = 3 H W and M = 3 sum(mask) (the mask broadcast over the
+ * channels), out [B, MOBGS_METRICS_COLUMNS] float64 (device) =
+ *   0 l1              sum |d| / n
+ *   1 mse             sum d^2 / n
+ *   2 psnr            20 log10(1 / sqrt(mse))                                              (utils/image_utils.py:30-31)
+ *   3 psnr_masked     -10 / ln 10 * ln(sum d^2 mask / max(M, 1e-6))                        (dycheck_metrics.py:57-64, :91)
+ *   4 ssim_box        skimage structural_similarity(multichannel=True): 7x7 uniform window with `reflect` borders, sample
+ *                     covariance (x 49 / 48), C1 = (0.01 R)^2, C2 = (0.03 R)^2, R = data_range; per channel the mean of
+ *                     the map cropped by 3 on every side, then the mean of the three
+ *   5 ssim_box_masked sum(map x mask) / (M + 1e-8) over the uncropped map                  (metrics.py:62-64)
+ *   6 ssim_gauss      dycheck's partial-convolution SSIM: 11 taps, sigma 1.5, `valid`; the horizontal pass over z x mask,
+ *                     renormalised by 11 / m_ where the window's mask count m_ != 0 and 0 elsewhere; the vertical pass
+ *                     over that with the mask (m_ != 0), renormalised the same way; variances clipped at 0, the covariance
+ *                     limited to sqrt(s00 s11); the mean of the whole (H - 10) x (W - 10) x 3 map, unmasked
+ *   7 sum d^2 mask    8 M
+ * arms: MOBGS_METRICS_BOX | MOBGS_METRICS_GAUSS, the windows that are evaluated (at least one); the columns of the other
+ *   are NaN.  partial: scratch, mobgs_image_metrics_scratch_doubles(B, H, W) doubles, contents irrelevant on entry.
+ * mobgs_image_metrics_scratch_doubles: a host computation; 0 for a shape outside 1 <= B <= 16384, 1 <= H, W <= 32768.
+ * Refused with MOBGS_E_INVALID before any launch: a shape outside that range, H or W < 7 with the box arm or < 11 with the
+ * Gaussian arm, arms = 0, an unknown bit, a data_range that is not positive and finite, a NULL pred / gt / partial / out,
+ * a misaligned pointer.  The inputs are only read; two or three launches, no synchronisation. */
+#define MOBGS_METRICS_BOX 1
+#define MOBGS_METRICS_GAUSS 2
+#define MOBGS_METRICS_CLAMP 1
+#define MOBGS_METRICS_QUANTIZE 2
+#define MOBGS_METRICS_COLUMNS 9
+size_t mobgs_image_metrics_scratch_doubles(int B, int H, int W);
+int mobgs_image_metrics(int B, int H, int W, const float* pred, const float* gt, const float* mask, int arms, int flags,
+                        double data_range, double* partial, double* out, void* stream);
 
 #ifdef __cplusplus
 }
