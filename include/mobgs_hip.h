@@ -963,6 +963,48 @@ size_t mobgs_image_metrics_scratch_doubles(int B, int H, int W);
 int mobgs_image_metrics(int B, int H, int W, const float* pred, const float* gt, const float* mask, int arms, int flags,
                         double data_range, double* partial, double* out, void* stream);
 
+/* ---- K23: test-time pose refinement: pose head, -PSNR loss, optimiser step ----------------------------------------
+ * The pieces of /root/reference/eval.py:43-166 (render_test_tto) around the render, on the caller's stream, without a
+ * float atomic and without a read-back (csrc/pose.hip, built with -ffp-contract=off).  All pointers are device pointers,
+ * fp32 unless stated, 4-byte aligned.  Entry points only: no struct, signature or scratch format of an earlier ABI
+ * version changes, and MOBGS_ABI_VERSION stays as it is.
+ *
+ * mobgs_pose_head_fwd: q [4] = (r, i, j, k), real part first and NOT normalised; t [3] -> w2c [16], row-major
+ *   [[R, t], [0 0 0 1]] with pytorch3d's quaternion_to_matrix as written (eval.py:122-123): two_s = 2 / (q . q),
+ *   R = [[1 - two_s (jj + kk), two_s (ij - kr), two_s (ik + jr)], [two_s (ij + kr), 1 - two_s (ii + kk), two_s (jk - ir)],
+ *        [two_s (ik - jr), two_s (jk + ir), 1 - two_s (ii + jj)]].  One wave.
+ * mobgs_pose_head_bwd: v_w2c [16] -> v_q [4], v_t [3] = v_w2c[3], [7], [11]: the exact Jacobian of the expression above,
+ *   two_s included, so the component of v_q along q is zero up to rounding.  q = 0 gives NaN, as the reference.  One wave.
+ * mobgs_pose_step: one wave, in this order: (v_q, v_t) = mobgs_pose_head_bwd(q, v_w2c); the Adam update of K16 on the seven
+ *   values with their moments exp_avg, exp_avg_sq [7] (q's four, then t's three), the SAME device code as
+ *   mobgs_adam_step (csrc/adam_shared.h), step_size_q for q and step_size_t for t (lr / (1 - beta1^step), formed by the
+ *   caller as for K16, like bias2_sqrt = sqrt(1 - beta2^step)); w2c = mobgs_pose_head_fwd(q, t) of the updated values;
+ *   v_w2c := 0 (the next step's zero_grad).  q, t, the moments and v_w2c are updated in place; bit-identical with the
+ *   three separate calls.
+ * mobgs_neg_psnr_fwd: pred, gt [n], n = 3 H W values of a [3,H,W] image pair, 1 <= n <= 2^40.
+ *   *mse (float64) = sum (pred - gt)^2 / n, differences and squares in fp32 as eval.py:137 forms them, added in float64;
+ *   *loss (fp32) = -20 log10(1 / sqrt(mse)) (eval.py:138-139), evaluated in float64 and rounded once; -inf for mse == 0.
+ *   Each workgroup adds a fixed contiguous range and a one-workgroup finishing launch adds the partial sums in a
+ *   fixed order that depends on their number alone: which element is added where depends on n alone, so the result is bit-identical from run to run AND from
+ *   address to address.  A 16-byte aligned array is read 16 bytes at a time, another one element by element.
+ *   partial: scratch, mobgs_neg_psnr_scratch_doubles(n) doubles (a host computation; 0 for n outside the range), contents
+ *   irrelevant on entry.  Two launches.  The inputs are only read.
+ * mobgs_neg_psnr_bwd: v_pred [n] = v_loss 20 / (ln 10 n mse) (pred - gt): the factor from *mse (device, as the forward
+ *   left it) and *v_loss (device; NULL = 1) in float64, rounded once; the product in fp32.  mse == 0 gives NaN everywhere,
+ *   as autograd does.  v_pred is fully written.  One launch.
+ * Refused with MOBGS_E_INVALID before any launch: a NULL pointer (v_loss excepted), a misaligned one (partial and mse:
+ * 8 bytes), n outside the range. */
+int mobgs_pose_head_fwd(const float* q, const float* t, float* w2c, void* stream);
+int mobgs_pose_head_bwd(const float* q, const float* v_w2c, float* v_q, float* v_t, void* stream);
+int mobgs_pose_step(float* q, float* t, float* v_w2c, float* exp_avg, float* exp_avg_sq, float step_size_q,
+                    float step_size_t, float bias2_sqrt, double beta1, double beta2, double eps, float* w2c,
+                    void* stream);
+size_t mobgs_neg_psnr_scratch_doubles(int64_t n);
+int mobgs_neg_psnr_fwd(int64_t n, const float* pred, const float* gt, double* partial, double* mse, float* loss,
+                       void* stream);
+int mobgs_neg_psnr_bwd(int64_t n, const float* pred, const float* gt, const double* mse, const float* v_loss,
+                       float* v_pred, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,7 @@
 // /root/reference/scene/gaussian_model.py:1044-1155 (prune_points, cat_tensors_to_optimizer,
 // densification_postfix), :1207-1244 (densify_and_splitv2), :1352-1356 (add_densification_stats), :1480-1506
 // (densify_and_clone) and /root/reference/helper_train.py:263 (max_radii2D update).
+#include "adam_shared.h"
 #include "common.h"
 
 namespace mobgs {
@@ -158,12 +159,7 @@ __global__ void __launch_bounds__(256) adam_step_kernel(AdamTable tab, float w1,
     const int64_t i0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     if (i0 >= T.n) return;
     auto one = [&](float& p, float g, float& m, float& v) {
-        m = m + w1 * (g - m);                  // exp_avg.lerp_(grad, 1 - beta1)
-        // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2); torch.optim.Adam's multi-tensor addcmul forms
-        // grad * grad first, so |grad| >= 1.9e19 overflows to inf there -- (w2 * g) * g stayed finite up to 5.8e20
-        v = v * beta2 + w2 * (g * g);
-        const float denom = sqrtf(v) / T.bias2_sqrt + eps;
-        p = p - T.step_size * (m / denom);     // param.addcdiv_(exp_avg, denom, value = -step_size)
+        mobgs::adam_update(p, g, m, v, w1, beta2, w2, eps, T.step_size, T.bias2_sqrt);   // csrc/adam_shared.h
     };
     if (i0 + 4 <= T.n && ((((uintptr_t)T.param | (uintptr_t)T.grad | (uintptr_t)T.exp_avg | (uintptr_t)T.exp_avg_sq) & 15) == 0)) {
         float4 p = *reinterpret_cast<float4*>(T.param + i0);

@@ -14,8 +14,8 @@ are four times what the images' own range would give.  This is a reading of that
 here.  So `data_range` is a required keyword of everything below that evaluates the box SSIM, and evaluate_views defaults
 to 2.0 (README, "UNPINNED").
 
-Not here: LPIPS (the AlexNet trunk weights are not available), tOF (OpenCV's Farneback flow), the test-time pose
-optimisation of eval.py, gradients.
+Not here: LPIPS (the AlexNet trunk weights are not available), tOF (OpenCV's Farneback flow), gradients.  The test-time pose
+optimisation of eval.py is mobgs_amd.tto, which scores its images through image_metrics(clamp=True, quantize=True).
 """
 from __future__ import annotations
 
