@@ -1005,6 +1005,59 @@ int mobgs_neg_psnr_fwd(int64_t n, const float* pred, const float* gt, double* pa
 int mobgs_neg_psnr_bwd(int64_t n, const float* pred, const float* gt, const double* mse, const float* v_loss,
                        float* v_pred, void* stream);
 
+/* ---- K24: LPIPS (net-lin, AlexNet trunk, v0.1, spatial average, no mask) of a batch of image pairs -----------------
+ * What /root/reference/metrics.py:84-85, :127-131 and eval.py:76 evaluate (models/networks_basic.py:68-105,
+ * models/pretrained_networks.py:57-95), forward only, on the caller's stream (csrc/lpips.hip).  Entry points only:
+ * MOBGS_ABI_VERSION stays as it is.  All device pointers fp32 unless stated.
+ *
+ * The computation, per pair (img0, img1), both [3,H,W]:
+ *   x = img (MOBGS_LPIPS_UNIT_RANGE: 2 img - 1), then (x - shift_c) / scale_c with shift (-.030, -.088, -.188) and scale
+ *   (.458, .448, .450); the trunk conv(3->64, k 11, stride 4, pad 2) ReLU [tap 1] maxpool(3, 2) conv(64->192, k 5, pad 2) ReLU
+ *   [tap 2] maxpool(3, 2) conv(192->384, k 3, pad 1) ReLU [tap 3] conv(384->256, k 3, pad 1) ReLU [tap 4] conv(256->256, k 3,
+ *   pad 1) ReLU [tap 5], every convolution with a bias and zero padding of its own input (the first one pads the SCALED
+ *   tensor); per tap and pixel n = f / (sqrt(sum_c f^2) + 1e-10) for both images, sum_c lin_c (n0 - n1)^2, the mean over
+ *   the tap's pixels; the total is the sum of the five layer values.
+ * The convolutions are implicit GEMMs on v_mfma_f32_32x32x2_f32 (exact fp32: every output is one k-ordered fmaf chain over
+ * K = (ky, kx, ci), whatever tile it falls into); activations are channel-last [2B, h, w, C] with image 2b = img0 of pair b
+ * and 2b + 1 = img1.  Norms, differences and the head dot product are fp32; a workgroup's sum over its 64 pixels and
+ * everything after it is float64, in an order that depends on the tap's size alone; no float atomics.  So a pair's row
+ * is bit-identical from run to run, whatever B is and wherever the pair sits in the batch, and exactly 0 for equal images.
+ *
+ * MobgsLpipsWeights (host struct, read before the call returns; device pointers, 16-byte aligned):
+ *   w1 .. w5    the convolution weights PACKED [Kpad, Cout]: row k = (ky * ks + kx) * Cin + ci for layers 2 .. 5, row
+ *               k = (ci * 11 + ky) * 11 + kx for layer 1 (Cin = 3: the image is read channel-first), rows K .. Kpad - 1
+ *               zero.  Kpad = mobgs_lpips_pack_k(layer): K rounded up to the kernel's K step (363 -> 384; the others are
+ *               multiples of it already).  layer = 1 .. 5; 0 for another value.
+ *   b1 .. b5    the biases [Cout];  lin1 .. lin5: the head weights [Cout] (>= 0).
+ * flags: MOBGS_LPIPS_UNIT_RANGE: the images are in [0, 1] and are mapped to [-1, 1] inside (without it they are taken as
+ *   [-1, 1] already); MOBGS_LPIPS_CLAMP: both images are clamped to [0, 1] first; MOBGS_LPIPS_QUANTIZE: img1, the
+ *   prediction in the reference's call order, is then replaced by floor(clip(img1, 0, 1) * 255) / 255 in fp32 (eval.py:162,
+ *   as K22 does).  Clamp and quantize act on the values as given, before the 2 x - 1.
+ * scratch: mobgs_lpips_scratch_bytes(B, H, W) bytes, 256-byte aligned, contents irrelevant on entry (two activation
+ *   regions the layers alternate between, and the float64 partial sums).  A host computation; 0 for a shape that is
+ *   refused.  Scratch grows with B: callers with a budget split the batch, which does not change a bit of any pair's row.
+ * out [B, MOBGS_LPIPS_COLUMNS] float64 (device): the total, then the five layer values.
+ * taps: NULL, or a HOST array of five device pointers (16-byte aligned) that receive the ReLU maps [2B, h_l, w_l, C_l] of
+ *   all images, channel-last; the layers then read their input from there.  Sizes: h_1 = (H - 7) / 4 + 1, pooled
+ *   p = (h - 3) / 2 + 1, h_2 = p(h_1), h_3 = h_4 = h_5 = p(h_2) (integer division; widths alike); C = 64, 192, 384, 256, 256.
+ * Refused with MOBGS_E_INVALID before any launch, under the entry point's name: a NULL pointer (taps excepted, but not one
+ *   of its five), B < 1 or B > 4096, H or W < 31 (below that the second pool has no output) or > 16384, 2 B h_1 w_1 > 2^30,
+ *   an unknown flag, a misaligned pointer, scratch_bytes smaller than the size query's answer.
+ * 13 launches (5 convolutions, 2 pools, 5 distance kernels, one finishing workgroup), no synchronisation, no read-back. */
+#define MOBGS_LPIPS_UNIT_RANGE 1
+#define MOBGS_LPIPS_CLAMP 2
+#define MOBGS_LPIPS_QUANTIZE 4
+#define MOBGS_LPIPS_COLUMNS 6
+typedef struct MobgsLpipsWeights {
+    const float *w1, *w2, *w3, *w4, *w5;
+    const float *b1, *b2, *b3, *b4, *b5;
+    const float *lin1, *lin2, *lin3, *lin4, *lin5;
+} MobgsLpipsWeights;
+size_t mobgs_lpips_scratch_bytes(int B, int H, int W);
+int mobgs_lpips_pack_k(int layer);
+int mobgs_lpips_alex(int B, int H, int W, const float* img0, const float* img1, const MobgsLpipsWeights* weights,
+                     int flags, void* scratch, size_t scratch_bytes, double* out, float* const* taps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -140,6 +140,12 @@ class MobgsLeafGrads(ctypes.Structure):
     _fields_ = _STRUCTS["MobgsLeafGrads"]
 
 
+class MobgsLpipsWeights(ctypes.Structure):
+    """include/mobgs_hip.h MobgsLpipsWeights: packed convolution weights, biases and head weights of the five layers
+    (device pointers)."""
+    _fields_ = _STRUCTS["MobgsLpipsWeights"]
+
+
 def _bind(lib, name, restype, argtypes):
     fn = getattr(lib, name)
     fn.restype = restype

@@ -1,0 +1,441 @@
+// K24: LPIPS (net-lin, AlexNet trunk, version 0.1, spatial average) of a batch of image pairs (include/mobgs_hip.h): the
+// reference's models/networks_basic.py:68-105 over models/pretrained_networks.py:57-95.  Forward only.  gfx950 only.
+//
+//   lpips_conv_kernel<FIRST>   a convolution + bias + ReLU as an implicit GEMM on v_mfma_f32_32x32x2_f32: M = the output
+//                              pixels of all 2B images, N = Cout, K = Cin k k.  One workgroup (4 waves) owns a 128 x 64 tile
+//                              of the output and walks K in steps of 32: the 128 x 32 patch slab and the 32 x 64 weight
+//                              slab go to LDS, each wave holds two 32 x 32 accumulators (64 rows x 32 columns).  Activations
+//                              are channel-last and Cin is a multiple of 32 from layer 2 on, so a K step lies inside one
+//                              (ky, kx) tap and a pixel's part of the slab is 128 contiguous bytes, or zeros in the padding.
+//                              FIRST: the slab is gathered from the caller's [B,3,H,W] images, with the clamp, the 8-bit
+//                              truncation, 2 x - 1 and the scaling layer applied on load; K = 363 is padded to 384 with
+//                              zero weight rows, there is no tail path.
+//   lpips_pool_kernel          maxpool(3, stride 2, floor), a kernel of its own, channel-last, four channels per thread.
+//   lpips_dist_kernel          one wave per pixel of a pair: both feature vectors are read once (<= 6 values per lane and
+//                              image), the two norms, the normalised squared difference and the head dot product are fp32,
+//                              reduced over the wave by a butterfly (every lane ends with the same bits); the wave adds
+//                              its 16 pixels in float64, the workgroup its 4 waves, into ONE float64 partial sum.
+//   lpips_finish_kernel        one workgroup, one wave per pair: per layer the lanes add contiguous runs of the partial sums
+//                              and a butterfly adds the lane sums (float64, an order that depends on the tap's size
+//                              alone), divides by the tap's pixels, adds the five layer values.
+//
+// Every output of a convolution is one k-ordered fmaf chain (the fp32 MFMA adds nothing wider), the same chain whatever tile
+// or row of a tile the pixel falls into; the workgroups of the distance kernel are cut per pair.  No float atomic, no
+// hand-off between workgroups inside a launch.  So a pair's result is bit-identical from run to run, whatever the batch
+// around it; and with equal images both feature vectors, norms and normalised values are equal and every difference is 0.
+#include "common.h"
+
+namespace mobgs {
+
+typedef float lp_f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int LP_LAYERS = 5;
+constexpr int LP_BM = 128, LP_BN = 64, LP_BK = 32, LP_THREADS = 256;
+constexpr int LP_APITCH = LP_BK + 1;         // sA[m][k]: the 32 lanes of a fragment read 32 rows -> 32 banks
+constexpr int LP_FINISH_THREADS = 1024;
+constexpr int LP_DPIX = 64;                  // pixels per workgroup of the distance kernel (16 per wave)
+constexpr int LP_MAX_B = 4096, LP_MAX_EDGE = 16384, LP_MIN_EDGE = 31;
+constexpr long long LP_MAX_M = 1ll << 30;
+constexpr int LP_K1 = 363;
+static_assert(MOBGS_LPIPS_COLUMNS == LP_LAYERS + 1, "out columns of include/mobgs_hip.h");
+
+static const int LP_CIN[LP_LAYERS] = {3, 64, 192, 384, 256};
+static const int LP_COUT[LP_LAYERS] = {64, 192, 384, 256, 256};
+static const int LP_KS[LP_LAYERS] = {11, 5, 3, 3, 3};
+static const int LP_STRIDE[LP_LAYERS] = {4, 1, 1, 1, 1};
+static const int LP_PAD[LP_LAYERS] = {2, 2, 1, 1, 1};
+
+struct LpConvArgs {
+    const float* in;                 // [N, Hi, Wi, Cin] channel-last (layers 2 .. 5)
+    const float *img0, *img1;        // [B,3,Hi,Wi] (layer 1)
+    const float *w, *bias;           // [Kpad, Cout], [Cout]
+    float* out;                      // [N, Ho, Wo, Cout]
+    int N, Hi, Wi, Cin, Ho, Wo, Cout, ks, stride, pad, Kpad, M, flags;
+};
+
+__device__ __forceinline__ float lp_clamp01(float x) { return x < 0.f ? 0.f : (x > 1.f ? 1.f : x); }
+
+// the value the first convolution sees at (image n = 2 b + s, channel c, y, x): inside the image only
+__device__ __forceinline__ float lp_input(const LpConvArgs& a, int n, int c, int y, int x) {
+    const int s = n & 1;
+    const float* img = s ? a.img1 : a.img0;
+    float v = img[(((size_t)(n >> 1) * 3 + c) * a.Hi + y) * a.Wi + x];
+    if (a.flags & MOBGS_LPIPS_CLAMP) v = lp_clamp01(v);
+    if ((a.flags & MOBGS_LPIPS_QUANTIZE) && s) v = floorf(lp_clamp01(v) * 255.f) / 255.f;
+    if (a.flags & MOBGS_LPIPS_UNIT_RANGE) v = 2.f * v - 1.f;
+    const float shift = c == 0 ? -.030f : (c == 1 ? -.088f : -.188f);
+    const float scale = c == 0 ? .458f : (c == 1 ? .448f : .450f);
+    return (v - shift) / scale;
+}
+
+template <bool FIRST>
+__global__ void __launch_bounds__(LP_THREADS) lpips_conv_kernel(LpConvArgs a) {
+    __shared__ float sA[LP_BM * LP_APITCH];
+    __shared__ __attribute__((aligned(16))) float sB[LP_BK * LP_BN];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int n_tiles = a.Cout / LP_BN;
+    const int m0 = (int)(blockIdx.x / n_tiles) * LP_BM, n0 = (int)(blockIdx.x % n_tiles) * LP_BN;
+    // the slab rows this thread stages: r = (t >> 3) + 32 j, four consecutive k at 4 (t & 7)
+    const int kq = (t & 7) * 4;
+    int img_n[4], iy0[4], ix0[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int m = m0 + (t >> 3) + 32 * j;
+        const bool row = m < a.M;                        // a row past M: zeros, never stored
+        const int mm = row ? m : 0, q = mm / a.Wo;
+        img_n[j] = row ? q / a.Ho : -1;
+        iy0[j] = (q % a.Ho) * a.stride - a.pad;
+        ix0[j] = (mm % a.Wo) * a.stride - a.pad;
+    }
+    lp_f32x16 acc[2];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[0][i] = acc[1][i] = 0.f;
+    const int wm = (wave & 1) * 64, wn = (wave >> 1) * 32;
+
+    for (int k0 = 0; k0 < a.Kpad; k0 += LP_BK) {
+        // ---- stage the slabs (registers first, so the loads are in flight together) ----
+        float4 va[4];
+        if (FIRST) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float e[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int k = k0 + kq + i;
+                    const int c = k / 121, r = k - c * 121, ky = r / 11, kx = r - ky * 11;
+                    const int y = iy0[j] + ky, x = ix0[j] + kx;
+                    const bool in = img_n[j] >= 0 && k < LP_K1 && y >= 0 && y < a.Hi && x >= 0 && x < a.Wi;
+                    e[i] = in ? lp_input(a, img_n[j], c, y, x) : 0.f;
+                }
+                va[j] = make_float4(e[0], e[1], e[2], e[3]);
+            }
+        } else {
+            const int tap = k0 / a.Cin, c0 = k0 - tap * a.Cin, ky = tap / a.ks, kx = tap - ky * a.ks;   // (uniform)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int y = iy0[j] + ky, x = ix0[j] + kx;
+                const bool in = img_n[j] >= 0 && y >= 0 && y < a.Hi && x >= 0 && x < a.Wi;
+                va[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (in)
+                    va[j] = *reinterpret_cast<const float4*>(a.in + (((size_t)img_n[j] * a.Hi + y) * a.Wi + x) * a.Cin +
+                                                             c0 + kq);
+            }
+        }
+        const float* pw = a.w + (size_t)(k0 + (t >> 4)) * a.Cout + n0 + (t & 15) * 4;
+        const float4 vb0 = *reinterpret_cast<const float4*>(pw);
+        const float4 vb1 = *reinterpret_cast<const float4*>(pw + (size_t)16 * a.Cout);
+        __syncthreads();                                 // the previous step has read sA, sB
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float* p = sA + ((t >> 3) + 32 * j) * LP_APITCH + kq;
+            p[0] = va[j].x;
+            p[1] = va[j].y;
+            p[2] = va[j].z;
+            p[3] = va[j].w;
+        }
+        *reinterpret_cast<float4*>(sB + (t >> 4) * LP_BN + (t & 15) * 4) = vb0;
+        *reinterpret_cast<float4*>(sB + ((t >> 4) + 16) * LP_BN + (t & 15) * 4) = vb1;
+        __syncthreads();
+        // ---- 16 k-steps of 2: lane l holds A[row l & 31][k = l >> 5] and B[k = l >> 5][column l & 31] ----
+        const float* pa = sA + (wm + (lane & 31)) * LP_APITCH + (lane >> 5);
+        const float* pb = sB + (lane >> 5) * LP_BN + wn + (lane & 31);
+#pragma unroll
+        for (int s = 0; s < LP_BK / 2; ++s) {
+            const float b = pb[2 * s * LP_BN];
+            const float a0 = pa[2 * s], a1 = pa[32 * LP_APITCH + 2 * s];
+            acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b, acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b, acc[1], 0, 0, 0);
+        }
+    }
+    // ---- bias + ReLU; accumulator register i of lane l is row (i & 3) + 8 (i >> 2) + 4 (l >> 5), column l & 31 ----
+    const int col = n0 + wn + (lane & 31);
+    const float bias = a.bias[col];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int m = m0 + wm + 32 * h + (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5);
+            if (m < a.M) {
+                const float v = acc[h][i] + bias;
+                a.out[(size_t)m * a.Cout + col] = v > 0.f ? v : 0.f;
+            }
+        }
+    }
+}
+
+// in [N, Hi, Wi, C] -> out [N, Ho, Wo, C], Ho = (Hi - 3) / 2 + 1: every window lies inside the input
+__global__ void __launch_bounds__(LP_THREADS) lpips_pool_kernel(const float* __restrict__ in, float* __restrict__ out,
+                                                                int Hi, int Wi, int Ho, int Wo, int C4, size_t total) {
+    const size_t idx = (size_t)blockIdx.x * LP_THREADS + threadIdx.x;
+    if (idx >= total) return;
+    const int c = (int)(idx % C4);
+    size_t q = idx / C4;
+    const int ox = (int)(q % Wo);
+    q /= Wo;
+    const int oy = (int)(q % Ho);
+    const size_t n = q / Ho;
+    const float4* p = reinterpret_cast<const float4*>(in) + ((n * Hi + 2 * oy) * Wi + 2 * ox) * C4 + c;
+    float4 m = p[0];
+#pragma unroll
+    for (int dy = 0; dy < 3; ++dy) {
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx) {
+            const float4 v = p[((size_t)dy * Wi + dx) * C4];
+            m.x = fmaxf(m.x, v.x);
+            m.y = fmaxf(m.y, v.y);
+            m.z = fmaxf(m.z, v.z);
+            m.w = fmaxf(m.w, v.w);
+        }
+    }
+    reinterpret_cast<float4*>(out)[idx] = m;
+}
+
+__device__ __forceinline__ float lp_wave_sum(float v) {
+#pragma unroll
+    for (int off = MOBGS_WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, MOBGS_WAVE);
+    return v;                                            // (a + b == b + a: every lane holds the same bits)
+}
+
+// feat [2B, P, C] (P pixels per image), lin [C]; grid (rows, B); partial[b * rows_total + row_off + blockIdx.x]
+__global__ void __launch_bounds__(LP_THREADS) lpips_dist_kernel(const float* __restrict__ feat,
+                                                                const float* __restrict__ lin, int P, int C,
+                                                                int rows_total, int row_off,
+                                                                double* __restrict__ partial) {
+    __shared__ double s_wave[LP_THREADS / MOBGS_WAVE];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const size_t pair = blockIdx.y;
+    const float* f0 = feat + (2 * pair) * (size_t)P * C;
+    const float* f1 = f0 + (size_t)P * C;
+    const int nj = C / MOBGS_WAVE;                       // 1, 3, 6, 4, 4
+    float w[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) w[j] = j < nj ? lin[lane + MOBGS_WAVE * j] : 0.f;
+    double sum = 0.0;
+    for (int i = 0; i < LP_DPIX / 4; ++i) {
+        const int p = blockIdx.x * LP_DPIX + 4 * i + wave;
+        if (p >= P) break;                               // (uniform over the wave)
+        float u[6], v[6], su = 0.f, sv = 0.f;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            u[j] = j < nj ? f0[(size_t)p * C + lane + MOBGS_WAVE * j] : 0.f;
+            v[j] = j < nj ? f1[(size_t)p * C + lane + MOBGS_WAVE * j] : 0.f;
+            su += u[j] * u[j];
+            sv += v[j] * v[j];
+        }
+        const float du = sqrtf(lp_wave_sum(su)) + 1e-10f, dv = sqrtf(lp_wave_sum(sv)) + 1e-10f;
+        float d = 0.f;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            const float e = u[j] / du - v[j] / dv;
+            d += w[j] * (e * e);
+        }
+        sum += (double)lp_wave_sum(d);
+    }
+    if (lane == 0) s_wave[wave] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        partial[pair * rows_total + row_off + blockIdx.x] = ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
+}
+
+struct LpFinishArgs {
+    int B, rows_total;
+    int rows[LP_LAYERS], row_off[LP_LAYERS];
+    double pixels[LP_LAYERS];
+};
+
+// one workgroup of LP_FINISH_THREADS; wave v owns the pairs v, v + 16, ...: per layer its lanes add contiguous runs of the
+// partial sums, a butterfly adds the 64 lane sums (a + b == b + a: every lane holds the same bits)
+__global__ void __launch_bounds__(LP_FINISH_THREADS) lpips_finish_kernel(LpFinishArgs a, const double* __restrict__ partial,
+                                                                         double* __restrict__ out) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int b = wave; b < a.B; b += LP_FINISH_THREADS / MOBGS_WAVE) {
+        double total = 0.0;
+        for (int l = 0; l < LP_LAYERS; ++l) {
+            const double* p = partial + (size_t)b * a.rows_total + a.row_off[l];
+            const int rows = a.rows[l], per = (rows + MOBGS_WAVE - 1) / MOBGS_WAVE;
+            const int r0 = min(lane * per, rows), r1 = min(r0 + per, rows);
+            double s = 0.0;
+            for (int r = r0; r < r1; ++r) s += p[r];
+#pragma unroll
+            for (int off = MOBGS_WAVE / 2; off > 0; off >>= 1) s += __shfl_xor(s, off, MOBGS_WAVE);
+            const double v = s / a.pixels[l];
+            if (lane == 0) out[(size_t)b * MOBGS_LPIPS_COLUMNS + 1 + l] = v;
+            total += v;
+        }
+        if (lane == 0) out[(size_t)b * MOBGS_LPIPS_COLUMNS] = total;
+    }
+}
+
+// ---- host: sizes and the scratch layout ------------------------------------------------------------------------------
+struct LpPlan {
+    int h[LP_LAYERS], w[LP_LAYERS];      // the taps
+    int ph[2], pw[2];                    // the two pooled maps
+    int rows[LP_LAYERS], row_off[LP_LAYERS], rows_total;
+    size_t region[2], off_region[2], off_partial, bytes;
+};
+
+static size_t lp_align(size_t x) { return (x + 255) & ~(size_t)255; }
+
+static bool lp_plan(int B, int H, int W, LpPlan& p) {
+    if (B < 1 || B > LP_MAX_B || H < LP_MIN_EDGE || W < LP_MIN_EDGE || H > LP_MAX_EDGE || W > LP_MAX_EDGE) return false;
+    p.h[0] = (H - 7) / 4 + 1;
+    p.w[0] = (W - 7) / 4 + 1;
+    p.ph[0] = (p.h[0] - 3) / 2 + 1;
+    p.pw[0] = (p.w[0] - 3) / 2 + 1;
+    p.h[1] = p.ph[0];
+    p.w[1] = p.pw[0];
+    p.ph[1] = (p.h[1] - 3) / 2 + 1;
+    p.pw[1] = (p.w[1] - 3) / 2 + 1;
+    for (int l = 2; l < LP_LAYERS; ++l) {
+        p.h[l] = p.ph[1];
+        p.w[l] = p.pw[1];
+    }
+    if ((long long)2 * B * p.h[0] * p.w[0] > LP_MAX_M) return false;
+    const size_t N = 2 * (size_t)B;
+    size_t tap[LP_LAYERS], pool[2];
+    p.rows_total = 0;
+    for (int l = 0; l < LP_LAYERS; ++l) {
+        tap[l] = N * p.h[l] * p.w[l] * LP_COUT[l];
+        p.rows[l] = (p.h[l] * p.w[l] + LP_DPIX - 1) / LP_DPIX;
+        p.row_off[l] = p.rows_total;
+        p.rows_total += p.rows[l];
+    }
+    for (int i = 0; i < 2; ++i) pool[i] = N * p.ph[i] * p.pw[i] * LP_COUT[i];
+    // the layers alternate between two regions: tap 1 -> X, pool -> Y, tap 2 -> X, pool -> Y, tap 3 -> X, tap 4 -> Y, tap 5 -> X
+    size_t x = tap[0], y = pool[0];
+    x = tap[1] > x ? tap[1] : x;
+    x = tap[2] > x ? tap[2] : x;
+    x = tap[4] > x ? tap[4] : x;
+    y = pool[1] > y ? pool[1] : y;
+    y = tap[3] > y ? tap[3] : y;
+    p.region[0] = x;
+    p.region[1] = y;
+    p.off_region[0] = 0;
+    p.off_region[1] = lp_align(x * sizeof(float));
+    p.off_partial = p.off_region[1] + lp_align(y * sizeof(float));
+    p.bytes = p.off_partial + lp_align((size_t)B * p.rows_total * sizeof(double));
+    return true;
+}
+
+}  // namespace mobgs
+
+using namespace mobgs;
+
+extern "C" {
+
+size_t mobgs_lpips_scratch_bytes(int B, int H, int W) {
+    LpPlan p;
+    return lp_plan(B, H, W, p) ? p.bytes : 0;
+}
+
+int mobgs_lpips_pack_k(int layer) {
+    if (layer < 1 || layer > LP_LAYERS) return 0;
+    const int K = LP_CIN[layer - 1] * LP_KS[layer - 1] * LP_KS[layer - 1];
+    return (K + LP_BK - 1) / LP_BK * LP_BK;
+}
+
+int mobgs_lpips_alex(int B, int H, int W, const float* img0, const float* img1, const MobgsLpipsWeights* weights,
+                     int flags, void* scratch, size_t scratch_bytes, double* out, float* const* taps, void* stream) {
+    LpPlan p;
+    if (!lp_plan(B, H, W, p)) {
+        set_error("mobgs_lpips_alex: B = %d, H = %d, W = %d outside 1 <= B <= %d, %d <= H, W <= %d, 2 B h1 w1 <= 2^30 (below "
+                  "31 the second pool has no output)", B, H, W, LP_MAX_B, LP_MIN_EDGE, LP_MAX_EDGE);
+        return MOBGS_E_INVALID;
+    }
+    if (flags & ~(MOBGS_LPIPS_UNIT_RANGE | MOBGS_LPIPS_CLAMP | MOBGS_LPIPS_QUANTIZE)) {
+        set_error("mobgs_lpips_alex: flags = %d has unknown bits", flags);
+        return MOBGS_E_INVALID;
+    }
+    if (!img0 || !img1 || !weights || !scratch || !out) {
+        set_error("mobgs_lpips_alex: NULL img0, img1, weights, scratch or out");
+        return MOBGS_E_INVALID;
+    }
+    const float* w[LP_LAYERS] = {weights->w1, weights->w2, weights->w3, weights->w4, weights->w5};
+    const float* bias[LP_LAYERS] = {weights->b1, weights->b2, weights->b3, weights->b4, weights->b5};
+    const float* lin[LP_LAYERS] = {weights->lin1, weights->lin2, weights->lin3, weights->lin4, weights->lin5};
+    for (int l = 0; l < LP_LAYERS; ++l) {
+        if (!w[l] || !bias[l] || !lin[l] || (taps && !taps[l])) {
+            set_error("mobgs_lpips_alex: NULL weight, bias, head or tap pointer of layer %d", l + 1);
+            return MOBGS_E_INVALID;
+        }
+        if (((uintptr_t)w[l] & 15) || ((uintptr_t)bias[l] & 3) || ((uintptr_t)lin[l] & 3) ||
+            (taps && ((uintptr_t)taps[l] & 15))) {
+            set_error("mobgs_lpips_alex: layer %d: packed weights and taps must be 16-byte aligned, biases and heads 4-byte",
+                      l + 1);
+            return MOBGS_E_INVALID;
+        }
+    }
+    if (((uintptr_t)img0 & 3) || ((uintptr_t)img1 & 3) || ((uintptr_t)scratch & 255) || ((uintptr_t)out & 7)) {
+        set_error("mobgs_lpips_alex: images must be 4-byte aligned, scratch 256-byte aligned, out 8-byte aligned");
+        return MOBGS_E_INVALID;
+    }
+    if (scratch_bytes < p.bytes) {
+        set_error("mobgs_lpips_alex: scratch_bytes = %zu, mobgs_lpips_scratch_bytes(%d, %d, %d) = %zu", scratch_bytes, B, H,
+                  W, p.bytes);
+        return MOBGS_E_INVALID;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    char* base = (char*)scratch;
+    float* region[2] = {(float*)(base + p.off_region[0]), (float*)(base + p.off_region[1])};
+    double* partial = (double*)(base + p.off_partial);
+    const int N = 2 * B;
+    static const int tap_region[LP_LAYERS] = {0, 0, 0, 1, 0};
+    const float* cur = nullptr;                          // the input of the next convolution
+    int cur_h = H, cur_w = W;
+    for (int l = 0; l < LP_LAYERS; ++l) {
+        float* tap = taps ? taps[l] : region[tap_region[l]];
+        LpConvArgs a;
+        a.in = cur;
+        a.img0 = img0;
+        a.img1 = img1;
+        a.w = w[l];
+        a.bias = bias[l];
+        a.out = tap;
+        a.N = N;
+        a.Hi = cur_h;
+        a.Wi = cur_w;
+        a.Cin = LP_CIN[l];
+        a.Ho = p.h[l];
+        a.Wo = p.w[l];
+        a.Cout = LP_COUT[l];
+        a.ks = LP_KS[l];
+        a.stride = LP_STRIDE[l];
+        a.pad = LP_PAD[l];
+        a.Kpad = mobgs_lpips_pack_k(l + 1);
+        a.M = N * p.h[l] * p.w[l];
+        a.flags = flags;
+        const unsigned blocks = (unsigned)((a.M + LP_BM - 1) / LP_BM) * (unsigned)(a.Cout / LP_BN);
+        if (l == 0)
+            hipLaunchKernelGGL(lpips_conv_kernel<true>, dim3(blocks), dim3(LP_THREADS), 0, s, a);
+        else
+            hipLaunchKernelGGL(lpips_conv_kernel<false>, dim3(blocks), dim3(LP_THREADS), 0, s, a);
+        const int P = p.h[l] * p.w[l];
+        hipLaunchKernelGGL(lpips_dist_kernel, dim3((unsigned)p.rows[l], (unsigned)B), dim3(LP_THREADS), 0, s,
+                           (const float*)tap, lin[l], P, a.Cout, p.rows_total, p.row_off[l], partial);
+        cur = tap;
+        cur_h = p.h[l];
+        cur_w = p.w[l];
+        if (l < 2) {
+            float* pooled = region[1];
+            const int C4 = a.Cout / 4;
+            const size_t total = (size_t)N * p.ph[l] * p.pw[l] * C4;
+            hipLaunchKernelGGL(lpips_pool_kernel, dim3((unsigned)((total + LP_THREADS - 1) / LP_THREADS)), dim3(LP_THREADS),
+                               0, s, (const float*)tap, pooled, cur_h, cur_w, p.ph[l], p.pw[l], C4, total);
+            cur = pooled;
+            cur_h = p.ph[l];
+            cur_w = p.pw[l];
+        }
+    }
+    LpFinishArgs f;
+    f.B = B;
+    f.rows_total = p.rows_total;
+    for (int l = 0; l < LP_LAYERS; ++l) {
+        f.rows[l] = p.rows[l];
+        f.row_off[l] = p.row_off[l];
+        f.pixels[l] = (double)p.h[l] * (double)p.w[l];
+    }
+    hipLaunchKernelGGL(lpips_finish_kernel, dim3(1), dim3(LP_FINISH_THREADS), 0, s, f, (const double*)partial, out);
+    return check_launch("mobgs_lpips_alex");
+}
+
+}  // extern "C"

@@ -1,0 +1,218 @@
+"""LPIPS on the HIP path (csrc/lpips.hip, include/mobgs_hip.h K24): the "net-lin" model with the AlexNet trunk, version
+0.1, spatial average, no mask -- what the reference's metrics.py:84-85, :127-131 and eval.py:76 evaluate -- for a whole
+batch of image pairs in one call, without the reference's models/ package, torchvision or a DataParallel wrapper.
+
+    model = LpipsAlex.from_files(trunk="alexnet-owt-7be5be79.pth", heads=".../models/weights/v0.1/alex.pth", device="cuda")
+    model = LpipsAlex(trunk_state_dict, heads_state_dict, device="cuda")
+    r = model(pred, gt, clamp=False, quantize=False)   # [B,3,H,W] in [0, 1] -> LpipsResult(total [B], per_layer [B,5]) float64
+    v = model.forward(in0, in1)                         # the reference's call: inputs in [-1, 1] -> [B,1,1,1] fp32
+    maps = model.features(img)                          # the five ReLU maps, NCHW, for tests and debugging
+
+mirrors /root/reference/models/networks_basic.py:68-105 (PNetLin.forward, ScalingLayer), models/pretrained_networks.py:57-95
+(the five slices of torchvision's alexnet().features), models/__init__.py:26-44 and metrics.py:49-51.  Forward only, under
+no_grad; tensors must live on a HIP device.
+
+THE WEIGHTS are the caller's: torchvision's AlexNet file for the trunk (keys features.{0,3,6,8,10}.{weight,bias}; other keys,
+the classifier's, are ignored) and the reference's v0.1/alex.pth for the heads (keys lin{0..4}.model.1.weight).  They are
+packed once, at construction, into the K-major layout the convolution kernel reads.  The value a user compares with the
+published one rests on that trunk file (README, "UNPINNED").
+
+Not here: a mask and spatial=True (dycheck's compute_lpips: NotImplementedError), the VGG and SqueezeNet trunks, gradients,
+reduced precision.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import List, NamedTuple
+
+import torch
+
+from . import _lib
+from ._lib import check, f32c, ptr, stream
+
+CIN, COUT = (3, 64, 192, 384, 256), (64, 192, 384, 256, 256)
+KS, STRIDE, PAD = (11, 5, 3, 3, 3), (4, 1, 1, 1, 1), (2, 2, 1, 1, 1)
+TRUNK_INDEX = (0, 3, 6, 8, 10)                      # the convolutions inside torchvision's alexnet().features
+K_STEP = 32                                          # the kernel's K step; mobgs_lpips_pack_k answers with it (tested)
+MIN_EDGE = 31
+UNIT_RANGE, CLAMP, QUANTIZE = (_lib._DEFINES[k] for k in ("MOBGS_LPIPS_UNIT_RANGE", "MOBGS_LPIPS_CLAMP",
+                                                           "MOBGS_LPIPS_QUANTIZE"))
+COLUMNS = _lib._DEFINES["MOBGS_LPIPS_COLUMNS"]
+
+
+class LpipsResult(NamedTuple):
+    total: torch.Tensor          # [B] float64, device: the sum of the five layer values
+    per_layer: torch.Tensor      # [B,5] float64, device
+
+
+def pack_k(layer: int) -> int:
+    """Rows of layer `layer`'s packed weight (1 .. 5): Cin k k rounded up to the kernel's K step."""
+    K = CIN[layer - 1] * KS[layer - 1] ** 2
+    return (K + K_STEP - 1) // K_STEP * K_STEP
+
+
+def tap_sizes(H: int, W: int) -> List[tuple]:
+    """(h, w) of the five ReLU maps of an H x W image; ValueError below 31, where the second pool has no output."""
+    if H < MIN_EDGE or W < MIN_EDGE:
+        raise ValueError(f"LPIPS (AlexNet): H, W >= {MIN_EDGE} (the second max-pool has no output below), got {H} x {W}")
+    def pool(n):
+        return (n - 3) // 2 + 1
+    h1, w1 = (H - 7) // 4 + 1, (W - 7) // 4 + 1
+    h2, w2 = pool(h1), pool(w1)
+    h3, w3 = pool(h2), pool(w2)
+    return [(h1, w1), (h2, w2), (h3, w3), (h3, w3), (h3, w3)]
+
+
+def pack_conv_weight(weight: torch.Tensor, layer: int) -> torch.Tensor:
+    """[Cout, Cin, k, k] -> [Kpad, Cout], the layout of include/mobgs_hip.h K24: row (ky k + kx) Cin + ci for layers 2 .. 5,
+    row (ci 11 + ky) 11 + kx for layer 1, zero rows up to pack_k(layer).  Plain torch, any device."""
+    cout, cin, k = COUT[layer - 1], CIN[layer - 1], KS[layer - 1]
+    if tuple(weight.shape) != (cout, cin, k, k):
+        raise ValueError(f"pack_conv_weight: layer {layer} needs [{cout}, {cin}, {k}, {k}], got {tuple(weight.shape)}")
+    rows = weight.reshape(cout, -1).t() if layer == 1 else weight.permute(2, 3, 1, 0).reshape(-1, cout)
+    packed = weight.new_zeros(pack_k(layer), cout)
+    packed[:rows.shape[0]] = rows
+    return packed.contiguous()
+
+
+def unpack_conv_weight(packed: torch.Tensor, layer: int) -> torch.Tensor:
+    """The inverse of pack_conv_weight (the padding rows are dropped)."""
+    cout, cin, k = COUT[layer - 1], CIN[layer - 1], KS[layer - 1]
+    rows = packed[:cin * k * k]
+    if layer == 1:
+        return rows.t().reshape(cout, cin, k, k).contiguous()
+    return rows.reshape(k, k, cin, cout).permute(3, 2, 0, 1).contiguous()
+
+
+def check_state_dicts(trunk, heads):
+    """-> (five conv weights [Cout,Cin,k,k], five biases [Cout], five head vectors [Cout]), fp32 on the host.  A missing
+    key, a wrong shape or a dtype that is no floating point raises ValueError naming the key."""
+    def take(sd, key, shape, what):
+        if not hasattr(sd, "keys") or key not in sd:
+            raise ValueError(f"LpipsAlex: the {what} state dict has no key {key!r}")
+        t = sd[key]
+        if not torch.is_tensor(t):
+            raise ValueError(f"LpipsAlex: {key!r} of the {what} state dict is no tensor")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"LpipsAlex: {key!r} must be {list(shape)}, got {list(t.shape)}")
+        if not t.dtype.is_floating_point:
+            raise ValueError(f"LpipsAlex: {key!r} must be a floating-point tensor, got {t.dtype}")
+        return t.detach().to("cpu", torch.float32)
+    ws, bs, ls = [], [], []
+    for l, idx in enumerate(TRUNK_INDEX):
+        ws.append(take(trunk, f"features.{idx}.weight", (COUT[l], CIN[l], KS[l], KS[l]), "trunk"))
+        bs.append(take(trunk, f"features.{idx}.bias", (COUT[l],), "trunk"))
+        ls.append(take(heads, f"lin{l}.model.1.weight", (1, COUT[l], 1, 1), "heads").reshape(-1))
+    return ws, bs, ls
+
+
+def _pair(what, a, b):
+    for name, t in (("the first image", a), ("the second image", b)):
+        if not torch.is_tensor(t):
+            raise TypeError(f"{what}: {name} must be a tensor")
+        if not t.is_cuda:
+            raise RuntimeError(f"{what}: tensors must live on a HIP device (device='cuda'); there is no CPU path")
+    if a.dim() == 3:
+        a = a[None]
+    if b.dim() == 3:
+        b = b[None]
+    if a.dim() != 4 or a.shape[1] != 3 or a.shape != b.shape:
+        raise ValueError(f"{what}: both images must be [B,3,H,W], got {tuple(a.shape)} and {tuple(b.shape)}")
+    if a.shape[0] < 1:
+        raise ValueError(f"{what}: an empty batch")
+    tap_sizes(a.shape[2], a.shape[3])
+    return f32c(a.detach()), f32c(b.detach())
+
+
+class LpipsAlex:
+    """The model, with its weights packed on one device.  Calls run on the current stream with 13 launches per chunk, no
+    synchronisation, no read-back and no allocation that depends on the data: they can be recorded into a graph.  A pair's
+    result is bit-identical from run to run, whatever the batch around it, and exactly 0 for equal images."""
+
+    max_scratch_bytes = 1 << 30      # scratch budget per call: a batch whose scratch exceeds it is processed in chunks
+
+    def __init__(self, trunk_state_dict, heads_state_dict, device="cuda"):
+        ws, bs, ls = check_state_dicts(trunk_state_dict, heads_state_dict)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("LpipsAlex: device must be a HIP device (device='cuda'); there is no CPU path")
+        lib = _lib.load()
+        for l in range(5):
+            if int(lib.mobgs_lpips_pack_k(l + 1)) != pack_k(l + 1):
+                raise RuntimeError(f"LpipsAlex: the library packs layer {l + 1} to {lib.mobgs_lpips_pack_k(l + 1)} rows, "
+                                   f"this module to {pack_k(l + 1)}")
+        self.weights = [pack_conv_weight(w, l + 1).to(self.device) for l, w in enumerate(ws)]
+        self.biases = [b.contiguous().to(self.device) for b in bs]
+        self.heads = [v.contiguous().to(self.device) for v in ls]
+        fields = {}
+        for l in range(5):
+            fields[f"w{l + 1}"] = self.weights[l].data_ptr()
+            fields[f"b{l + 1}"] = self.biases[l].data_ptr()
+            fields[f"lin{l + 1}"] = self.heads[l].data_ptr()
+        self._record = _lib.MobgsLpipsWeights(**fields)
+
+    @classmethod
+    def from_files(cls, trunk, heads, device="cuda"):
+        """trunk: torchvision's alexnet-owt-7be5be79.pth; heads: the reference's models/weights/v0.1/alex.pth."""
+        return cls(torch.load(trunk, map_location="cpu"), torch.load(heads, map_location="cpu"), device=device)
+
+    # ---- the call -----------------------------------------------------------------------------------------------------
+
+    def _chunk(self, B, H, W):
+        """The largest number of pairs whose scratch fits max_scratch_bytes (at least one)."""
+        lib = _lib.load()
+        n = B
+        while n > 1 and int(lib.mobgs_lpips_scratch_bytes(n, H, W)) > self.max_scratch_bytes:
+            n = (n + 1) // 2
+        if int(lib.mobgs_lpips_scratch_bytes(n, H, W)) == 0:
+            raise ValueError(f"LpipsAlex: B = {n}, H = {H}, W = {W} is outside what mobgs_lpips_alex accepts")
+        return n
+
+    def _run(self, img0, img1, flags, taps=None):
+        lib = _lib.load()
+        B, _, H, W = img0.shape
+        dev = img0.device
+        out = torch.empty(B, COLUMNS, dtype=torch.float64, device=dev)
+        n = B if taps is not None else self._chunk(B, H, W)
+        nbytes = int(lib.mobgs_lpips_scratch_bytes(n, H, W))
+        if nbytes == 0:
+            raise ValueError(f"LpipsAlex: B = {n}, H = {H}, W = {W} is outside what mobgs_lpips_alex accepts")
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        tap_ptrs = None
+        if taps is not None:
+            tap_ptrs = (ctypes.c_void_p * 5)(*[t.data_ptr() for t in taps])
+        with torch.cuda.device(dev):
+            for b0 in range(0, B, n):
+                b1 = min(B, b0 + n)
+                check(lib.mobgs_lpips_alex(b1 - b0, H, W, ptr(img0[b0:b1]), ptr(img1[b0:b1]), ctypes.byref(self._record),
+                                           flags, ptr(scratch), nbytes, ptr(out[b0:b1]), tap_ptrs, stream()),
+                      "mobgs_lpips_alex")
+        return out
+
+    @torch.no_grad()
+    def __call__(self, pred, gt, clamp=False, quantize=False) -> LpipsResult:
+        """pred, gt [B,3,H,W] (or [3,H,W]) in [0, 1].  clamp: both are clamped to [0, 1] first; quantize: the prediction is
+        then replaced by floor(clip(pred, 0, 1) * 255) / 255 (eval.py:162): the score of the written PNG."""
+        p, g = _pair("LpipsAlex", pred, gt)
+        flags = UNIT_RANGE | (CLAMP if clamp else 0) | (QUANTIZE if quantize else 0)
+        out = self._run(g, p, flags)                      # the reference's order (metrics.py:130): ground truth first
+        return LpipsResult(out[:, 0], out[:, 1:])
+
+    @torch.no_grad()
+    def forward(self, pred, target, mask=None, normalize=False, spatial=False) -> torch.Tensor:
+        """PerceptualLoss.forward (models/__init__.py:26-40): inputs in [-1, 1] (normalize=True: in [0, 1]) -> [B,1,1,1] fp32."""
+        if mask is not None or spatial:
+            raise NotImplementedError("LpipsAlex.forward: a mask and spatial=True (dycheck's compute_lpips) are not built")
+        a, b = _pair("LpipsAlex.forward", target, pred)
+        out = self._run(a, b, UNIT_RANGE if normalize else 0)
+        return out[:, 0].float().reshape(-1, 1, 1, 1)
+
+    @torch.no_grad()
+    def features(self, img) -> List[torch.Tensor]:
+        """The five ReLU maps of img [B,3,H,W] in [0, 1] as [B,C,h,w] tensors (views of the kernel's channel-last storage)."""
+        a, _ = _pair("LpipsAlex.features", img, img)
+        B, _, H, W = a.shape
+        taps = [torch.empty(2 * B, h, w, c, dtype=torch.float32, device=a.device)
+                for (h, w), c in zip(tap_sizes(H, W), COUT)]
+        self._run(a, a, UNIT_RANGE, taps=taps)
+        return [t[0::2].permute(0, 3, 1, 2) for t in taps]

@@ -14,8 +14,9 @@ are four times what the images' own range would give.  This is a reading of that
 here.  So `data_range` is a required keyword of everything below that evaluates the box SSIM, and evaluate_views defaults
 to 2.0 (README, "UNPINNED").
 
-Not here: LPIPS (the AlexNet trunk weights are not available), tOF (OpenCV's Farneback flow), gradients.  The test-time pose
-optimisation of eval.py is mobgs_amd.tto, which scores its images through image_metrics(clamp=True, quantize=True).
+LPIPS is mobgs_amd.lpips (csrc/lpips.hip, K24); evaluate_views(..., lpips=model) adds it.  Not here: tOF (OpenCV's
+Farneback flow), gradients.  The test-time pose optimisation of eval.py is mobgs_amd.tto, which scores its images through
+image_metrics(clamp=True, quantize=True).
 """
 from __future__ import annotations
 
@@ -194,7 +195,8 @@ def aligned_test_pose(input_train, input_test, output_train):
 
 
 @torch.no_grad()
-def evaluate_views(cams, stat_pc, dyn_pc, pipe, bg, gt_images, *, stage="fine", ssim_data_range=2.0, **render_kw):
+def evaluate_views(cams, stat_pc, dyn_pc, pipe, bg, gt_images, *, stage="fine", ssim_data_range=2.0, lpips=None,
+                   **render_kw):
     """The test loop of training_report (train.py:895-925) with the SSIMs next to it: renders every camera through
     gaussian_renderer.render, stacks the images and scores them against gt_images ([K,3,H,W], or K tensors [3,H,W]) in ONE
     image_metrics call with clamp=True, then reads the result back ONCE.
@@ -203,7 +205,10 @@ def evaluate_views(cams, stat_pc, dyn_pc, pipe, bg, gt_images, *, stage="fine", 
     (see the module docstring; this is a reading of that package's source, nobody could run it here).
 
     -> {"per_view": ImageMetrics (device, [K]), "l1", "psnr", "ssim_box", "ssim_gauss": the means over the views as Python
-    floats (l1 and psnr are what training_report prints), "images": [K,3,H,W] as rendered (not clamped)}."""
+    floats (l1 and psnr are what training_report prints), "images": [K,3,H,W] as rendered (not clamped)}.
+
+    lpips: None, or a mobgs_amd.lpips.LpipsAlex: the result then also holds "lpips_per_view" ([K] float64, device: the
+    model on the clamped images, in the same pass) and "lpips", its mean as a Python float."""
     from .gaussian_renderer import render
     cams = list(cams)
     if not cams:
@@ -212,5 +217,9 @@ def evaluate_views(cams, stat_pc, dyn_pc, pipe, bg, gt_images, *, stage="fine", 
     gt = gt_images if torch.is_tensor(gt_images) else torch.stack(list(gt_images))
     per_view = image_metrics(images, gt.to(images.device), data_range=ssim_data_range, clamp=True)
     means = torch.stack([per_view.l1, per_view.psnr, per_view.ssim_box, per_view.ssim_gauss]).mean(1).tolist()
-    return {"per_view": per_view, "l1": means[0], "psnr": means[1], "ssim_box": means[2], "ssim_gauss": means[3],
-            "images": images}
+    report = {"per_view": per_view, "l1": means[0], "psnr": means[1], "ssim_box": means[2], "ssim_gauss": means[3],
+              "images": images}
+    if lpips is not None:
+        report["lpips_per_view"] = lpips(images, gt.to(images.device), clamp=True).total
+        report["lpips"] = float(report["lpips_per_view"].mean())
+    return report

@@ -18,7 +18,8 @@ quaternion_to_matrix does not normalise (two_s = 2 / (q . q)).  scripts/dump_pos
 gives, for a machine that has it (README, "UNPINNED").
 
 Not here: use_sgd and loss_type != "psnr" (never enabled by the reference: NotImplementedError), batching cameras, graph
-capture, LPIPS.  Tensors must live on a HIP device.
+capture.  LPIPS of the written images: render_test_tto(..., lpips=model) with a mobgs_amd.lpips.LpipsAlex.  Tensors must live
+on a HIP device.
 """
 from __future__ import annotations
 
@@ -247,7 +248,7 @@ def refine_pose(cam, gt, stat_pc, dyn_pc, pipe, bg, *, steps, decay_start, lr_p,
 def render_test_tto(H, W, scene, test_cams, save_dir, gt_images, tto_steps=25, decay_start=15, lr_p=0.003, lr_q=0.003,
                     lr_final=0.0001, use_sgd=False, loss_type="psnr", initialize_from_previous_camera=True,
                     initialize_from_previous_step_factor=10, initialize_from_previous_lr_factor=0.1, fg_mask_th=0.1,
-                    local_viewdirs=None, batch_shape=None, renderArgs=None, ssim_data_range=2.0):
+                    local_viewdirs=None, batch_shape=None, renderArgs=None, ssim_data_range=2.0, lpips=None):
     """eval.py:43-166 with the reference's keyword names and defaults, ground-truth TENSORS (gt_images [K,3,H,W] in [0, 1],
     or K tensors [3,H,W]) in place of a directory of PNGs, and a result in place of None.  scene: anything with
     .stat_gaussians and .dyn_gaussians (and optionally .dataset_type); renderArgs = [pipe, background].
@@ -264,7 +265,8 @@ def render_test_tto(H, W, scene, test_cams, save_dir, gt_images, tto_steps=25, d
     -> {"poses": [K,4,4], "images": [K,3,H,W] as rendered (not clamped), "loss_histories": K device tensors (camera k's
     has tto_steps * step_factor[k] entries), "step_factors", "lr_factors": what each camera ran with, "metrics":
     metrics.image_metrics(images, gt, data_range=ssim_data_range, clamp=True, quantize=True) -- the scores of the written
-    PNGs, without reading them back}."""
+    PNGs, without reading them back}.  lpips: None, or a mobgs_amd.lpips.LpipsAlex: the result then also holds "lpips", its
+    LpipsResult on the same pairs with clamp=True, quantize=True (metrics.py:127-131 on the written PNGs)."""
     from .gaussian_renderer import render
     from .metrics import image_metrics
     what = "render_test_tto"
@@ -303,8 +305,8 @@ def render_test_tto(H, W, scene, test_cams, save_dir, gt_images, tto_steps=25, d
         step_factors.append(step_factor)
         lr_factors.append(lr_factor)
     poses, images = torch.stack(poses), torch.stack(images)
-    metrics = image_metrics(images, torch.stack([g.to(device).float() for g in gts]), data_range=ssim_data_range,
-                            clamp=True, quantize=True)
+    gt_stack = torch.stack([g.to(device).float() for g in gts])
+    metrics = image_metrics(images, gt_stack, data_range=ssim_data_range, clamp=True, quantize=True)
     if save_dir is not None:
         import numpy as np
         from PIL import Image
@@ -316,5 +318,8 @@ def render_test_tto(H, W, scene, test_cams, save_dir, gt_images, tto_steps=25, d
             name = getattr(cam, "image_name", f"{k:05d}")
             Image.fromarray(bytes_hwc[k]).save(os.path.join(folder, f"img_{name}.png.png"))
         np.save(os.path.join(save_dir, "solved_poses.npy"), poses.cpu().numpy())
-    return {"poses": poses, "images": images, "loss_histories": histories, "step_factors": step_factors,
-            "lr_factors": lr_factors, "metrics": metrics}
+    result = {"poses": poses, "images": images, "loss_histories": histories, "step_factors": step_factors,
+              "lr_factors": lr_factors, "metrics": metrics}
+    if lpips is not None:
+        result["lpips"] = lpips(images, gt_stack, clamp=True, quantize=True)
+    return result
