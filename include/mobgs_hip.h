@@ -769,8 +769,13 @@ int mobgs_ssim_l1_bwd(int C, int H, int W, const float* img1, const float* img2,
  *      scratch: mobgs_flow_warp_loss_bwd_scratch_floats(B,K,H,W) floats (needed when g_ori or g_latent is wanted: the
  *      images' gradients as TARGETS of the other term are written there and added at the end).
  *      combine_taps != 0: coinciding taps of neighbouring pixels (next lane, next row) are merged in registers before
- *      the atomics (same sums, a quarter of the atomics). */
+ *      the atomics (same sums, a quarter of the atomics).
+ * mobgs_flow_warp_loss_bwd_rows: the rows of a wave's strip (4 or 8) in the build of the backward kernel that
+ *      mobgs_flow_warp_loss_bwd launches for these sizes -- 8 when combine_taps != 0 and ceil(W / 64) ceil(H / 32) B
+ *      >= 1024, else 4; the launcher chooses its kernel by this very function.  A size query: no device is touched.
+ *      Bad sizes (B <= 0, H < 2, W < 2): MOBGS_E_INVALID with a message, as the other flow entry points. */
 int mobgs_flow_warp_loss_blocks(int B, int H, int W);
+int mobgs_flow_warp_loss_bwd_rows(int B, int H, int W, int combine_taps);
 int mobgs_flow_warp_loss_fwd(int B, int K, int H, int W, const float* ori, const float* latent, const float* exp2mid,
                              const float* mid2exp, const float* latent_alpha, const float* d_alpha, float* partial,
                              float* sums, float* loss, void* stream);

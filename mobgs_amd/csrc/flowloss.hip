@@ -499,6 +499,13 @@ size_t mobgs_flow_warp_loss_bwd_scratch_floats(int B, int K, int H, int W) {
     return (size_t)B * (K + 1) * 3 * (size_t)H * W;
 }
 
+// FL_ROWS of the backward build for these sizes (the rule itself: see the comment above flow_warp_l1_bwd_kernel)
+int mobgs_flow_warp_loss_bwd_rows(int B, int H, int W, int combine_taps) {
+    if (!flow_sizes_ok("mobgs_flow_warp_loss_bwd_rows", B, 1, H, W)) return MOBGS_E_INVALID;
+    const bool tall = (size_t)((W + FL_TX - 1) / FL_TX) * ((H + 31) / 32) * B >= 1024;
+    return (combine_taps && tall) ? 8 : 4;
+}
+
 int mobgs_flow_warp_loss_bwd(int B, int K, int H, int W, const float* ori, const float* latent, const float* exp2mid,
                              const float* mid2exp, const float* latent_alpha, const float* d_alpha, const float* sums,
                              const float* v_loss, float* g_ori, float* g_latent, float* g_exp2mid, float* g_mid2exp,
@@ -520,13 +527,13 @@ int mobgs_flow_warp_loss_bwd(int B, int K, int H, int W, const float* ori, const
                            d_alpha, sums, v_loss, g_ori, d_ori, g_latent, d_latent, g_exp2mid, g_mid2exp, g_latent_alpha,
                            g_d_alpha);
     };
-    const bool tall = (size_t)((W + FL_TX - 1) / FL_TX) * ((H + 31) / 32) * B >= 1024;
+    const int rows = mobgs_flow_warp_loss_bwd_rows(B, H, W, combine_taps);
     if (!combine_taps)
-        launch(flow_warp_l1_bwd_kernel<false, 4>, 4);
-    else if (tall)
-        launch(flow_warp_l1_bwd_kernel<true, 8>, 8);
+        launch(flow_warp_l1_bwd_kernel<false, 4>, rows);
+    else if (rows == 8)
+        launch(flow_warp_l1_bwd_kernel<true, 8>, rows);
     else
-        launch(flow_warp_l1_bwd_kernel<true, 4>, 4);
+        launch(flow_warp_l1_bwd_kernel<true, 4>, rows);
     auto add = [&](float* g, const float* d, size_t n) {
         // (both come from one allocation each: 16-byte aligned when the element offsets are multiples of 4)
         const bool aligned = ((uintptr_t)g % 16 == 0) && ((uintptr_t)d % 16 == 0);

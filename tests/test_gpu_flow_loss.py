@@ -134,9 +134,14 @@ def test_needs_input_grad_subsets_and_shapes(hip_device):
 
 
 def test_flow_warp_loss_at_benchmark_size(hip_device):
-    """One view x K = 3 exposures at 1352x1014 (the 8-row strips of the backward pass, many workgroups) against the
-    reference block on the CPU."""
+    """One view x K = 3 exposures at 1352x1014 against the reference block on the CPU.  One view is 22 x 32 = 704 workgroups
+    of 32 rows, under the 1024 from which the backward pass walks 8-row strips: this runs the 4-ROW build at many
+    workgroups.  The 8-row build (what training launches for two views of this size) is tested on the cases tall8_a,
+    tall8_b and white_noise_8 of tests/test_gpu_flow_kernels.py."""
+    from mobgs_amd import _lib
     from mobgs_amd.loss_utils import flow_warp_loss
+    assert _lib.load().mobgs_flow_warp_loss_bwd_rows(1, 1014, 1352, 1) == 4
+    assert _lib.load().mobgs_flow_warp_loss_bwd_rows(2, 1014, 1352, 1) == 8
     case = _case(1, 3, 1014, 1352, 9, flow=3.0)
     ref, gref = _run(RT.flow_warp_loss, case, "cpu", torch.float64)
     _, gref32 = _run(RT.flow_warp_loss, case, "cpu", torch.float32)  # only to tell flipped sgn() terms (see _check)
