@@ -1063,6 +1063,80 @@ int mobgs_lpips_pack_k(int layer);
 int mobgs_lpips_alex(int B, int H, int W, const float* img0, const float* img1, const MobgsLpipsWeights* weights,
                      int flags, void* scratch, size_t scratch_bytes, double* out, float* const* taps, void* stream);
 
+/* ---- K25: tOF, the temporal optical-flow metric: dense Farneback flow and the distance of two flow fields -----------
+ * What the reference's metrics.py:14-47 and :108-120 evaluate: cv2.calcOpticalFlowFarneback(prev, next, None, 0.5, 3, 15,
+ * 3, 5, 1.2, 0) between consecutive 8-bit grey frames, for the prediction and for the ground truth, and the mean of
+ * |flow_gt - flow_pred|_2 over the crop_8x8 window.  Forward only, on the caller's stream (csrc/tof.hip, built with
+ * -ffp-contract=off).  Entry points only: MOBGS_ABI_VERSION stays as it is.  OpenCV could not be run where this was
+ * written: the algorithm is a restatement (README, "UNPINNED"; tests/tof_restatement.py is the same text in float64).
+ * Device pointers are fp32 unless stated, 4-byte aligned; every input is only read; no call synchronises, allocates or
+ * reads back, so all of them can be recorded into a graph.  A frame pair is a grid index and there is no float atomic: a
+ * pair's result is bit-identical from run to run and does not depend on the batch around it.
+ * x = column; flow channel 0 = u along x, channel 1 = v along y, from the pair's first frame to its second.
+ *
+ * mobgs_tof_levels: a host computation (no device is touched).  scale = 1; for k = 0, 1, 2: scale *= 0.5, stop if W scale
+ *   < 32 or H scale < 32; L = the k reached.  out[i], i = 0 .. L, COARSEST FIRST (k = L - i, s = 0.5^k): width = rint(W s),
+ *   height = rint(H s) (half to even), sigma = (1 / s - 1) / 2, taps = max(rint(5 sigma) | 1, 3).  Returns L + 1 (1 .. 4),
+ *   or 0 for a NULL out or a size outside 48 <= H, W <= 16384 (below 48 the crop window is empty).  out holds 4 records.
+ * mobgs_tof_crop: yxhw (HOST, 4 x int32) = crop_8x8's window (metrics.py:32-47): h = (H / 32) 32, minus 32 while h > H - 16,
+ *   y = (H - h) / 2; w and x alike.  A host computation.
+ * mobgs_tof_grey: rgb [F,3,H,W] -> grey [F,H,W], 8-bit values held as fp32.  Per channel: with MOBGS_METRICS_CLAMP, clip to
+ *   [0, 1]; with MOBGS_METRICS_QUANTIZE, floor(clip(x) * 255) / 255 in fp32 (the written PNG read back, metrics.py:100);
+ *   then trunc(fl32(x * 255)), saturated to 0 .. 255 (metrics.py:109-110: the product is formed in fp32 as numpy forms
+ *   it; on k / 255 that round trip is the identity for all 256 k, tests/test_tof_cpu.py); then OpenCV's 8-bit COLOR_RGB2GRAY, (4899 R + 9617 G + 1868 B + 8192) >> 14.  1 launch.
+ * mobgs_tof_pyramid_level: grey [F,H,W] -> out [F,height,width]: the Gaussian blur of the full-size image (taps, sigma;
+ *   the taps exp(-t^2 / (2 sigma^2)) normalised to sum 1, [1/4, 1/2, 1/4] for sigma = 0; reflect-101 border) resized
+ *   bilinearly (sx = (dx + 0.5) W / width - 0.5, clamped to [0, W - 1]).  level: one HOST record as mobgs_tof_levels fills
+ *   them (odd taps in 3 .. 19, sigma >= 0, a size not above the image's).  1 launch.
+ * mobgs_tof_polyexp: img [F,h,w] -> R [F,5,h,w] = (r_x, r_y, r_xx, r_yy, r_xy): per pixel the coefficients of x, y, x^2, y^2,
+ *   xy of the least-squares fit of (1, x, y, x^2, y^2, xy) over the 11x11 window under the weight g(x) g(y), g ~ exp(-t^2 /
+ *   (2 1.2^2)) normalised to sum 1; samples outside the image are replicated.  1 launch; run it once per frame and level.
+ * mobgs_tof_update_matrices: R [P+1,5,h,w] (pair p = frames p, p + 1) -> M [P,5,h,w] = (G11, G12, G22, h1, h2).  The flow
+ *   (u, v) of a pixel: 0 if flow is NULL; flow [P,src_h,src_w,2] itself if (src_h, src_w) = (h, w); otherwise that field
+ *   resized bilinearly to (h, w) (as above) and multiplied by 2.  flow_out [P,h,w,2] or NULL receives the flow used.  With
+ *   S = R1 sampled bilinearly at (x + u, y + v) if 0 <= floor(x + u) < w - 1 and 0 <= floor(y + v) < h - 1:
+ *     in bounds: a_xx = (R0.xx + S.xx) / 2, a_yy alike, a_xy = (R0.xy + S.xy) / 4, b_x = (R0.x - S.x) / 2, b_y alike;
+ *     otherwise: a_xx = R0.xx, a_yy = R0.yy, a_xy = R0.xy / 2, b_x = R0.x / 2, b_y = R0.y / 2;
+ *     b_x += a_xx u + a_xy v, b_y += a_xy u + a_yy v; all five times the product of the border factors of the four sides,
+ *     t[d] = (0.14, 0.14, 0.4472, 0.4472, 0.4472) for a distance d = 0 .. 4 to that side, 1 beyond;
+ *     G11 = a_xx^2 + a_xy^2, G12 = (a_xx + a_yy) a_xy, G22 = a_yy^2 + a_xy^2, h1 = a_xx b_x + a_xy b_y, h2 = a_xy b_x + a_yy b_y.
+ *   A flow that is not finite, or beyond 1e6 pixels, counts as out of bounds.  1 launch.
+ * mobgs_tof_blur_solve: M_in [P,5,h,w] -> flow [P,h,w,2] (fully written): the 15x15 box MEAN of the five values (replicate
+ *   border, float64), det = G11 G22 - G12^2 + 1e-3, u = (G22 h1 - G12 h2) / det, v = (G11 h2 - G12 h1) / det.  With M_out
+ *   (and R) not NULL the update matrices of the NEW flow are written to M_out in the same launch, bit-identical with a
+ *   mobgs_tof_update_matrices call on that flow; M_out must not be M_in.  1 launch.
+ * mobgs_tof_flow: grey [F,H,W] -> flow_out [F-1,H,W,2], the flows of the F - 1 consecutive pairs.  Per level, coarsest
+ *   first: the level image and the expansion of every FRAME once, the first update matrices from the coarser level's flow
+ *   (zero at the coarsest), three rounds of mobgs_tof_blur_solve, the first two with the next update fused in.  6 launches
+ *   per level, at most 24.  scratch: mobgs_tof_scratch_bytes(F, H, W) bytes (a host computation; 0 for a shape that is
+ *   refused), 256-byte aligned, contents irrelevant on entry.  It grows with F: a caller with a budget splits the frames
+ *   into runs that overlap by one, which does not change a bit of any pair's flow.
+ * mobgs_tof_score: flow_a, flow_b [P,H,W,2], mask [P,H,W] or NULL -> out [P] float64 (device): over crop_8x8's window,
+ *   the mean of sqrt(du^2 + dv^2) (float64 from the differences on), or sum(. mask) / sum(mask) (NaN for
+ *   an empty mask, as the reference's 0 / 0).  partial: scratch, mobgs_tof_score_scratch_doubles(P, H, W) float64 (a host
+ *   computation; 0 for a refused shape), contents irrelevant on entry.  Fixed summation order; 2 launches.
+ * Refused with MOBGS_E_INVALID before any launch, under the entry point's name: a NULL pointer (the optional ones
+ *   excepted) or a misaligned one (scratch 256 bytes, partial and out 8), a count outside 1 .. 4096 (mobgs_tof_flow: F < 2),
+ *   an image below 48 or above 16384 on a side (grey, the stage calls on a level: below 2), an unknown flag, a level record
+ *   outside the ranges above, a src size above the level's. */
+typedef struct MobgsTofLevel {
+    int width, height, taps;
+    double sigma;
+} MobgsTofLevel;
+int mobgs_tof_levels(int H, int W, MobgsTofLevel* out);
+int mobgs_tof_crop(int H, int W, int32_t* yxhw);
+size_t mobgs_tof_scratch_bytes(int F, int H, int W);
+size_t mobgs_tof_score_scratch_doubles(int P, int H, int W);
+int mobgs_tof_grey(int F, int H, int W, const float* rgb, int flags, float* grey, void* stream);
+int mobgs_tof_pyramid_level(int F, int H, int W, const float* grey, const MobgsTofLevel* level, float* out, void* stream);
+int mobgs_tof_polyexp(int F, int h, int w, const float* img, float* R, void* stream);
+int mobgs_tof_update_matrices(int P, int h, int w, const float* R, const float* flow, int src_h, int src_w,
+                              float* flow_out, float* M, void* stream);
+int mobgs_tof_blur_solve(int P, int h, int w, const float* M_in, float* flow, const float* R, float* M_out, void* stream);
+int mobgs_tof_flow(int F, int H, int W, const float* grey, void* scratch, float* flow_out, void* stream);
+int mobgs_tof_score(int P, int H, int W, const float* flow_a, const float* flow_b, const float* mask, double* partial,
+                    double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

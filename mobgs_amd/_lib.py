@@ -146,6 +146,11 @@ class MobgsLpipsWeights(ctypes.Structure):
     _fields_ = _STRUCTS["MobgsLpipsWeights"]
 
 
+class MobgsTofLevel(ctypes.Structure):
+    """include/mobgs_hip.h MobgsTofLevel: one scale of the Farneback pyramid (width, height, taps, sigma)."""
+    _fields_ = _STRUCTS["MobgsTofLevel"]
+
+
 def _bind(lib, name, restype, argtypes):
     fn = getattr(lib, name)
     fn.restype = restype

@@ -14,9 +14,15 @@ are four times what the images' own range would give.  This is a reading of that
 here.  So `data_range` is a required keyword of everything below that evaluates the box SSIM, and evaluate_views defaults
 to 2.0 (README, "UNPINNED").
 
-LPIPS is mobgs_amd.lpips (csrc/lpips.hip, K24); evaluate_views(..., lpips=model) adds it.  Not here: tOF (OpenCV's
-Farneback flow), gradients.  The test-time pose optimisation of eval.py is mobgs_amd.tto, which scores its images through
-image_metrics(clamp=True, quantize=True).
+LPIPS is mobgs_amd.lpips (csrc/lpips.hip, K24); evaluate_views(..., lpips=model) adds it.  tOF, the temporal optical-flow
+metric of metrics.py:14-47 and :108-120 (OpenCV's Farneback flow between consecutive frames, prediction against ground truth),
+is temporal_of / TofTarget below (csrc/tof.hip, K25); evaluate_views(..., tof=True) adds it.  Not here: gradients.  The
+test-time pose optimisation of eval.py is mobgs_amd.tto, which scores its images through image_metrics(clamp=True,
+quantize=True).
+
+    flows = farneback_flow(grey_frames(frames))             # [F,3,H,W] -> [F,H,W] 8-bit grey -> [F-1,H,W,2]
+    tof = temporal_of(pred, gt)                              # [F-1] float64, device; .mean() is the reference's mean_tof
+    target = TofTarget.from_frames(gt); temporal_of(pred, target)   # the ground truth's flows computed once
 """
 from __future__ import annotations
 
@@ -186,6 +192,171 @@ def structural_similarity(im1, im2, *, data_range, multichannel=True, full=False
     return float(m.ssim_box)
 
 
+# ---- tOF: Farneback flow between consecutive frames, prediction against ground truth (K25) ---------------------------------
+
+TOF_MIN_EDGE = 48                    # below it crop_8x8's window is empty
+TOF_SCRATCH_BUDGET = 1 << 30         # bytes of scratch per mobgs_tof_flow call; longer sequences run in overlapping pieces
+
+
+def _tof_frames(what, name, t, channels):
+    _device_image(what, name, t)
+    want = "[F,3,H,W]" if channels else "[F,H,W]"
+    if t.dim() != (4 if channels else 3) or (channels and t.shape[1] != 3):
+        raise ValueError(f"{what}: {name} must be {want}, got {tuple(t.shape)}")
+    if t.shape[-2] < TOF_MIN_EDGE or t.shape[-1] < TOF_MIN_EDGE:
+        raise ValueError(f"{what}: {name} needs H, W >= {TOF_MIN_EDGE} (crop_8x8's window is empty below), got "
+                         f"{t.shape[-2]} x {t.shape[-1]}")
+    return f32c(t.detach())
+
+
+def crop_window(H, W):
+    """metrics.py:32-47 -> (y, x, h, w) of crop_8x8's window (the library's own arithmetic: mobgs_tof_crop)."""
+    import ctypes
+    yxhw = (ctypes.c_int32 * 4)()
+    check(_lib.load().mobgs_tof_crop(int(H), int(W), ctypes.cast(yxhw, ctypes.c_void_p)), "mobgs_tof_crop")
+    return tuple(yxhw)
+
+
+def crop_8x8(img):
+    """metrics.py:32-47 on a [H,W] or [H,W,C] tensor (or array): -> (the window, a view; y; x)."""
+    if img.shape[0] < TOF_MIN_EDGE or img.shape[1] < TOF_MIN_EDGE:
+        raise ValueError(f"crop_8x8: needs H, W >= {TOF_MIN_EDGE}, got {img.shape[0]} x {img.shape[1]}")
+    y, x, h, w = crop_window(img.shape[0], img.shape[1])
+    return img[y:y + h, x:x + w], y, x
+
+
+@torch.no_grad()
+def grey_frames(frames, *, clamp=False, quantize=False):
+    """[F,3,H,W] float images -> [F,H,W] fp32 holding the 8-bit grey values the reference hands to OpenCV
+    (metrics.py:109-110: (img * 255.0).astype(np.uint8) in fp32, then cv2.COLOR_RGB2GRAY in 14-bit fixed point).  clamp:
+    clip to [0, 1] first; quantize: then floor(clip(x) * 255) / 255 in fp32, the written PNG read back.  One launch."""
+    what = "grey_frames"
+    frames = _tof_frames(what, "frames", frames, True)
+    F_, _, H, W = frames.shape
+    grey = torch.empty(F_, H, W, dtype=torch.float32, device=frames.device)
+    flags = (CLAMP if clamp else 0) | (QUANTIZE if quantize else 0)
+    with torch.cuda.device(frames.device):
+        check(_lib.load().mobgs_tof_grey(F_, H, W, ptr(frames), flags, ptr(grey), stream()), "mobgs_tof_grey")
+    return grey
+
+
+@torch.no_grad()
+def farneback_flow(frames_grey):
+    """[F,H,W] grey frames (8-bit values in a float tensor) -> [F-1,H,W,2] fp32: cv2.calcOpticalFlowFarneback(prev, next, None,
+    0.5, 3, 15, 3, 5, 1.2, 0) of every consecutive pair, channel 0 along x.  Six launches per pyramid level (at most 24) per
+    piece of the sequence; a sequence whose scratch would pass TOF_SCRATCH_BUDGET runs in pieces that overlap by one frame,
+    which changes no bit of any pair's flow.  No synchronisation; bit-identical from run to run and whatever F is."""
+    what = "farneback_flow"
+    grey = _tof_frames(what, "frames_grey", frames_grey, False)
+    F_, H, W = grey.shape
+    if F_ < 2:
+        raise ValueError(f"{what}: needs at least two frames, got {F_}")
+    lib = _lib.load()
+    dev = grey.device
+    flow = torch.empty(F_ - 1, H, W, 2, dtype=torch.float32, device=dev)
+    piece = F_
+    while piece > 2 and int(lib.mobgs_tof_scratch_bytes(piece, H, W)) > TOF_SCRATCH_BUDGET:
+        piece -= 1
+    nbytes = int(lib.mobgs_tof_scratch_bytes(piece, H, W))
+    if nbytes == 0:
+        raise ValueError(f"{what}: the library refuses F = {piece}, H = {H}, W = {W}")
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        for first in range(0, F_ - 1, piece - 1):
+            n = min(piece, F_ - first)
+            check(lib.mobgs_tof_flow(n, H, W, ptr(grey[first:first + n]), ptr(scratch), ptr(flow[first:first + n - 1]),
+                                     stream()), "mobgs_tof_flow")
+    return flow
+
+
+@torch.no_grad()
+def flow_distance(flow_a, flow_b, mask=None):
+    """Two flow stacks [P,H,W,2] (mask [P,H,W] of weights, or None) -> [P] float64 on the device: per pair the mean of
+    |flow_a - flow_b|_2 over crop_8x8's window, or sum(. mask) / sum(mask) (metrics.py:18-29).  Two launches."""
+    what = "flow_distance"
+    _device_image(what, "flow_a", flow_a), _device_image(what, "flow_b", flow_b)
+    if flow_a.dim() != 4 or flow_a.shape[-1] != 2 or flow_a.shape != flow_b.shape:
+        raise ValueError(f"{what}: flows must both be [P,H,W,2], got {tuple(flow_a.shape)} and {tuple(flow_b.shape)}")
+    P, H, W, _ = flow_a.shape
+    if P < 1 or H < TOF_MIN_EDGE or W < TOF_MIN_EDGE:
+        raise ValueError(f"{what}: needs P >= 1 and H, W >= {TOF_MIN_EDGE}, got {tuple(flow_a.shape)}")
+    if mask is not None:
+        _device_image(what, "mask", mask)
+        if mask.numel() != P * H * W or mask.shape[-2:] != (H, W):
+            raise ValueError(f"{what}: mask must be [P,H,W] or [P,1,H,W], got {tuple(mask.shape)}")
+        mask = f32c(mask.detach().reshape(P, H, W))
+    flow_a, flow_b = f32c(flow_a.detach()), f32c(flow_b.detach())
+    lib = _lib.load()
+    dev = flow_a.device
+    partial = torch.empty(int(lib.mobgs_tof_score_scratch_doubles(P, H, W)), dtype=torch.float64, device=dev)
+    out = torch.empty(P, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.mobgs_tof_score(P, H, W, ptr(flow_a), ptr(flow_b), ptr(mask), ptr(partial), ptr(out), stream()),
+              "mobgs_tof_score")
+    return out
+
+
+class TofTarget:
+    """The ground truth's side of tOF: its F - 1 flows, computed once.  They do not change between evaluations, and
+    training_report runs at every testing iteration: temporal_of(pred, target) then computes the prediction's flows only.
+    (The flows are kept whole; crop_8x8's window is an index range of the scoring kernel.)"""
+
+    def __init__(self, flows):
+        self.flows = flows
+
+    @classmethod
+    def from_frames(cls, gt, *, clamp=False):
+        """gt [F,3,H,W] in [0, 1] (clamp: clipped to it first, as evaluate_views scores its images)."""
+        return cls(farneback_flow(grey_frames(gt, clamp=clamp)))
+
+    @property
+    def frames(self):
+        return self.flows.shape[0] + 1
+
+
+@torch.no_grad()
+def temporal_of(pred, gt, mask=None, *, clamp=False, quantize=False):
+    """tOF of a sequence: pred [F,3,H,W], gt [F,3,H,W] or a TofTarget of F frames, mask [F-1,H,W] or None (pair p = frames
+    p, p + 1) -> [F-1] float64 on the device; its mean is the reference's mean_tof (metrics.py:141-142: the -1.0 of frame 0
+    is filtered out there).  clamp: both sequences are clipped to [0, 1] first; quantize: the prediction is then replaced by
+    its 8-bit version, as image_metrics does: the tOF of the written PNGs without writing them.  No synchronisation."""
+    what = "temporal_of"
+    flows = farneback_flow(grey_frames(pred, clamp=clamp, quantize=quantize))
+    if isinstance(gt, TofTarget):
+        if gt.flows.shape != flows.shape:
+            raise ValueError(f"{what}: the target holds flows {tuple(gt.flows.shape)}, the prediction gives "
+                             f"{tuple(flows.shape)}")
+        target = gt.flows
+    else:
+        _device_image(what, "gt", gt)
+        if gt.shape != pred.shape:
+            raise ValueError(f"{what}: pred and gt must have one shape, got {tuple(pred.shape)} and {tuple(gt.shape)}")
+        target = farneback_flow(grey_frames(gt.to(flows.device), clamp=clamp))
+    return flow_distance(target, flows, mask)
+
+
+def _grey_hw(what, name, img):
+    if not torch.is_tensor(img):
+        img = torch.as_tensor(img).to("cuda")
+    _device_image(what, name, img)
+    if img.dim() != 2:
+        raise ValueError(f"{what}: {name} must be a [H,W] grey image, got {tuple(img.shape)}")
+    return img.float()
+
+
+def get_tOF(pre_gt_grey, gt_grey, pre_output_grey, output_grey, mask=None) -> float:
+    """metrics.py:14-29 under its own name: four [H,W] 8-bit grey images (device tensors of any dtype, or arrays, which are
+    uploaded), mask [H,W] / [H,W,1] or None -> the tOF of the pair as a Python float."""
+    what = "get_tOF"
+    a = torch.stack([_grey_hw(what, "pre_gt_grey", pre_gt_grey), _grey_hw(what, "gt_grey", gt_grey)])
+    b = torch.stack([_grey_hw(what, "pre_output_grey", pre_output_grey), _grey_hw(what, "output_grey", output_grey)])
+    if mask is not None:
+        if not torch.is_tensor(mask):
+            mask = torch.as_tensor(mask).to(a.device)
+        mask = mask.squeeze()[None]
+    return float(flow_distance(farneback_flow(a), farneback_flow(b), mask))
+
+
 # ---- training_report ---------------------------------------------------------------------------------------------------
 
 def aligned_test_pose(input_train, input_test, output_train):
@@ -196,7 +367,7 @@ def aligned_test_pose(input_train, input_test, output_train):
 
 @torch.no_grad()
 def evaluate_views(cams, stat_pc, dyn_pc, pipe, bg, gt_images, *, stage="fine", ssim_data_range=2.0, lpips=None,
-                   **render_kw):
+                   tof=None, **render_kw):
     """The test loop of training_report (train.py:895-925) with the SSIMs next to it: renders every camera through
     gaussian_renderer.render, stacks the images and scores them against gt_images ([K,3,H,W], or K tensors [3,H,W]) in ONE
     image_metrics call with clamp=True, then reads the result back ONCE.
@@ -208,7 +379,11 @@ def evaluate_views(cams, stat_pc, dyn_pc, pipe, bg, gt_images, *, stage="fine", 
     floats (l1 and psnr are what training_report prints), "images": [K,3,H,W] as rendered (not clamped)}.
 
     lpips: None, or a mobgs_amd.lpips.LpipsAlex: the result then also holds "lpips_per_view" ([K] float64, device: the
-    model on the clamped images, in the same pass) and "lpips", its mean as a Python float."""
+    model on the clamped images, in the same pass) and "lpips", its mean as a Python float.
+
+    tof: None, True, or a TofTarget built from these ground truths with clamp=True: the cameras are then taken as
+    consecutive frames, and the result also holds "tof_per_pair" ([K-1] float64, device: temporal_of on the clamped images)
+    and "tof", its mean as a Python float -- the mean_tof metrics.py:141-142 prints.  Needs K >= 2 and H, W >= 48."""
     from .gaussian_renderer import render
     cams = list(cams)
     if not cams:
@@ -222,4 +397,7 @@ def evaluate_views(cams, stat_pc, dyn_pc, pipe, bg, gt_images, *, stage="fine", 
     if lpips is not None:
         report["lpips_per_view"] = lpips(images, gt.to(images.device), clamp=True).total
         report["lpips"] = float(report["lpips_per_view"].mean())
+    if tof is not None and tof is not False:
+        report["tof_per_pair"] = temporal_of(images, tof if isinstance(tof, TofTarget) else gt.to(images.device), clamp=True)
+        report["tof"] = float(report["tof_per_pair"].mean())
     return report

@@ -248,7 +248,8 @@ def refine_pose(cam, gt, stat_pc, dyn_pc, pipe, bg, *, steps, decay_start, lr_p,
 def render_test_tto(H, W, scene, test_cams, save_dir, gt_images, tto_steps=25, decay_start=15, lr_p=0.003, lr_q=0.003,
                     lr_final=0.0001, use_sgd=False, loss_type="psnr", initialize_from_previous_camera=True,
                     initialize_from_previous_step_factor=10, initialize_from_previous_lr_factor=0.1, fg_mask_th=0.1,
-                    local_viewdirs=None, batch_shape=None, renderArgs=None, ssim_data_range=2.0, lpips=None):
+                    local_viewdirs=None, batch_shape=None, renderArgs=None, ssim_data_range=2.0, lpips=None,
+                    tof=None):
     """eval.py:43-166 with the reference's keyword names and defaults, ground-truth TENSORS (gt_images [K,3,H,W] in [0, 1],
     or K tensors [3,H,W]) in place of a directory of PNGs, and a result in place of None.  scene: anything with
     .stat_gaussians and .dyn_gaussians (and optionally .dataset_type); renderArgs = [pipe, background].
@@ -266,9 +267,12 @@ def render_test_tto(H, W, scene, test_cams, save_dir, gt_images, tto_steps=25, d
     has tto_steps * step_factor[k] entries), "step_factors", "lr_factors": what each camera ran with, "metrics":
     metrics.image_metrics(images, gt, data_range=ssim_data_range, clamp=True, quantize=True) -- the scores of the written
     PNGs, without reading them back}.  lpips: None, or a mobgs_amd.lpips.LpipsAlex: the result then also holds "lpips", its
-    LpipsResult on the same pairs with clamp=True, quantize=True (metrics.py:127-131 on the written PNGs)."""
+    LpipsResult on the same pairs with clamp=True, quantize=True (metrics.py:127-131 on the written PNGs).  tof: None, True,
+    or a metrics.TofTarget built from these ground truths with clamp=True: the cameras are then taken as consecutive frames
+    and the result also holds "tof_per_pair" ([K-1] float64, device: metrics.temporal_of with clamp=True, quantize=True,
+    metrics.py:108-120 on the written PNGs) and "tof", its mean as a Python float."""
     from .gaussian_renderer import render
-    from .metrics import image_metrics
+    from .metrics import TofTarget, image_metrics, temporal_of
     what = "render_test_tto"
     if use_sgd:
         raise NotImplementedError(f"{what}: use_sgd=True (the reference never enables it)")
@@ -322,4 +326,8 @@ def render_test_tto(H, W, scene, test_cams, save_dir, gt_images, tto_steps=25, d
               "lr_factors": lr_factors, "metrics": metrics}
     if lpips is not None:
         result["lpips"] = lpips(images, gt_stack, clamp=True, quantize=True)
+    if tof is not None and tof is not False:
+        result["tof_per_pair"] = temporal_of(images, tof if isinstance(tof, TofTarget) else gt_stack, clamp=True,
+                                             quantize=True)
+        result["tof"] = float(result["tof_per_pair"].mean())
     return result
