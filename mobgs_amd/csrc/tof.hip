@@ -22,9 +22,10 @@
 // Arithmetic: fp32 as OpenCV's, with three exceptions that only make it more exact.  (1) Resize coordinates are exact
 // rationals ((2 dx + 1) src - dst) / (2 dst): an integer floor and ONE rounded division for the weight.  (2) The sample
 // position x + u is split as (x + floor(u), u - floor(u)), both exact, so the in-bounds test is an integer test.  (3) The
-// polynomial expansion subtracts the tile's centre value before fitting (a constant changes only the constant coefficient,
-// which is not kept): r_xx = b_1 ig03 + b_xx ig33 then cancels on values of the size of the local contrast, not of the grey
-// level.  The 15x15 box sums and the 2x2 solve are float64 (OpenCV's are too).  Built with -ffp-contract=off.
+// polynomial expansion subtracts a value near the tile's centre value before fitting (a constant changes only the constant
+// coefficient, which is not kept): r_xx = b_1 ig03 + b_xx ig33 then cancels on values of the size of the local contrast, not
+// of the grey level; the value is limited so that no patch entry grows in magnitude (tof_polyexp_kernel).  The 15x15 box
+// sums and the 2x2 solve are float64 (OpenCV's are too).  Built with -ffp-contract=off.
 #include <math.h>
 
 #include "common.h"
@@ -130,14 +131,43 @@ struct TofPolyArgs {
 __global__ void __launch_bounds__(TOF_BLOCK) tof_polyexp_kernel(TofPolyArgs a) {
     __shared__ float s_p[TOF_PP][TOF_PP + 1];
     __shared__ float s_v[3][TOF_T][TOF_PP + 1];
+    __shared__ float s_lo[TOF_WAVES], s_hi[TOF_WAVES];
     const int h = a.h, w = a.w;
     const size_t plane = (size_t)h * w;
     const float* src = a.img + (size_t)blockIdx.z * plane;
     const int x0 = blockIdx.x * TOF_T, y0 = blockIdx.y * TOF_T;
-    const float centre = src[(size_t)tof_clampi(y0 + TOF_T / 2, h) * w + tof_clampi(x0 + TOF_T / 2, w)];
+    float centre = src[(size_t)tof_clampi(y0 + TOF_T / 2, h) * w + tof_clampi(x0 + TOF_T / 2, w)];
+    float lo = INFINITY, hi = -INFINITY;
     for (int i = threadIdx.x; i < TOF_PP * TOF_PP; i += TOF_BLOCK) {
         const int py = i / TOF_PP, px = i - py * TOF_PP;
-        s_p[py][px] = src[(size_t)tof_clampi(y0 + py - TOF_PN, h) * w + tof_clampi(x0 + px - TOF_PN, w)] - centre;
+        const float v = src[(size_t)tof_clampi(y0 + py - TOF_PN, h) * w + tof_clampi(x0 + px - TOF_PN, w)];
+        s_p[py][px] = v;
+        lo = fminf(lo, v);
+        hi = fmaxf(hi, v);
+    }
+#pragma unroll
+    for (int off = MOBGS_WAVE / 2; off > 0; off >>= 1) {
+        lo = fminf(lo, __shfl_xor(lo, off, MOBGS_WAVE));
+        hi = fmaxf(hi, __shfl_xor(hi, off, MOBGS_WAVE));
+    }
+    if ((threadIdx.x & (MOBGS_WAVE - 1)) == 0) {
+        s_lo[threadIdx.x / MOBGS_WAVE] = lo;
+        s_hi[threadIdx.x / MOBGS_WAVE] = hi;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < TOF_WAVES; ++k) {
+        lo = fminf(lo, s_lo[k]);
+        hi = fmaxf(hi, s_hi[k]);
+    }
+    // the value every patch entry is taken relative to: the tile's centre value, limited to twice the patch's value nearest
+    // to 0 (0 if the patch changes sign).  For lo >= 0 that is c = min(centre, 2 lo), and |v - c| <= |v| for every entry:
+    // v >= c gives v - c <= v, v < c gives c - v <= 2 lo - v <= v.  No term of a sum grows, so a dark region next to a bright
+    // one is as exact as without the shift.  2 lo is exact; on a flat patch c is its value and every entry exactly 0.
+    centre = lo >= 0.f ? fminf(centre, 2.f * lo) : (hi <= 0.f ? fmaxf(centre, 2.f * hi) : 0.f);
+    for (int i = threadIdx.x; i < TOF_PP * TOF_PP; i += TOF_BLOCK) {
+        const int py = i / TOF_PP, px = i - py * TOF_PP;
+        s_p[py][px] -= centre;
     }
     __syncthreads();
     // vertical pass: 16 rows x 26 columns: sum g s, sum k g s, sum k^2 g s
