@@ -1063,6 +1063,44 @@ int mobgs_lpips_pack_k(int layer);
 int mobgs_lpips_alex(int B, int H, int W, const float* img0, const float* img1, const MobgsLpipsWeights* weights,
                      int flags, void* scratch, size_t scratch_bytes, double* out, float* const* taps, void* stream);
 
+/* ---- K24, spatial and masked forms: the per-pixel LPIPS map and the two masked averages ---------------------------------
+ * What PNetLin.forward computes under spatial=True (models/networks_basic.py:24-28, :79-80) and with mask= (:16-22, :82),
+ * and what dycheck's compute_lpips reduces the map to (dycheck_metrics.py:203-244).  Same trunk, weights, flags, layout and
+ * per-pixel arithmetic as mobgs_lpips_alex, whose results keep their bits.  Entry points only: MOBGS_ABI_VERSION stays.
+ *
+ * Let d_l [h_l, w_l] be the head-weighted squared difference of the channel-normalised taps of a pair (the value
+ * mobgs_lpips_alex averages), l = 1 .. 5, fp32.
+ *   map [H, W] = up(d_1) + up(d_2) + ... + up(d_5), added in fp32 in that order; up is bilinear, align_corners = False, onto
+ *     H x W: source coordinate max(s (dst + 0.5) - 0.5, 0) with s = (float)h / (float)H formed on the host (one fp32 fma),
+ *     i0 = (int)src, i1 = i0 + (i0 < h - 1), t = src - i0, value (1 - ty) ((1 - tx) a + tx b) + ty ((1 - tx) c + tx d).  This
+ *     is nn.Upsample(size = (H, W)): defined for every size (the reference's scale_factor form yields H - 1 rows for some).
+ *   m_l = the mask resized to (h_l, w_l) by nearest neighbour: row min((int)floorf(i sH), H - 1) with sH = (float)H /
+ *     (float)h_l and the product rounded to fp32; columns alike.  d_l m_l is formed in fp32, every sum is float64.
+ * mask [B, H, W] fp32 in [0, 1], or NULL = all ones (the same bits as a mask of ones).
+ * map [B, H, W] fp32 or NULL: receives the map; the row in `out` has the same bits with and without it.
+ * out [B, MOBGS_LPIPS_SPATIAL_COLUMNS] float64 (device), per pair:
+ *   0        mean of the map, sum(map) / (H W)
+ *   1        dycheck's masked mean, sum(map m) / max(sum(m), 1e-6)   (map m exact in float64)
+ *   2, 3, 4  sum(map m), sum(m), sum(map)
+ *   5        the sum of the five masked layer values (columns 6 .. 10, added in that order)
+ *   6 .. 10  the reference's masked average per layer, numerator_l / (denominator_l + 1e-8)
+ *   11 .. 15 numerator_l = sum(d_l m_l);  16 .. 20 denominator_l = sum(m_l)
+ *   An empty mask gives 0 in columns 1 and 5 .. 10, never NaN; equal images give a map of +0 and 0 in every column but 3
+ *   and 16 .. 20.  (The reference's mask= form divides sums over the WHOLE batch: callers form that from 11 .. 20.)
+ * scratch: mobgs_lpips_spatial_scratch_bytes(B, H, W) bytes, 256-byte aligned, contents irrelevant on entry (the scratch of
+ *   mobgs_lpips_alex, the five d maps -- sum h_l w_l floats per pair -- and the float64 partial sums).  0 for a refused shape.
+ * Every sum has a fixed order that depends on the sizes alone; a pair is a grid index; no atomics.  So a pair's row and map
+ * are bit-identical from run to run, whatever B is and wherever the pair sits in the batch.
+ * Refused with MOBGS_E_INVALID before any launch, under the entry point's name: as mobgs_lpips_alex (mask and map may be
+ *   NULL; 4-byte aligned otherwise).
+ * 15 launches (5 convolutions, 2 pools, 5 distance-map kernels, the masked sums, the upsample-and-reduce kernel, one finish),
+ * no synchronisation, no read-back. */
+#define MOBGS_LPIPS_SPATIAL_COLUMNS 21
+size_t mobgs_lpips_spatial_scratch_bytes(int B, int H, int W);
+int mobgs_lpips_alex_spatial(int B, int H, int W, const float* img0, const float* img1, const MobgsLpipsWeights* weights,
+                             const float* mask, int flags, void* scratch, size_t scratch_bytes, float* map, double* out,
+                             void* stream);
+
 /* ---- K25: tOF, the temporal optical-flow metric: dense Farneback flow and the distance of two flow fields -----------
  * What the reference's metrics.py:14-47 and :108-120 evaluate: cv2.calcOpticalFlowFarneback(prev, next, None, 0.5, 3, 15,
  * 3, 5, 1.2, 0) between consecutive 8-bit grey frames, for the prediction and for the ground truth, and the mean of

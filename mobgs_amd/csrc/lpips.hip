@@ -19,6 +19,15 @@
 //                              and a butterfly adds the lane sums (float64, an order that depends on the tap's size
 //                              alone), divides by the tap's pixels, adds the five layer values.
 //
+// The spatial and masked forms (mobgs_lpips_alex_spatial: networks_basic.py:16-28, :79-82, dycheck_metrics.py:203-244):
+//   lpips_dist_kernel<true>    the same kernel; a pixel's d is also stored into a small map [B, sum h_l w_l].
+//   lpips_mask_sum_kernel      one launch for the five taps: d m_l (fp32 product) and m_l, m_l = the mask's nearest
+//                              neighbour, added in float64 per 64 pixels in the distance kernel's order.
+//   lpips_upsample_kernel      per output pixel the bilinear value (align_corners = False) of each of the five d maps, their
+//                              fp32 sum in layer order, an optional store, float64 sums of map m, m and map: thread,
+//                              wave butterfly, workgroup, one partial row per 1024 pixels of a pair.
+//   lpips_spatial_finish_kernel  one workgroup, one wave per pair: the sums in lpips_finish_kernel's order, the row.
+//
 // Every output of a convolution is one k-ordered fmaf chain (the fp32 MFMA adds nothing wider), the same chain whatever tile
 // or row of a tile the pixel falls into; the workgroups of the distance kernel are cut per pair.  No float atomic, no
 // hand-off between workgroups inside a launch.  So a pair's result is bit-identical from run to run, whatever the batch
@@ -38,6 +47,10 @@ constexpr int LP_MAX_B = 4096, LP_MAX_EDGE = 16384, LP_MIN_EDGE = 31;
 constexpr long long LP_MAX_M = 1ll << 30;
 constexpr int LP_K1 = 363;
 static_assert(MOBGS_LPIPS_COLUMNS == LP_LAYERS + 1, "out columns of include/mobgs_hip.h");
+constexpr int LP_UPIX = 4;                   // output pixels per thread of the upsample kernel
+constexpr int LP_UP_BLOCK = LP_THREADS * LP_UPIX;
+static_assert(MOBGS_LPIPS_SPATIAL_COLUMNS == 6 + 3 * LP_LAYERS, "out columns of the spatial call");
+static_assert(LP_THREADS / MOBGS_WAVE == 4, "the workgroups add four wave sums");
 
 static const int LP_CIN[LP_LAYERS] = {3, 64, 192, 384, 256};
 static const int LP_COUT[LP_LAYERS] = {64, 192, 384, 256, 256};
@@ -196,11 +209,23 @@ __device__ __forceinline__ float lp_wave_sum(float v) {
     return v;                                            // (a + b == b + a: every lane holds the same bits)
 }
 
-// feat [2B, P, C] (P pixels per image), lin [C]; grid (rows, B); partial[b * rows_total + row_off + blockIdx.x]
+// the MAP arm of the distance kernel (mobgs_lpips_alex_spatial): where a pixel's d goes
+struct LpMapArgs {
+    float* dmap;                     // [B, p_total]: this tap's d at p_off + p
+    int p_total, p_off;
+};
+
+// feat [2B, P, C] (P pixels per image), lin [C]; grid (rows, B); partial[b * rows_total + row_off + blockIdx.x].
+// MAP: the same statements, and the wave also stores the pixel's d -- every lane, without a branch.  Nothing else differs,
+// on purpose: which products the compiler fuses or pairs in the loop depends on what surrounds them (a store under
+// `lane == 0` splits the block, and the packed multiplications of the plain arm become fused ones: d moves by an ulp), and
+// both arms must form the same fp32 d.  The two arms' floating-point instruction sequences were compared after the build;
+// tests/test_gpu_lpips_spatial.py holds the values together (numerators of an all-ones mask against the plain call).
+template <bool MAP>
 __global__ void __launch_bounds__(LP_THREADS) lpips_dist_kernel(const float* __restrict__ feat,
                                                                 const float* __restrict__ lin, int P, int C,
                                                                 int rows_total, int row_off,
-                                                                double* __restrict__ partial) {
+                                                                double* __restrict__ partial, LpMapArgs ma) {
     __shared__ double s_wave[LP_THREADS / MOBGS_WAVE];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const size_t pair = blockIdx.y;
@@ -229,12 +254,64 @@ __global__ void __launch_bounds__(LP_THREADS) lpips_dist_kernel(const float* __r
             const float e = u[j] / du - v[j] / dv;
             d += w[j] * (e * e);
         }
-        sum += (double)lp_wave_sum(d);
+        const float dp = lp_wave_sum(d);
+        if (MAP) ma.dmap[pair * ma.p_total + ma.p_off + p] = dp;       // (every lane holds the same bits: one address, one value)
+        sum += (double)dp;
     }
     if (lane == 0) s_wave[wave] = sum;
     __syncthreads();
     if (threadIdx.x == 0)
         partial[pair * rows_total + row_off + blockIdx.x] = ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
+}
+
+// the masked sums of the five d maps (the reference's spatial_average with a mask), one launch for all taps
+struct LpMaskSumArgs {
+    const float* dmap;               // [B, p_total]
+    const float* mask;               // [B, H, W], or nullptr = all ones
+    double* partial;                 // [B, rows_total, 2]: sum d m_l, sum m_l over 64 pixels of a tap
+    int H, W, p_total, rows_total;
+    int P[LP_LAYERS], w[LP_LAYERS], p_off[LP_LAYERS], row_off[LP_LAYERS];
+    float sH[LP_LAYERS], sW[LP_LAYERS];      // (float)H / (float)h, (float)W / (float)w
+};
+
+// grid (rows_total, B), one wave: the workgroup owns the 64 pixels the distance kernel's workgroup of that row owns, a lane
+// one pixel.  m_l = the mask's nearest neighbour of the pixel; d m_l is an fp32 product.  The sums are float64 in the
+// distance kernel's order -- pixels q, q + 4, q + 8, ... for q = 0 .. 3, then ((s0 + s1) + s2) + s3 --, so that with a mask
+// of ones the numerator has the bits of the plain call's sum.
+__global__ void __launch_bounds__(MOBGS_WAVE) lpips_mask_sum_kernel(LpMaskSumArgs a) {
+    __shared__ float s_dm[LP_DPIX], s_m[LP_DPIX];
+    __shared__ double s_q[8];
+    const int t = threadIdx.x, row = blockIdx.x;
+    const size_t pair = blockIdx.y;
+    int l = 0;
+#pragma unroll
+    for (int k = 1; k < LP_LAYERS; ++k) l += row >= a.row_off[k] ? 1 : 0;
+    const int p = (row - a.row_off[l]) * LP_DPIX + t;
+    float dm = 0.f, m = 0.f;
+    if (p < a.P[l]) {
+        m = 1.f;
+        if (a.mask) {
+            const int ty = p / a.w[l], tx = p - ty * a.w[l];
+            const int iy = min((int)floorf((float)ty * a.sH[l]), a.H - 1), ix = min((int)floorf((float)tx * a.sW[l]), a.W - 1);
+            m = a.mask[(pair * a.H + iy) * a.W + ix];
+        }
+        dm = a.dmap[pair * a.p_total + a.p_off[l] + p] * m;
+    }
+    s_dm[t] = dm;
+    s_m[t] = m;
+    __syncthreads();
+    if (t < 8) {                                         // lanes 0 .. 3: d m_l of pixels t, t + 4, ...; lanes 4 .. 7: m_l
+        const float* src = t < 4 ? s_dm : s_m;
+        const int n = min(LP_DPIX, a.P[l] - (row - a.row_off[l]) * LP_DPIX);
+        double s = 0.0;
+        for (int q = t & 3; q < n; q += 4) s += (double)src[q];
+        s_q[t] = s;
+    }
+    __syncthreads();
+    if (t < 2) {
+        const double* q = s_q + 4 * t;
+        a.partial[(pair * a.rows_total + row) * 2 + t] = ((q[0] + q[1]) + q[2]) + q[3];
+    }
 }
 
 struct LpFinishArgs {
@@ -263,6 +340,130 @@ __global__ void __launch_bounds__(LP_FINISH_THREADS) lpips_finish_kernel(LpFinis
             total += v;
         }
         if (lane == 0) out[(size_t)b * MOBGS_LPIPS_COLUMNS] = total;
+    }
+}
+
+// ---- the spatial map: bilinear upsample of the five d maps, their fp32 sum, the float64 sums over the image -------------
+struct LpUpArgs {
+    const float* dmap;               // [B, p_total]: the five d maps of a pair, tap l at p_off[l]
+    const float* mask;               // [B, H, W], or nullptr = all ones
+    float* map;                      // [B, H, W], or nullptr
+    double* partial;                 // [B, gridDim.x, 3]: sum map m, sum m, sum map of a workgroup's pixels
+    int H, W, p_total;
+    int h[LP_LAYERS], w[LP_LAYERS], p_off[LP_LAYERS];
+    float sy[LP_LAYERS], sx[LP_LAYERS];      // (float)h / (float)H, (float)w / (float)W
+};
+
+// align_corners = False: the source coordinate of output index dst, its two neighbours and the weight of the second
+__device__ __forceinline__ void lp_source(float s, int dst, int n, int& i0, int& i1, float& t) {
+    const float src = fmaxf(fmaf(s, (float)dst + 0.5f, -0.5f), 0.f);
+    i0 = min((int)src, n - 1);                           // (src < n - 1/2: the min never acts; it keeps the reads inside)
+    i1 = i0 + (i0 < n - 1 ? 1 : 0);
+    t = src - (float)i0;
+}
+
+// grid (blocks, B); a workgroup owns LP_UP_BLOCK consecutive pixels of a pair's H x W image, a thread the pixels t, t + 256,
+// ... of them (coalesced mask reads and map stores).  The d maps are small (L2 / L1 hits).  A thread adds its pixels in
+// float64 in that order, a butterfly adds the lanes (every lane ends with the same bits), thread 0 the four waves.
+__global__ void __launch_bounds__(LP_THREADS) lpips_upsample_kernel(LpUpArgs a) {
+    __shared__ double s_wave[3 * (LP_THREADS / MOBGS_WAVE)];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const size_t pair = blockIdx.y;
+    const int HW = a.H * a.W;                            // <= 2^28
+    const float* dm = a.dmap + pair * a.p_total;
+    double s_mm = 0.0, s_m = 0.0, s_map = 0.0;
+    for (int k = 0; k < LP_UPIX; ++k) {
+        const long long idx = (long long)blockIdx.x * LP_UP_BLOCK + k * LP_THREADS + threadIdx.x;
+        if (idx < HW) {
+            const int y = (int)(idx / a.W), x = (int)(idx - (long long)y * a.W);
+            int y0 = 0, y1 = 0, x0 = 0, x1 = 0;
+            float ty = 0.f, tx = 0.f, val = 0.f;
+#pragma unroll
+            for (int l = 0; l < LP_LAYERS; ++l) {
+                if (l < 3) {                             // taps 3, 4 and 5 have one size
+                    lp_source(a.sy[l], y, a.h[l], y0, y1, ty);
+                    lp_source(a.sx[l], x, a.w[l], x0, x1, tx);
+                }
+                const float* q = dm + a.p_off[l];
+                const float v00 = q[y0 * a.w[l] + x0], v01 = q[y0 * a.w[l] + x1];
+                const float v10 = q[y1 * a.w[l] + x0], v11 = q[y1 * a.w[l] + x1];
+                const float up = (1.f - ty) * ((1.f - tx) * v00 + tx * v01) + ty * ((1.f - tx) * v10 + tx * v11);
+                val = l == 0 ? up : val + up;
+            }
+            const float m = a.mask ? a.mask[pair * HW + idx] : 1.f;
+            if (a.map) a.map[pair * HW + idx] = val;
+            s_mm += (double)val * (double)m;             // (exact product)
+            s_m += (double)m;
+            s_map += (double)val;
+        }
+    }
+#pragma unroll
+    for (int off = MOBGS_WAVE / 2; off > 0; off >>= 1) {
+        s_mm += __shfl_xor(s_mm, off, MOBGS_WAVE);
+        s_m += __shfl_xor(s_m, off, MOBGS_WAVE);
+        s_map += __shfl_xor(s_map, off, MOBGS_WAVE);
+    }
+    if (lane == 0) {
+        s_wave[3 * wave] = s_mm;
+        s_wave[3 * wave + 1] = s_m;
+        s_wave[3 * wave + 2] = s_map;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const int c = threadIdx.x;
+        a.partial[(pair * gridDim.x + blockIdx.x) * 3 + c] = ((s_wave[c] + s_wave[3 + c]) + s_wave[6 + c]) + s_wave[9 + c];
+    }
+}
+
+struct LpSpatialFinishArgs {
+    int B, rows_total, up_blocks;
+    int rows[LP_LAYERS], row_off[LP_LAYERS];
+    double pixels;                   // H W
+};
+
+// n values at p[0], p[stride], ...: the lanes add contiguous runs, a butterfly adds the 64 lane sums (the order of
+// lpips_finish_kernel: it depends on n alone, and every lane ends with the same bits)
+__device__ __forceinline__ double lp_run_sum(const double* __restrict__ p, int n, int stride, int lane) {
+    const int per = (n + MOBGS_WAVE - 1) / MOBGS_WAVE;
+    const int r0 = min(lane * per, n), r1 = min(r0 + per, n);
+    double s = 0.0;
+    for (int r = r0; r < r1; ++r) s += p[(size_t)r * stride];
+#pragma unroll
+    for (int off = MOBGS_WAVE / 2; off > 0; off >>= 1) s += __shfl_xor(s, off, MOBGS_WAVE);
+    return s;
+}
+
+// one workgroup of LP_FINISH_THREADS; wave v owns the pairs v, v + 16, ...; writes the row of include/mobgs_hip.h
+__global__ void __launch_bounds__(LP_FINISH_THREADS) lpips_spatial_finish_kernel(LpSpatialFinishArgs a,
+                                                                                 const double* __restrict__ dpart,
+                                                                                 const double* __restrict__ upart,
+                                                                                 double* __restrict__ out) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int b = wave; b < a.B; b += LP_FINISH_THREADS / MOBGS_WAVE) {
+        double* o = out + (size_t)b * MOBGS_LPIPS_SPATIAL_COLUMNS;
+        const double* u = upart + (size_t)b * a.up_blocks * 3;
+        const double mm = lp_run_sum(u, a.up_blocks, 3, lane), m = lp_run_sum(u + 1, a.up_blocks, 3, lane);
+        const double sm = lp_run_sum(u + 2, a.up_blocks, 3, lane);
+        double total = 0.0;
+        for (int l = 0; l < LP_LAYERS; ++l) {
+            const double* p = dpart + ((size_t)b * a.rows_total + a.row_off[l]) * 2;
+            const double num = lp_run_sum(p, a.rows[l], 2, lane), den = lp_run_sum(p + 1, a.rows[l], 2, lane);
+            const double v = num / (den + 1e-8);
+            if (lane == 0) {
+                o[6 + l] = v;
+                o[11 + l] = num;
+                o[16 + l] = den;
+            }
+            total += v;
+        }
+        if (lane == 0) {
+            o[0] = sm / a.pixels;
+            o[1] = mm / fmax(m, 1e-6);
+            o[2] = mm;
+            o[3] = m;
+            o[4] = sm;
+            o[5] = total;
+        }
     }
 }
 
@@ -317,37 +518,39 @@ static bool lp_plan(int B, int H, int W, LpPlan& p) {
     return true;
 }
 
-}  // namespace mobgs
+// what mobgs_lpips_alex_spatial needs behind the plain call's scratch
+struct LpSpatialPlan {
+    int p_off[LP_LAYERS], p_total;       // the five d maps of a pair, floats
+    int up_blocks;                       // workgroups of the upsample kernel per pair
+    size_t off_dmap, off_dpart, off_upart, bytes;
+};
 
-using namespace mobgs;
-
-extern "C" {
-
-size_t mobgs_lpips_scratch_bytes(int B, int H, int W) {
-    LpPlan p;
-    return lp_plan(B, H, W, p) ? p.bytes : 0;
-}
-
-int mobgs_lpips_pack_k(int layer) {
-    if (layer < 1 || layer > LP_LAYERS) return 0;
-    const int K = LP_CIN[layer - 1] * LP_KS[layer - 1] * LP_KS[layer - 1];
-    return (K + LP_BK - 1) / LP_BK * LP_BK;
-}
-
-int mobgs_lpips_alex(int B, int H, int W, const float* img0, const float* img1, const MobgsLpipsWeights* weights,
-                     int flags, void* scratch, size_t scratch_bytes, double* out, float* const* taps, void* stream) {
-    LpPlan p;
-    if (!lp_plan(B, H, W, p)) {
-        set_error("mobgs_lpips_alex: B = %d, H = %d, W = %d outside 1 <= B <= %d, %d <= H, W <= %d, 2 B h1 w1 <= 2^30 (below "
-                  "31 the second pool has no output)", B, H, W, LP_MAX_B, LP_MIN_EDGE, LP_MAX_EDGE);
-        return MOBGS_E_INVALID;
+static bool lp_spatial_plan(int B, int H, int W, LpPlan& p, LpSpatialPlan& q) {
+    if (!lp_plan(B, H, W, p)) return false;
+    q.p_total = 0;
+    for (int l = 0; l < LP_LAYERS; ++l) {
+        q.p_off[l] = q.p_total;
+        q.p_total += p.h[l] * p.w[l];
     }
+    q.up_blocks = (int)(((long long)H * W + LP_UP_BLOCK - 1) / LP_UP_BLOCK);
+    q.off_dmap = p.bytes;
+    q.off_dpart = q.off_dmap + lp_align((size_t)B * q.p_total * sizeof(float));
+    q.off_upart = q.off_dpart + lp_align((size_t)B * p.rows_total * 2 * sizeof(double));
+    q.bytes = q.off_upart + lp_align((size_t)B * q.up_blocks * 3 * sizeof(double));
+    return true;
+}
+
+// both entry points: the checks, the trunk with its distance kernels, the finish.  sp: the spatial call's plan or nullptr
+static int lp_run(const char* name, const LpPlan& p, const LpSpatialPlan* sp, int B, int H, int W, const float* img0,
+                  const float* img1, const MobgsLpipsWeights* weights, const float* mask, int flags, void* scratch,
+                  size_t scratch_bytes, float* map, double* out, float* const* taps, void* stream) {
+    const size_t need = sp ? sp->bytes : p.bytes;
     if (flags & ~(MOBGS_LPIPS_UNIT_RANGE | MOBGS_LPIPS_CLAMP | MOBGS_LPIPS_QUANTIZE)) {
-        set_error("mobgs_lpips_alex: flags = %d has unknown bits", flags);
+        set_error("%s: flags = %d has unknown bits", name, flags);
         return MOBGS_E_INVALID;
     }
     if (!img0 || !img1 || !weights || !scratch || !out) {
-        set_error("mobgs_lpips_alex: NULL img0, img1, weights, scratch or out");
+        set_error("%s: NULL img0, img1, weights, scratch or out", name);
         return MOBGS_E_INVALID;
     }
     const float* w[LP_LAYERS] = {weights->w1, weights->w2, weights->w3, weights->w4, weights->w5};
@@ -355,29 +558,35 @@ int mobgs_lpips_alex(int B, int H, int W, const float* img0, const float* img1, 
     const float* lin[LP_LAYERS] = {weights->lin1, weights->lin2, weights->lin3, weights->lin4, weights->lin5};
     for (int l = 0; l < LP_LAYERS; ++l) {
         if (!w[l] || !bias[l] || !lin[l] || (taps && !taps[l])) {
-            set_error("mobgs_lpips_alex: NULL weight, bias, head or tap pointer of layer %d", l + 1);
+            set_error("%s: NULL weight, bias, head or tap pointer of layer %d", name, l + 1);
             return MOBGS_E_INVALID;
         }
         if (((uintptr_t)w[l] & 15) || ((uintptr_t)bias[l] & 3) || ((uintptr_t)lin[l] & 3) ||
             (taps && ((uintptr_t)taps[l] & 15))) {
-            set_error("mobgs_lpips_alex: layer %d: packed weights and taps must be 16-byte aligned, biases and heads 4-byte",
-                      l + 1);
+            set_error("%s: layer %d: packed weights and taps must be 16-byte aligned, biases and heads 4-byte", name, l + 1);
             return MOBGS_E_INVALID;
         }
     }
     if (((uintptr_t)img0 & 3) || ((uintptr_t)img1 & 3) || ((uintptr_t)scratch & 255) || ((uintptr_t)out & 7)) {
-        set_error("mobgs_lpips_alex: images must be 4-byte aligned, scratch 256-byte aligned, out 8-byte aligned");
+        set_error("%s: images must be 4-byte aligned, scratch 256-byte aligned, out 8-byte aligned", name);
         return MOBGS_E_INVALID;
     }
-    if (scratch_bytes < p.bytes) {
-        set_error("mobgs_lpips_alex: scratch_bytes = %zu, mobgs_lpips_scratch_bytes(%d, %d, %d) = %zu", scratch_bytes, B, H,
-                  W, p.bytes);
+    if (((uintptr_t)mask & 3) || ((uintptr_t)map & 3)) {
+        set_error("%s: mask and map must be 4-byte aligned", name);
+        return MOBGS_E_INVALID;
+    }
+    if (scratch_bytes < need) {
+        set_error("%s: scratch_bytes = %zu, %s(%d, %d, %d) = %zu", name, scratch_bytes,
+                  sp ? "mobgs_lpips_spatial_scratch_bytes" : "mobgs_lpips_scratch_bytes", B, H, W, need);
         return MOBGS_E_INVALID;
     }
     hipStream_t s = (hipStream_t)stream;
     char* base = (char*)scratch;
     float* region[2] = {(float*)(base + p.off_region[0]), (float*)(base + p.off_region[1])};
     double* partial = (double*)(base + p.off_partial);
+    float* dmap = sp ? (float*)(base + sp->off_dmap) : nullptr;
+    double* dpart = sp ? (double*)(base + sp->off_dpart) : nullptr;
+    double* upart = sp ? (double*)(base + sp->off_upart) : nullptr;
     const int N = 2 * B;
     static const int tap_region[LP_LAYERS] = {0, 0, 0, 1, 0};
     const float* cur = nullptr;                          // the input of the next convolution
@@ -410,8 +619,17 @@ int mobgs_lpips_alex(int B, int H, int W, const float* img0, const float* img1, 
         else
             hipLaunchKernelGGL(lpips_conv_kernel<false>, dim3(blocks), dim3(LP_THREADS), 0, s, a);
         const int P = p.h[l] * p.w[l];
-        hipLaunchKernelGGL(lpips_dist_kernel, dim3((unsigned)p.rows[l], (unsigned)B), dim3(LP_THREADS), 0, s,
-                           (const float*)tap, lin[l], P, a.Cout, p.rows_total, p.row_off[l], partial);
+        LpMapArgs ma = {};
+        if (sp) {
+            ma.dmap = dmap;
+            ma.p_total = sp->p_total;
+            ma.p_off = sp->p_off[l];
+            hipLaunchKernelGGL(lpips_dist_kernel<true>, dim3((unsigned)p.rows[l], (unsigned)B), dim3(LP_THREADS), 0, s,
+                               (const float*)tap, lin[l], P, a.Cout, p.rows_total, p.row_off[l], partial, ma);
+        } else {
+            hipLaunchKernelGGL(lpips_dist_kernel<false>, dim3((unsigned)p.rows[l], (unsigned)B), dim3(LP_THREADS), 0, s,
+                               (const float*)tap, lin[l], P, a.Cout, p.rows_total, p.row_off[l], partial, ma);
+        }
         cur = tap;
         cur_h = p.h[l];
         cur_w = p.w[l];
@@ -426,6 +644,51 @@ int mobgs_lpips_alex(int B, int H, int W, const float* img0, const float* img1, 
             cur_w = p.pw[l];
         }
     }
+    if (sp) {
+        LpMaskSumArgs ms;
+        ms.dmap = dmap;
+        ms.mask = mask;
+        ms.partial = dpart;
+        ms.H = H;
+        ms.W = W;
+        ms.p_total = sp->p_total;
+        ms.rows_total = p.rows_total;
+        for (int l = 0; l < LP_LAYERS; ++l) {
+            ms.P[l] = p.h[l] * p.w[l];
+            ms.w[l] = p.w[l];
+            ms.p_off[l] = sp->p_off[l];
+            ms.row_off[l] = p.row_off[l];
+            ms.sH[l] = (float)H / (float)p.h[l];
+            ms.sW[l] = (float)W / (float)p.w[l];
+        }
+        hipLaunchKernelGGL(lpips_mask_sum_kernel, dim3((unsigned)p.rows_total, (unsigned)B), dim3(MOBGS_WAVE), 0, s, ms);
+        LpUpArgs u;
+        u.dmap = dmap;
+        u.mask = mask;
+        u.map = map;
+        u.partial = upart;
+        u.H = H;
+        u.W = W;
+        u.p_total = sp->p_total;
+        LpSpatialFinishArgs f;
+        f.B = B;
+        f.rows_total = p.rows_total;
+        f.up_blocks = sp->up_blocks;
+        f.pixels = (double)H * (double)W;
+        for (int l = 0; l < LP_LAYERS; ++l) {
+            u.h[l] = p.h[l];
+            u.w[l] = p.w[l];
+            u.p_off[l] = sp->p_off[l];
+            u.sy[l] = (float)p.h[l] / (float)H;
+            u.sx[l] = (float)p.w[l] / (float)W;
+            f.rows[l] = p.rows[l];
+            f.row_off[l] = p.row_off[l];
+        }
+        hipLaunchKernelGGL(lpips_upsample_kernel, dim3((unsigned)sp->up_blocks, (unsigned)B), dim3(LP_THREADS), 0, s, u);
+        hipLaunchKernelGGL(lpips_spatial_finish_kernel, dim3(1), dim3(LP_FINISH_THREADS), 0, s, f, (const double*)dpart,
+                           (const double*)upart, out);
+        return check_launch(name);
+    }
     LpFinishArgs f;
     f.B = B;
     f.rows_total = p.rows_total;
@@ -435,7 +698,57 @@ int mobgs_lpips_alex(int B, int H, int W, const float* img0, const float* img1, 
         f.pixels[l] = (double)p.h[l] * (double)p.w[l];
     }
     hipLaunchKernelGGL(lpips_finish_kernel, dim3(1), dim3(LP_FINISH_THREADS), 0, s, f, (const double*)partial, out);
-    return check_launch("mobgs_lpips_alex");
+    return check_launch(name);
+}
+
+}  // namespace mobgs
+
+using namespace mobgs;
+
+extern "C" {
+
+size_t mobgs_lpips_scratch_bytes(int B, int H, int W) {
+    LpPlan p;
+    return lp_plan(B, H, W, p) ? p.bytes : 0;
+}
+
+size_t mobgs_lpips_spatial_scratch_bytes(int B, int H, int W) {
+    LpPlan p;
+    LpSpatialPlan q;
+    return lp_spatial_plan(B, H, W, p, q) ? q.bytes : 0;
+}
+
+int mobgs_lpips_pack_k(int layer) {
+    if (layer < 1 || layer > LP_LAYERS) return 0;
+    const int K = LP_CIN[layer - 1] * LP_KS[layer - 1] * LP_KS[layer - 1];
+    return (K + LP_BK - 1) / LP_BK * LP_BK;
+}
+
+int mobgs_lpips_alex(int B, int H, int W, const float* img0, const float* img1, const MobgsLpipsWeights* weights,
+                     int flags, void* scratch, size_t scratch_bytes, double* out, float* const* taps, void* stream) {
+    LpPlan p;
+    if (!lp_plan(B, H, W, p)) {
+        set_error("mobgs_lpips_alex: B = %d, H = %d, W = %d outside 1 <= B <= %d, %d <= H, W <= %d, 2 B h1 w1 <= 2^30 (below "
+                  "31 the second pool has no output)", B, H, W, LP_MAX_B, LP_MIN_EDGE, LP_MAX_EDGE);
+        return MOBGS_E_INVALID;
+    }
+    return lp_run("mobgs_lpips_alex", p, nullptr, B, H, W, img0, img1, weights, nullptr, flags, scratch, scratch_bytes,
+                  nullptr, out, taps, stream);
+}
+
+int mobgs_lpips_alex_spatial(int B, int H, int W, const float* img0, const float* img1, const MobgsLpipsWeights* weights,
+                             const float* mask, int flags, void* scratch, size_t scratch_bytes, float* map, double* out,
+                             void* stream) {
+    LpPlan p;
+    LpSpatialPlan q;
+    if (!lp_spatial_plan(B, H, W, p, q)) {
+        set_error("mobgs_lpips_alex_spatial: B = %d, H = %d, W = %d outside 1 <= B <= %d, %d <= H, W <= %d, 2 B h1 w1 <= 2^30 "
+                  "(below 31 the second pool has no output)", B, H, W, LP_MAX_B, LP_MIN_EDGE, LP_MAX_EDGE);
+        return MOBGS_E_INVALID;
+    }
+    return lp_run("mobgs_lpips_alex_spatial", p, &q, B, H, W, img0, img1, weights, mask, flags, scratch, scratch_bytes, map,
+                  out, nullptr, stream);
 }
 
 }  // extern "C"
+

@@ -1,29 +1,39 @@
 """LPIPS on the HIP path (csrc/lpips.hip, include/mobgs_hip.h K24): the "net-lin" model with the AlexNet trunk, version
-0.1, spatial average, no mask -- what the reference's metrics.py:84-85, :127-131 and eval.py:76 evaluate -- for a whole
-batch of image pairs in one call, without the reference's models/ package, torchvision or a DataParallel wrapper.
+0.1 -- the spatial average the reference's metrics.py:84-85, :127-131 and eval.py:76 evaluate, the per-pixel map of
+spatial=True and the two masked averages (the reference's mask=, dycheck's compute_lpips) -- for a whole batch of image
+pairs in one call, without the reference's models/ package, torchvision or a DataParallel wrapper.
 
     model = LpipsAlex.from_files(trunk="alexnet-owt-7be5be79.pth", heads=".../models/weights/v0.1/alex.pth", device="cuda")
     model = LpipsAlex(trunk_state_dict, heads_state_dict, device="cuda")
     r = model(pred, gt, clamp=False, quantize=False)   # [B,3,H,W] in [0, 1] -> LpipsResult(total [B], per_layer [B,5]) float64
     v = model.forward(in0, in1)                         # the reference's call: inputs in [-1, 1] -> [B,1,1,1] fp32
     maps = model.features(img)                          # the five ReLU maps, NCHW, for tests and debugging
+    s = model.spatial(pred, gt, mask)                   # LpipsSpatial: map [B,1,H,W] fp32, mean, masked_mean, ... float64
+    m = model.forward_spatial(in0, in1)                 # PerceptualLoss(spatial=True).forward: [B,1,H,W] fp32
+    v = model.forward_masked(in0, in1, mask)            # PNetLin.forward(mask=): a 0-dim fp32 tensor
 
-mirrors /root/reference/models/networks_basic.py:68-105 (PNetLin.forward, ScalingLayer), models/pretrained_networks.py:57-95
-(the five slices of torchvision's alexnet().features), models/__init__.py:26-44 and metrics.py:49-51.  Forward only, under
-no_grad; tensors must live on a HIP device.
+mirrors /root/reference/models/networks_basic.py:16-28 and :68-105 (spatial_average, upsample, PNetLin.forward,
+ScalingLayer), models/pretrained_networks.py:57-95 (the five slices of torchvision's alexnet().features),
+models/__init__.py:26-44, metrics.py:49-51 and dycheck_metrics.py:203-244.  Forward only, under no_grad; tensors must live
+on a HIP device.
+
+THE MAP is defined at H x W for every size: bilinear, align_corners=False, with the scale h / H (nn.Upsample(size=)).  The
+reference passes scale_factor = H / h, for which torch sizes the output as floor(h * scale_factor): H - 1 for some sizes
+(H = 49 with h = 11, 61 with 14, 98 with 11, ...), where the reference raises.  Where the reference's form works the two
+agree to rounding.
 
 THE WEIGHTS are the caller's: torchvision's AlexNet file for the trunk (keys features.{0,3,6,8,10}.{weight,bias}; other keys,
 the classifier's, are ignored) and the reference's v0.1/alex.pth for the heads (keys lin{0..4}.model.1.weight).  They are
 packed once, at construction, into the K-major layout the convolution kernel reads.  The value a user compares with the
 published one rests on that trunk file (README, "UNPINNED").
 
-Not here: a mask and spatial=True (dycheck's compute_lpips: NotImplementedError), the VGG and SqueezeNet trunks, gradients,
-reduced precision.
+Not here: the VGG and SqueezeNet trunks, gradients, reduced precision.  forward() itself keeps refusing mask= and
+spatial=True (NotImplementedError): forward_masked and forward_spatial are those calls.
 """
 from __future__ import annotations
 
 import ctypes
-from typing import List, NamedTuple
+from typing import List, NamedTuple, Optional
 
 import torch
 
@@ -38,11 +48,26 @@ MIN_EDGE = 31
 UNIT_RANGE, CLAMP, QUANTIZE = (_lib._DEFINES[k] for k in ("MOBGS_LPIPS_UNIT_RANGE", "MOBGS_LPIPS_CLAMP",
                                                            "MOBGS_LPIPS_QUANTIZE"))
 COLUMNS = _lib._DEFINES["MOBGS_LPIPS_COLUMNS"]
+SPATIAL_COLUMNS = _lib._DEFINES["MOBGS_LPIPS_SPATIAL_COLUMNS"]
 
 
 class LpipsResult(NamedTuple):
     total: torch.Tensor          # [B] float64, device: the sum of the five layer values
     per_layer: torch.Tensor      # [B,5] float64, device
+
+
+class LpipsSpatial(NamedTuple):
+    """LpipsAlex.spatial: float64 device tensors per pair (include/mobgs_hip.h K24, the spatial row), and the map."""
+    map: Optional[torch.Tensor]      # [B,1,H,W] fp32: the sum of the five upsampled distance maps; None without want_map
+    mean: torch.Tensor               # [B]: the map's mean
+    masked_mean: torch.Tensor        # [B]: dycheck's masked_mean, sum(map m) / max(sum(m), 1e-6)
+    masked_total: torch.Tensor       # [B]: the sum of masked_per_layer
+    masked_per_layer: torch.Tensor   # [B,5]: the reference's masked average per pair, numerators / (denominators + 1e-8)
+    numerators: torch.Tensor         # [B,5]: sum(d_l m_l), m_l the mask resized to the tap by nearest neighbour
+    denominators: torch.Tensor       # [B,5]: sum(m_l)
+    map_mask_sum: torch.Tensor       # [B]: sum(map m), sum(m) and sum(map)
+    mask_sum: torch.Tensor
+    map_sum: torch.Tensor
 
 
 def pack_k(layer: int) -> int:
@@ -124,6 +149,28 @@ def _pair(what, a, b):
     return f32c(a.detach()), f32c(b.detach())
 
 
+def _mask(what, mask, like):
+    """None, [B,H,W], [B,C,H,W] (its first channel, as the reference's mask[:, 0:1]) or, for one pair, [H,W] -> None or
+    [B,H,W] fp32 contiguous on the images' device."""
+    if mask is None:
+        return None
+    if not torch.is_tensor(mask):
+        raise TypeError(f"{what}: the mask must be a tensor")
+    if not mask.is_cuda:
+        raise RuntimeError(f"{what}: tensors must live on a HIP device (device='cuda'); there is no CPU path")
+    B, _, H, W = like.shape
+    if mask.dim() == 4:
+        mask = mask[:, 0]
+    elif mask.dim() == 2:
+        mask = mask[None]
+    if mask.dim() != 3 or tuple(mask.shape) != (B, H, W):
+        raise ValueError(f"{what}: the mask must be [B,H,W] or [B,C,H,W] with B, H, W = {B}, {H}, {W}, got "
+                         f"{tuple(mask.shape)}")
+    if mask.device != like.device:
+        raise ValueError(f"{what}: the mask is on {mask.device}, the images on {like.device}")
+    return f32c(mask.detach())
+
+
 class LpipsAlex:
     """The model, with its weights packed on one device.  Calls run on the current stream with 13 launches per chunk, no
     synchronisation, no read-back and no allocation that depends on the data: they can be recorded into a graph.  A pair's
@@ -158,13 +205,14 @@ class LpipsAlex:
 
     # ---- the call -----------------------------------------------------------------------------------------------------
 
-    def _chunk(self, B, H, W):
+    def _chunk(self, B, H, W, spatial=False):
         """The largest number of pairs whose scratch fits max_scratch_bytes (at least one)."""
         lib = _lib.load()
+        query = lib.mobgs_lpips_spatial_scratch_bytes if spatial else lib.mobgs_lpips_scratch_bytes
         n = B
-        while n > 1 and int(lib.mobgs_lpips_scratch_bytes(n, H, W)) > self.max_scratch_bytes:
+        while n > 1 and int(query(n, H, W)) > self.max_scratch_bytes:
             n = (n + 1) // 2
-        if int(lib.mobgs_lpips_scratch_bytes(n, H, W)) == 0:
+        if int(query(n, H, W)) == 0:
             raise ValueError(f"LpipsAlex: B = {n}, H = {H}, W = {W} is outside what mobgs_lpips_alex accepts")
         return n
 
@@ -189,6 +237,58 @@ class LpipsAlex:
                       "mobgs_lpips_alex")
         return out
 
+    def _run_spatial(self, img0, img1, mask, flags, want_map):
+        """-> (out [B, SPATIAL_COLUMNS] float64, map [B,1,H,W] fp32 or None), chunked like _run."""
+        lib = _lib.load()
+        B, _, H, W = img0.shape
+        dev = img0.device
+        out = torch.empty(B, SPATIAL_COLUMNS, dtype=torch.float64, device=dev)
+        fmap = torch.empty(B, 1, H, W, dtype=torch.float32, device=dev) if want_map else None
+        n = self._chunk(B, H, W, spatial=True)
+        nbytes = int(lib.mobgs_lpips_spatial_scratch_bytes(n, H, W))
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            for b0 in range(0, B, n):
+                b1 = min(B, b0 + n)
+                check(lib.mobgs_lpips_alex_spatial(b1 - b0, H, W, ptr(img0[b0:b1]), ptr(img1[b0:b1]),
+                                                   ctypes.byref(self._record), ptr(None if mask is None else mask[b0:b1]),
+                                                   flags, ptr(scratch), nbytes, ptr(None if fmap is None else fmap[b0:b1]),
+                                                   ptr(out[b0:b1]), stream()), "mobgs_lpips_alex_spatial")
+        return out, fmap
+
+    @torch.no_grad()
+    def spatial(self, pred, gt, mask=None, *, clamp=False, quantize=False, want_map=True) -> LpipsSpatial:
+        """pred, gt [B,3,H,W] (or [3,H,W]) in [0, 1]; mask [B,H,W] / [B,C,H,W] (first channel) in [0, 1], or None = all ones;
+        clamp, quantize as in __call__.  The images are taken as given: dycheck's compute_lpips multiplies them by the mask
+        first (mobgs_amd.metrics.compute_lpips does).  15 launches per chunk, no synchronisation, no read-back.  The row of
+        a pair has the same bits with and without want_map, whatever the batch and the chunking."""
+        p, g = _pair("LpipsAlex.spatial", pred, gt)
+        m = _mask("LpipsAlex.spatial", mask, p)
+        flags = UNIT_RANGE | (CLAMP if clamp else 0) | (QUANTIZE if quantize else 0)
+        out, fmap = self._run_spatial(g, p, m, flags, want_map)
+        return LpipsSpatial(fmap, out[:, 0], out[:, 1], out[:, 5], out[:, 6:11], out[:, 11:16], out[:, 16:21], out[:, 2],
+                            out[:, 3], out[:, 4])
+
+    @torch.no_grad()
+    def forward_spatial(self, pred, target, normalize=False) -> torch.Tensor:
+        """PerceptualLoss(spatial=True).forward: inputs in [-1, 1] (normalize=True: in [0, 1]) -> the map [B,1,H,W] fp32,
+        at H x W for every size (see the module docstring)."""
+        a, b = _pair("LpipsAlex.forward_spatial", target, pred)
+        return self._run_spatial(a, b, None, UNIT_RANGE if normalize else 0, True)[1]
+
+    @torch.no_grad()
+    def forward_masked(self, pred, target, mask, normalize=False) -> torch.Tensor:
+        """PNetLin.forward(mask=) through PerceptualLoss.forward (spatial=False): per layer sum(d_l m_l) / (sum(m_l) + 1e-8)
+        with BOTH sums taken over the whole batch, as the reference's torch.sum does, then the sum of the five -> a 0-dim
+        fp32 tensor.  mask [B,C,H,W] (its first channel) or [B,H,W]."""
+        a, b = _pair("LpipsAlex.forward_masked", target, pred)
+        if mask is None:
+            raise ValueError("LpipsAlex.forward_masked: a mask is required (forward() is the call without one)")
+        m = _mask("LpipsAlex.forward_masked", mask, a)
+        out, _ = self._run_spatial(a, b, m, UNIT_RANGE if normalize else 0, False)
+        layers = out[:, 11:16].sum(0) / (out[:, 16:21].sum(0) + 1e-8)
+        return layers.sum().float()
+
     @torch.no_grad()
     def __call__(self, pred, gt, clamp=False, quantize=False) -> LpipsResult:
         """pred, gt [B,3,H,W] (or [3,H,W]) in [0, 1].  clamp: both are clamped to [0, 1] first; quantize: the prediction is
@@ -202,7 +302,8 @@ class LpipsAlex:
     def forward(self, pred, target, mask=None, normalize=False, spatial=False) -> torch.Tensor:
         """PerceptualLoss.forward (models/__init__.py:26-40): inputs in [-1, 1] (normalize=True: in [0, 1]) -> [B,1,1,1] fp32."""
         if mask is not None or spatial:
-            raise NotImplementedError("LpipsAlex.forward: a mask and spatial=True (dycheck's compute_lpips) are not built")
+            raise NotImplementedError("LpipsAlex.forward: a mask and spatial=True are calls of their own: forward_masked, "
+                                      "forward_spatial (and spatial, which dycheck's compute_lpips reduces)")
         a, b = _pair("LpipsAlex.forward", target, pred)
         out = self._run(a, b, UNIT_RANGE if normalize else 0)
         return out[:, 0].float().reshape(-1, 1, 1, 1)

@@ -14,7 +14,8 @@ are four times what the images' own range would give.  This is a reading of that
 here.  So `data_range` is a required keyword of everything below that evaluates the box SSIM, and evaluate_views defaults
 to 2.0 (README, "UNPINNED").
 
-LPIPS is mobgs_amd.lpips (csrc/lpips.hip, K24); evaluate_views(..., lpips=model) adds it.  tOF, the temporal optical-flow
+LPIPS is mobgs_amd.lpips (csrc/lpips.hip, K24); evaluate_views(..., lpips=model) adds it, compute_lpips is dycheck's masked
+one, and evaluate_views(..., masks=) reports dycheck's masked triple mPSNR / mSSIM / mLPIPS.  tOF, the temporal optical-flow
 metric of metrics.py:14-47 and :108-120 (OpenCV's Farneback flow between consecutive frames, prediction against ground truth),
 is temporal_of / TofTarget below (csrc/tof.hip, K25); evaluate_views(..., tof=True) adds it.  Not here: gradients.  The
 test-time pose optimisation of eval.py is mobgs_amd.tto, which scores its images through image_metrics(clamp=True,
@@ -152,6 +153,29 @@ def compute_ssim(img0, img1, mask=None, max_val=1.0, filter_size=11, filter_sigm
     m = image_metrics(a, _chw("compute_ssim", "img1", img1), _hw_mask("compute_ssim", mask, a), data_range=max_val,
                       arms=("gauss",))
     return float(m.ssim_gauss)
+
+
+@torch.no_grad()
+def compute_lpips(lpips_model, img0, img1, mask=None, device=None) -> float:
+    """dycheck_metrics.py:203-244 (mLPIPS): both images [H,W,3] in [0, 1] are multiplied by the mask ([H,W,1] or [H,W];
+    None = ones), mapped to [-1, 1], and the masked mean of the model's spatial map is returned, sum(map m) / max(sum(m),
+    1e-6); 0 for an empty mask.  lpips_model: a mobgs_amd.lpips.LpipsAlex.  device: where arrays are uploaded to (default:
+    the model's device); tensors must already live on a HIP device."""
+    what = "compute_lpips"
+    dev = device if device is not None else getattr(lpips_model, "device", "cuda")
+
+    def up(x):
+        return x if torch.is_tensor(x) else torch.as_tensor(x).to(dev)
+
+    a, b = _chw(what, "img0", up(img0)), _chw(what, "img1", up(img1))
+    if a.shape != b.shape:
+        raise ValueError(f"{what}: img0 and img1 must have one shape, got {tuple(a.shape[-2:])} and {tuple(b.shape[-2:])}")
+    m = _hw_mask(what, None if mask is None else up(mask), a)
+    if m is None:
+        m = torch.ones(1, a.shape[2], a.shape[3], device=a.device)
+    m = m.to(torch.float32)
+    r = lpips_model.spatial(a.float() * m[:, None], b.float() * m[:, None], m, want_map=False)
+    return float(r.masked_mean)
 
 
 def calculate_psnr(img1, img2, mask) -> float:
@@ -367,7 +391,7 @@ def aligned_test_pose(input_train, input_test, output_train):
 
 @torch.no_grad()
 def evaluate_views(cams, stat_pc, dyn_pc, pipe, bg, gt_images, *, stage="fine", ssim_data_range=2.0, lpips=None,
-                   tof=None, **render_kw):
+                   tof=None, masks=None, **render_kw):
     """The test loop of training_report (train.py:895-925) with the SSIMs next to it: renders every camera through
     gaussian_renderer.render, stacks the images and scores them against gt_images ([K,3,H,W], or K tensors [3,H,W]) in ONE
     image_metrics call with clamp=True, then reads the result back ONCE.
@@ -383,7 +407,13 @@ def evaluate_views(cams, stat_pc, dyn_pc, pipe, bg, gt_images, *, stage="fine", 
 
     tof: None, True, or a TofTarget built from these ground truths with clamp=True: the cameras are then taken as
     consecutive frames, and the result also holds "tof_per_pair" ([K-1] float64, device: temporal_of on the clamped images)
-    and "tof", its mean as a Python float -- the mean_tof metrics.py:141-142 prints.  Needs K >= 2 and H, W >= 48."""
+    and "tof", its mean as a Python float -- the mean_tof metrics.py:141-142 prints.  Needs K >= 2 and H, W >= 48.
+
+    masks: None, or [K,H,W] / [K,1,H,W] co-visibility masks in [0, 1]: the result then also holds dycheck's masked triple on
+    the clamped images: "mpsnr" and "mssim" (the means of a second image_metrics call with the mask and data_range 1:
+    psnr_masked and the masked ssim_gauss; "per_view_masked" is its record) and, with lpips, "mlpips_per_view" ([K] float64,
+    device: compute_lpips's convention, both images times the mask, then the masked mean of the spatial map) and "mlpips".
+    Every other entry is what it is without masks."""
     from .gaussian_renderer import render
     cams = list(cams)
     if not cams:
@@ -397,6 +427,16 @@ def evaluate_views(cams, stat_pc, dyn_pc, pipe, bg, gt_images, *, stage="fine", 
     if lpips is not None:
         report["lpips_per_view"] = lpips(images, gt.to(images.device), clamp=True).total
         report["lpips"] = float(report["lpips_per_view"].mean())
+    if masks is not None:
+        gt_dev = gt.to(images.device)
+        masked = image_metrics(images, gt_dev, masks, data_range=1.0, clamp=True, arms=("gauss",))
+        report["per_view_masked"] = masked
+        report["mpsnr"], report["mssim"] = torch.stack([masked.psnr_masked, masked.ssim_gauss]).mean(1).tolist()
+        if lpips is not None:
+            m = masks.detach().reshape(len(cams), 1, *images.shape[-2:]).to(images.device, torch.float32)
+            report["mlpips_per_view"] = lpips.spatial(images.clamp(0, 1) * m, gt_dev.clamp(0, 1) * m, m[:, 0],
+                                                      want_map=False).masked_mean
+            report["mlpips"] = float(report["mlpips_per_view"].mean())
     if tof is not None and tof is not False:
         report["tof_per_pair"] = temporal_of(images, tof if isinstance(tof, TofTarget) else gt.to(images.device), clamp=True)
         report["tof"] = float(report["tof_per_pair"].mean())
