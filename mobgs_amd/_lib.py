@@ -191,12 +191,24 @@ def check(rc: int, what: str) -> None:
         raise RuntimeError(f"{what} failed (code {rc}): {msg}")
 
 
+NO_CPU_PATH = "tensors must live on a HIP device (device='cuda'); there is no CPU path"
+
+
+def device_tensor(what: str, name: str, t) -> torch.Tensor:
+    """t, if it is a tensor on a HIP device: TypeError for anything but a tensor, RuntimeError for a host tensor."""
+    if not torch.is_tensor(t):
+        raise TypeError(f"{what}: {name} must be a tensor")
+    if not t.is_cuda:
+        raise RuntimeError(f"{what}: {NO_CPU_PATH}")
+    return t
+
+
 def ptr(t: Optional[torch.Tensor]):
     """Device pointer of a contiguous HIP tensor (None -> NULL)."""
     if t is None:
         return None
     if not t.is_cuda:
-        raise RuntimeError("mobgs_amd: tensors must live on a HIP device (device='cuda'); there is no CPU path")
+        raise RuntimeError(f"mobgs_amd: {NO_CPU_PATH}")
     if not t.is_contiguous():
         raise RuntimeError("mobgs_amd: internal error, non-contiguous tensor passed to the C ABI")
     return c_void_p(t.data_ptr())

@@ -24,7 +24,7 @@
 // dense atomic instruction per (row, channel, warp) leaves instead of four (struct Scatter / StrayQueue below).
 #include <hip/hip_runtime.h>
 
-#include "common.h"
+#include "reduce_shared.h"
 
 namespace mobgs {
 
@@ -93,15 +93,6 @@ __device__ __forceinline__ float bilinear(const Quad& q, const Taps& t) {
     return o;
 }
 
-__device__ __forceinline__ float block_sum(float v, float* sm) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return sm[0] + sm[1] + sm[2] + sm[3];
-}
-
 // ori [B,3,H,W], latent [B,K,3,H,W], e2m / m2e [B,K,H,W,2], la [B,K,H,W], da [B,H,W]
 // partial [n_blocks,4] = {sum |d1 la|, sum la, sum |d2 da|, sum da (per exposure)} of the workgroup's pixels
 __global__ void __launch_bounds__(FL_THREADS)
@@ -140,7 +131,7 @@ flow_warp_l1_fwd_kernel(int B, int K, int H, int W, const float* __restrict__ or
             s2 += dav;
         }
     }
-    const float r0 = block_sum(n1, red), r1 = block_sum(s1, red), r2 = block_sum(n2, red), r3 = block_sum(s2, red);
+    const float r0 = block_sum4(n1, red), r1 = block_sum4(s1, red), r2 = block_sum4(n2, red), r3 = block_sum4(s2, red);
     if (threadIdx.x == 0) {
         float* p = partial + 4 * ((size_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x);
         p[0] = r0;

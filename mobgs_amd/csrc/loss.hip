@@ -13,7 +13,7 @@
 // partial sums plus the three derivative maps d(ssim)/d(mu1, E[x^2], E[xy]).  Backward convolves those maps with
 // the same window and combines them with the pixel values.  HBM traffic: 8 B read + 12 B written per element
 // forward, 20 B read + 4 B written backward.
-#include "common.h"
+#include "reduce_shared.h"
 
 namespace mobgs {
 
@@ -25,16 +25,6 @@ constexpr float SS_C1 = 0.01f * 0.01f, SS_C2 = 0.03f * 0.03f;
 struct Window {
     float w[11];
 };
-
-__device__ inline float block_sum_256(float v, float* sm) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const float r = sm[0] + sm[1] + sm[2] + sm[3];
-    __syncthreads();
-    return r;
-}
 
 // img1, img2: [C,H,W].  partial: [n_blocks, 2] = {sum of ssim_map, sum of |img1-img2|} per workgroup.
 // dmaps: [3][C,H,W] = d ssim / d{mu1, E[x^2], E[xy]} (only when non-null).
@@ -108,8 +98,8 @@ ssim_l1_fwd_kernel(int C, int H, int W, Window win, const float* __restrict__ im
             dmaps[2 * CP + o] = d_e12;
         }
     }
-    const float ts = block_sum_256(ssim_v, red);
-    const float tl = block_sum_256(l1_v, red);
+    const float ts = block_sum4(ssim_v, red);
+    const float tl = block_sum4(l1_v, red);
     if (threadIdx.x == 0) {
         const size_t blk = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
         partial[2 * blk] = ts;

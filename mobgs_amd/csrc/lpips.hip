@@ -32,7 +32,7 @@
 // or row of a tile the pixel falls into; the workgroups of the distance kernel are cut per pair.  No float atomic, no
 // hand-off between workgroups inside a launch.  So a pair's result is bit-identical from run to run, whatever the batch
 // around it; and with equal images both feature vectors, norms and normalised values are equal and every difference is 0.
-#include "common.h"
+#include "reduce_shared.h"
 
 namespace mobgs {
 
@@ -66,15 +66,13 @@ struct LpConvArgs {
     int N, Hi, Wi, Cin, Ho, Wo, Cout, ks, stride, pad, Kpad, M, flags;
 };
 
-__device__ __forceinline__ float lp_clamp01(float x) { return x < 0.f ? 0.f : (x > 1.f ? 1.f : x); }
-
 // the value the first convolution sees at (image n = 2 b + s, channel c, y, x): inside the image only
 __device__ __forceinline__ float lp_input(const LpConvArgs& a, int n, int c, int y, int x) {
     const int s = n & 1;
     const float* img = s ? a.img1 : a.img0;
     float v = img[(((size_t)(n >> 1) * 3 + c) * a.Hi + y) * a.Wi + x];
-    if (a.flags & MOBGS_LPIPS_CLAMP) v = lp_clamp01(v);
-    if ((a.flags & MOBGS_LPIPS_QUANTIZE) && s) v = floorf(lp_clamp01(v) * 255.f) / 255.f;
+    if (a.flags & MOBGS_LPIPS_CLAMP) v = clamp01(v);
+    if ((a.flags & MOBGS_LPIPS_QUANTIZE) && s) v = quantize8(v);
     if (a.flags & MOBGS_LPIPS_UNIT_RANGE) v = 2.f * v - 1.f;
     const float shift = c == 0 ? -.030f : (c == 1 ? -.088f : -.188f);
     const float scale = c == 0 ? .458f : (c == 1 ? .448f : .450f);
@@ -203,12 +201,6 @@ __global__ void __launch_bounds__(LP_THREADS) lpips_pool_kernel(const float* __r
     reinterpret_cast<float4*>(out)[idx] = m;
 }
 
-__device__ __forceinline__ float lp_wave_sum(float v) {
-#pragma unroll
-    for (int off = MOBGS_WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, MOBGS_WAVE);
-    return v;                                            // (a + b == b + a: every lane holds the same bits)
-}
-
 // the MAP arm of the distance kernel (mobgs_lpips_alex_spatial): where a pixel's d goes
 struct LpMapArgs {
     float* dmap;                     // [B, p_total]: this tap's d at p_off + p
@@ -247,14 +239,14 @@ __global__ void __launch_bounds__(LP_THREADS) lpips_dist_kernel(const float* __r
             su += u[j] * u[j];
             sv += v[j] * v[j];
         }
-        const float du = sqrtf(lp_wave_sum(su)) + 1e-10f, dv = sqrtf(lp_wave_sum(sv)) + 1e-10f;
+        const float du = sqrtf(wave_sum(su)) + 1e-10f, dv = sqrtf(wave_sum(sv)) + 1e-10f;
         float d = 0.f;
 #pragma unroll
         for (int j = 0; j < 6; ++j) {
             const float e = u[j] / du - v[j] / dv;
             d += w[j] * (e * e);
         }
-        const float dp = lp_wave_sum(d);
+        const float dp = wave_sum(d);
         if (MAP) ma.dmap[pair * ma.p_total + ma.p_off + p] = dp;       // (every lane holds the same bits: one address, one value)
         sum += (double)dp;
     }
@@ -329,13 +321,7 @@ __global__ void __launch_bounds__(LP_FINISH_THREADS) lpips_finish_kernel(LpFinis
         double total = 0.0;
         for (int l = 0; l < LP_LAYERS; ++l) {
             const double* p = partial + (size_t)b * a.rows_total + a.row_off[l];
-            const int rows = a.rows[l], per = (rows + MOBGS_WAVE - 1) / MOBGS_WAVE;
-            const int r0 = min(lane * per, rows), r1 = min(r0 + per, rows);
-            double s = 0.0;
-            for (int r = r0; r < r1; ++r) s += p[r];
-#pragma unroll
-            for (int off = MOBGS_WAVE / 2; off > 0; off >>= 1) s += __shfl_xor(s, off, MOBGS_WAVE);
-            const double v = s / a.pixels[l];
+            const double v = wave_rows_sum(p, a.rows[l], 1, lane) / a.pixels[l];
             if (lane == 0) out[(size_t)b * MOBGS_LPIPS_COLUMNS + 1 + l] = v;
             total += v;
         }
@@ -421,18 +407,6 @@ struct LpSpatialFinishArgs {
     double pixels;                   // H W
 };
 
-// n values at p[0], p[stride], ...: the lanes add contiguous runs, a butterfly adds the 64 lane sums (the order of
-// lpips_finish_kernel: it depends on n alone, and every lane ends with the same bits)
-__device__ __forceinline__ double lp_run_sum(const double* __restrict__ p, int n, int stride, int lane) {
-    const int per = (n + MOBGS_WAVE - 1) / MOBGS_WAVE;
-    const int r0 = min(lane * per, n), r1 = min(r0 + per, n);
-    double s = 0.0;
-    for (int r = r0; r < r1; ++r) s += p[(size_t)r * stride];
-#pragma unroll
-    for (int off = MOBGS_WAVE / 2; off > 0; off >>= 1) s += __shfl_xor(s, off, MOBGS_WAVE);
-    return s;
-}
-
 // one workgroup of LP_FINISH_THREADS; wave v owns the pairs v, v + 16, ...; writes the row of include/mobgs_hip.h
 __global__ void __launch_bounds__(LP_FINISH_THREADS) lpips_spatial_finish_kernel(LpSpatialFinishArgs a,
                                                                                  const double* __restrict__ dpart,
@@ -442,12 +416,12 @@ __global__ void __launch_bounds__(LP_FINISH_THREADS) lpips_spatial_finish_kernel
     for (int b = wave; b < a.B; b += LP_FINISH_THREADS / MOBGS_WAVE) {
         double* o = out + (size_t)b * MOBGS_LPIPS_SPATIAL_COLUMNS;
         const double* u = upart + (size_t)b * a.up_blocks * 3;
-        const double mm = lp_run_sum(u, a.up_blocks, 3, lane), m = lp_run_sum(u + 1, a.up_blocks, 3, lane);
-        const double sm = lp_run_sum(u + 2, a.up_blocks, 3, lane);
+        const double mm = wave_rows_sum(u, a.up_blocks, 3, lane), m = wave_rows_sum(u + 1, a.up_blocks, 3, lane);
+        const double sm = wave_rows_sum(u + 2, a.up_blocks, 3, lane);
         double total = 0.0;
         for (int l = 0; l < LP_LAYERS; ++l) {
             const double* p = dpart + ((size_t)b * a.rows_total + a.row_off[l]) * 2;
-            const double num = lp_run_sum(p, a.rows[l], 2, lane), den = lp_run_sum(p + 1, a.rows[l], 2, lane);
+            const double num = wave_rows_sum(p, a.rows[l], 2, lane), den = wave_rows_sum(p + 1, a.rows[l], 2, lane);
             const double v = num / (den + 1e-8);
             if (lane == 0) {
                 o[6 + l] = v;

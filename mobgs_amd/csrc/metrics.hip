@@ -19,7 +19,7 @@
 // squares, window sums, the SSIM formula: skimage itself widens to float64, and E[x^2] - mu^2 in fp32 is 1e-5 off on
 // smooth images (docs/MEASUREMENT_LOG.md).  This file is built with -ffp-contract=off: with both images equal, or flat,
 // numerator and denominator of the SSIM map are then the same operations on the same values and the map is exactly 1.
-#include "common.h"
+#include "reduce_shared.h"
 
 namespace mobgs {
 
@@ -54,20 +54,6 @@ __device__ __forceinline__ bool met_owns(int kind, int do_err, int c) {
 __device__ __forceinline__ int met_reflect(int i, int n) {
     i = i < 0 ? -i - 1 : (i >= n ? 2 * n - 1 - i : i);
     return i < 0 ? 0 : (i >= n ? n - 1 : i);
-}
-
-__device__ __forceinline__ float met_clamp01(float x) { return x < 0.f ? 0.f : (x > 1.f ? 1.f : x); }
-
-__device__ __forceinline__ double met_block_sum(double v, double* s_wave) {
-#pragma unroll
-    for (int off = MOBGS_WAVE / 2; off > 0; off >>= 1) v += __shfl_down(v, off, MOBGS_WAVE);
-    if ((threadIdx.x & (MOBGS_WAVE - 1)) == 0) s_wave[threadIdx.x / MOBGS_WAVE] = v;
-    __syncthreads();
-    double total = s_wave[0];
-#pragma unroll
-    for (int w = 1; w < MET_WAVES; ++w) total += s_wave[w];
-    __syncthreads();
-    return total;
 }
 
 template <int KIND>
@@ -114,10 +100,10 @@ __global__ void __launch_bounds__(MET_BLOCK) metrics_kernel(MetArgs a, double* _
                     u = pa[o];
                     v = pb[o];
                     if (a.clamp) {
-                        u = met_clamp01(u);
-                        v = met_clamp01(v);
+                        u = clamp01(u);
+                        v = clamp01(v);
                     }
-                    if (a.quantize) u = floorf(met_clamp01(u) * 255.f) / 255.f;
+                    if (a.quantize) u = quantize8(u);
                     if (c == 0) m = pm ? pm[o] : 1.f;
                 }
                 s_a[py][px] = u;
@@ -220,7 +206,7 @@ __global__ void __launch_bounds__(MET_BLOCK) metrics_kernel(MetArgs a, double* _
 #pragma unroll
     for (int c = 0; c < MET_NCOL; ++c) {
         if (!met_owns(KIND, a.do_err, c)) continue;      // (uniform)
-        const double total = met_block_sum(acc[c], s_wave);
+        const double total = block_sum<MET_WAVES>(acc[c], s_wave);
         if (threadIdx.x == 0) partial[row * MET_NCOL + c] = total;
     }
 }
@@ -230,9 +216,6 @@ __global__ void __launch_bounds__(MET_BLOCK) metrics_finish_kernel(int B, int H,
                                                                    const double* __restrict__ partial,
                                                                    double* __restrict__ out) {
     __shared__ double s_wave[MET_WAVES];
-    const int per = (rows + MET_BLOCK - 1) / MET_BLOCK;
-    const int r0 = threadIdx.x * per < rows ? threadIdx.x * per : rows;
-    const int r1 = r0 + per < rows ? r0 + per : rows;
     const double nan = __longlong_as_double(0x7ff8000000000000LL);
     for (int b = 0; b < B; ++b) {
         const double* p = partial + (size_t)b * rows * MET_NCOL;
@@ -241,10 +224,7 @@ __global__ void __launch_bounds__(MET_BLOCK) metrics_finish_kernel(int B, int H,
         for (int c = 0; c < MET_NCOL; ++c) {
             const bool have = c < MET_COL_BOX || (c < MET_COL_GAUSS ? (arms & MOBGS_METRICS_BOX) != 0
                                                                     : (arms & MOBGS_METRICS_GAUSS) != 0);
-            double s = 0.0;
-            if (have)
-                for (int r = r0; r < r1; ++r) s += p[(size_t)r * MET_NCOL + c];
-            S[c] = have ? met_block_sum(s, s_wave) : nan;
+            S[c] = have ? rows_sum<MET_BLOCK>(p + c, rows, MET_NCOL, s_wave) : nan;
         }
         if (threadIdx.x == 0) {
             double* o = out + (size_t)b * MOBGS_METRICS_COLUMNS;

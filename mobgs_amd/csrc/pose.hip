@@ -23,7 +23,7 @@
 // element by element (a branch that is uniform over the launch); the last, partial quad is read element by element in
 // either case.
 #include "adam_shared.h"
-#include "common.h"
+#include "reduce_shared.h"
 
 namespace mobgs {
 
@@ -157,25 +157,10 @@ __global__ void __launch_bounds__(MOBGS_WAVE) pose_step_kernel(PoseStep a) {
 }
 
 // ---- the loss -------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool pose_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 // the four elements of quad qd (all inside the array)
 __device__ __forceinline__ float4 pose_load_quad(const float* __restrict__ a, int64_t qd, bool vec) {
     const float* p = a + qd * 4;
     return vec ? *reinterpret_cast<const float4*>(p) : make_float4(p[0], p[1], p[2], p[3]);
-}
-
-// Sum over the workgroup in a fixed order: down the wave by shuffles, then the waves' values in wave order.  The total is
-// returned to thread 0 (other threads: unspecified).  Called by all threads.
-__device__ __forceinline__ double pose_block_sum(double v, double* s_wave) {
-#pragma unroll
-    for (int off = MOBGS_WAVE / 2; off > 0; off >>= 1) v += __shfl_down(v, off, MOBGS_WAVE);
-    if ((threadIdx.x & (MOBGS_WAVE - 1)) == 0) s_wave[threadIdx.x / MOBGS_WAVE] = v;
-    __syncthreads();
-    double total = s_wave[0];
-#pragma unroll
-    for (int w = 1; w < POSE_WAVES; ++w) total += s_wave[w];
-    return total;
 }
 
 __device__ __forceinline__ float pose_sq(float x, float y) {
@@ -189,7 +174,7 @@ neg_psnr_fwd_kernel(int64_t n, const float* __restrict__ pred, const float* __re
     const int64_t full = n / 4, run = pose_run(n);       // full: the quads that lie inside the array entirely
     const int64_t q0 = (int64_t)blockIdx.x * run;
     const int64_t q1 = q0 + run < pose_quads(n) ? q0 + run : pose_quads(n);
-    const bool pv = pose_aligned16(pred), gv = pose_aligned16(gt);
+    const bool pv = aligned16(pred), gv = aligned16(gt);
     double sum = 0.0;
     for (int64_t qd = q0 + threadIdx.x; qd < q1; qd += POSE_BLOCK) {
         if (qd < full) {
@@ -202,7 +187,7 @@ neg_psnr_fwd_kernel(int64_t n, const float* __restrict__ pred, const float* __re
             for (int64_t e = qd * 4; e < n; ++e) sum += (double)pose_sq(pred[e], gt[e]);
         }
     }
-    sum = pose_block_sum(sum, s_wave);
+    sum = block_sum<POSE_WAVES>(sum, s_wave);
     if (threadIdx.x == 0) partial[blockIdx.x] = sum;
 }
 
@@ -210,13 +195,7 @@ __global__ void __launch_bounds__(POSE_BLOCK)
 neg_psnr_finish_kernel(int64_t n, int nb, const double* __restrict__ partial, double* __restrict__ mse,
                        float* __restrict__ loss) {
     __shared__ double s_wave[POSE_WAVES];
-    // a fixed order that depends on nb alone: thread t adds its run of consecutive rows, pose_block_sum adds the runs
-    const int per = (nb + POSE_BLOCK - 1) / POSE_BLOCK;
-    const int r0 = threadIdx.x * per;
-    const int r1 = r0 + per < nb ? r0 + per : nb;
-    double s = 0.0;
-    for (int r = r0; r < r1; ++r) s += partial[r];
-    s = pose_block_sum(s, s_wave);
+    const double s = rows_sum<POSE_BLOCK>(partial, nb, 1, s_wave);
     if (threadIdx.x == 0) {
         // eval.py:137-139: -(20 log10(1 / sqrt(mse))), in float64 and rounded once (csrc/regterms.hip says why); mse == 0
         // gives -inf
@@ -234,7 +213,7 @@ neg_psnr_bwd_kernel(int64_t n, const float* __restrict__ pred, const float* __re
     const double up = v_loss ? (double)*v_loss : 1.0;
     const float c = (float)(up * 20.0 / (2.302585092994045684 * (double)n * *mse));
     const int64_t full = n / 4, quads = pose_quads(n);
-    const bool pv = pose_aligned16(pred), gv = pose_aligned16(gt), ov = pose_aligned16(v_pred);
+    const bool pv = aligned16(pred), gv = aligned16(gt), ov = aligned16(v_pred);
     const int64_t stride = (int64_t)gridDim.x * POSE_BLOCK;
     for (int64_t qd = (int64_t)blockIdx.x * POSE_BLOCK + threadIdx.x; qd < quads; qd += stride) {
         if (qd < full) {
@@ -255,8 +234,6 @@ neg_psnr_bwd_kernel(int64_t n, const float* __restrict__ pred, const float* __re
     }
 }
 
-static bool pose_misaligned(const void* p, uintptr_t mask) { return ((uintptr_t)p & mask) != 0; }
-
 }  // namespace mobgs
 
 using namespace mobgs;
@@ -264,7 +241,7 @@ using namespace mobgs;
 extern "C" {
 
 int mobgs_pose_head_fwd(const float* q, const float* t, float* w2c, void* stream) {
-    if (!q || !t || !w2c || pose_misaligned(q, 3) || pose_misaligned(t, 3) || pose_misaligned(w2c, 3)) {
+    if (!q || !t || !w2c || !aligned(q, 4) || !aligned(t, 4) || !aligned(w2c, 4)) {
         set_error("mobgs_pose_head_fwd: q, t and w2c must be given and 4-byte aligned");
         return MOBGS_E_INVALID;
     }
@@ -273,8 +250,7 @@ int mobgs_pose_head_fwd(const float* q, const float* t, float* w2c, void* stream
 }
 
 int mobgs_pose_head_bwd(const float* q, const float* v_w2c, float* v_q, float* v_t, void* stream) {
-    if (!q || !v_w2c || !v_q || !v_t || pose_misaligned(q, 3) || pose_misaligned(v_w2c, 3) || pose_misaligned(v_q, 3) ||
-        pose_misaligned(v_t, 3)) {
+    if (!q || !v_w2c || !v_q || !v_t || !aligned(q, 4) || !aligned(v_w2c, 4) || !aligned(v_q, 4) || !aligned(v_t, 4)) {
         set_error("mobgs_pose_head_bwd: q, v_w2c, v_q and v_t must be given and 4-byte aligned");
         return MOBGS_E_INVALID;
     }
@@ -287,7 +263,7 @@ int mobgs_pose_step(float* q, float* t, float* v_w2c, float* exp_avg, float* exp
                     void* stream) {
     float* const all[6] = {q, t, v_w2c, exp_avg, exp_avg_sq, w2c};
     for (float* p : all) {
-        if (!p || pose_misaligned(p, 3)) {
+        if (!p || !aligned(p, 4)) {
             set_error("mobgs_pose_step: q, t, v_w2c, exp_avg, exp_avg_sq and w2c must be given and 4-byte aligned");
             return MOBGS_E_INVALID;
         }
@@ -311,8 +287,7 @@ int mobgs_neg_psnr_fwd(int64_t n, const float* pred, const float* gt, double* pa
         set_error("mobgs_neg_psnr_fwd: NULL pred, gt, partial, mse or loss");
         return MOBGS_E_INVALID;
     }
-    if (pose_misaligned(pred, 3) || pose_misaligned(gt, 3) || pose_misaligned(loss, 3) || pose_misaligned(partial, 7) ||
-        pose_misaligned(mse, 7)) {
+    if (!aligned(pred, 4) || !aligned(gt, 4) || !aligned(loss, 4) || !aligned(partial, 8) || !aligned(mse, 8)) {
         set_error("mobgs_neg_psnr_fwd: pred, gt and loss must be 4-byte aligned, partial and mse 8-byte aligned");
         return MOBGS_E_INVALID;
     }
@@ -333,8 +308,7 @@ int mobgs_neg_psnr_bwd(int64_t n, const float* pred, const float* gt, const doub
         set_error("mobgs_neg_psnr_bwd: NULL pred, gt, mse or v_pred");
         return MOBGS_E_INVALID;
     }
-    if (pose_misaligned(pred, 3) || pose_misaligned(gt, 3) || pose_misaligned(v_loss, 3) || pose_misaligned(v_pred, 3) ||
-        pose_misaligned(mse, 7)) {
+    if (!aligned(pred, 4) || !aligned(gt, 4) || !aligned(v_loss, 4) || !aligned(v_pred, 4) || !aligned(mse, 8)) {
         set_error("mobgs_neg_psnr_bwd: pred, gt, v_loss and v_pred must be 4-byte aligned, mse 8-byte aligned");
         return MOBGS_E_INVALID;
     }

@@ -22,7 +22,7 @@
 // a body of float4 and a scalar tail; the head and the tail are two more "vectors" of the same grid-stride loop.  A
 // second array or an output whose own address is not 16-byte aligned at the body's start is accessed element by element
 // (a branch that is uniform over the launch).
-#include "common.h"
+#include "reduce_shared.h"
 
 namespace mobgs {
 
@@ -42,8 +42,6 @@ __host__ __device__ inline int reg_grid(int64_t n) {
     return (int)(g < 1 ? 1 : (g < REG_MAX_GRID ? g : REG_MAX_GRID));
 }
 
-__device__ __forceinline__ bool reg_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 // fn(x, y) for every element of a[0..n) (y = b[i], or 0 without b); with STORE its value goes to out[i].
 template <bool STORE, class Fn>
 __device__ __forceinline__ void reg_walk(int64_t n, const float* __restrict__ a, const float* __restrict__ b,
@@ -52,8 +50,8 @@ __device__ __forceinline__ void reg_walk(int64_t n, const float* __restrict__ a,
     const int64_t head = to_boundary < n ? to_boundary : n;
     const int64_t nvec = (n - head) / REG_VEC;
     const int64_t tail0 = head + nvec * REG_VEC;
-    const bool b_vec = b && reg_aligned16(b + head);
-    const bool o_vec = STORE && reg_aligned16(out + head);
+    const bool b_vec = b && aligned16(b + head);
+    const bool o_vec = STORE && aligned16(out + head);
     const int64_t stride = (int64_t)gridDim.x * REG_BLOCK;
     for (int64_t v = (int64_t)blockIdx.x * REG_BLOCK + threadIdx.x; v < nvec + 2; v += stride) {
         if (v < nvec) {
@@ -84,20 +82,6 @@ __device__ __forceinline__ void reg_walk(int64_t n, const float* __restrict__ a,
             }
         }
     }
-}
-
-// Sum over the workgroup in a fixed order: down the wave by shuffles, then the waves' values in wave order.
-// The total is returned to thread 0 (other threads: unspecified).  Called by all threads.
-__device__ __forceinline__ double reg_block_sum(double v, double* s_wave) {
-#pragma unroll
-    for (int off = MOBGS_WAVE / 2; off > 0; off >>= 1) v += __shfl_down(v, off, MOBGS_WAVE);
-    if ((threadIdx.x & (MOBGS_WAVE - 1)) == 0) s_wave[threadIdx.x / MOBGS_WAVE] = v;
-    __syncthreads();
-    double total = s_wave[0];
-#pragma unroll
-    for (int w = 1; w < REG_WAVES; ++w) total += s_wave[w];
-    __syncthreads();    // (s_wave is reused by the next call)
-    return total;
 }
 
 struct RegMaps {
@@ -131,9 +115,9 @@ __global__ void __launch_bounds__(REG_BLOCK) reg_fwd_kernel(RegMaps m, double* _
             return 0.f;
         });
     }
-    sd = reg_block_sum(sd, s_wave);
-    se = reg_block_sum(se, s_wave);
-    ss = reg_block_sum(ss, s_wave);
+    sd = block_sum<REG_WAVES>(sd, s_wave);
+    se = block_sum<REG_WAVES>(se, s_wave);
+    ss = block_sum<REG_WAVES>(ss, s_wave);
     if (threadIdx.x == 0) {
         row[0] = sd;
         row[1] = se;
@@ -147,20 +131,9 @@ __global__ void __launch_bounds__(REG_BLOCK) reg_fwd_kernel(RegMaps m, double* _
                             sq += (double)(d * d);
                             return 0.f;
                         });
-        sq = reg_block_sum(sq, s_wave);
+        sq = block_sum<REG_WAVES>(sq, s_wave);
         if (threadIdx.x == 0) row[REG_SUMS + b] = sq;
     }
-}
-
-// column c of the nb rows, added in index order: thread t adds its run of consecutive rows, reg_block_sum adds the runs
-__device__ __forceinline__ double reg_column_sum(const double* __restrict__ partial, int nb, int ncol, int c,
-                                                 double* s_wave) {
-    const int per = (nb + REG_BLOCK - 1) / REG_BLOCK;
-    const int r0 = threadIdx.x * per;
-    const int r1 = r0 + per < nb ? r0 + per : nb;
-    double s = 0.0;
-    for (int r = r0; r < r1; ++r) s += partial[(size_t)r * ncol + c];
-    return reg_block_sum(s, s_wave);
 }
 
 __global__ void __launch_bounds__(REG_BLOCK) reg_finish_kernel(RegMaps m, int nb, float w_d, float w_e, float w_s,
@@ -169,9 +142,9 @@ __global__ void __launch_bounds__(REG_BLOCK) reg_finish_kernel(RegMaps m, int nb
     __shared__ double s_wave[REG_WAVES];
     const int ncol = REG_SUMS + m.B;
     // (the three sums are meaningful in thread 0 only, which is the one that uses them)
-    const float S_d = (float)reg_column_sum(partial, nb, ncol, 0, s_wave);
-    const float S_e = (float)reg_column_sum(partial, nb, ncol, 1, s_wave);
-    const float S_s = (float)reg_column_sum(partial, nb, ncol, 2, s_wave);
+    const float S_d = (float)rows_sum<REG_BLOCK>(partial, nb, ncol, s_wave);
+    const float S_e = (float)rows_sum<REG_BLOCK>(partial + 1, nb, ncol, s_wave);
+    const float S_s = (float)rows_sum<REG_BLOCK>(partial + 2, nb, ncol, s_wave);
     if (threadIdx.x == 0) {
         // train.py:651-655: depth_loss = mean |.|; reg_loss = 0 + 0.2 depth_loss; mask_loss = 1e-7 E + 1e-7 S;
         // reg_loss += mask_loss
@@ -185,7 +158,7 @@ __global__ void __launch_bounds__(REG_BLOCK) reg_finish_kernel(RegMaps m, int nb
         out[4] = S_s;
     }
     for (int b = 0; b < m.B; ++b) {
-        const double S_b = reg_column_sum(partial, nb, ncol, REG_SUMS + b, s_wave);
+        const double S_b = rows_sum<REG_BLOCK>(partial + REG_SUMS + b, nb, ncol, s_wave);
         if (threadIdx.x == 0) {
             // utils/image_utils.py:30-31: 20 log10(1 / sqrt(mean((img1 - img2)^2))).  The one value formed in float64 and
             // rounded at the end: at 16 .. 32 dB the last place of an fp32 is 1.9e-6 dB and one ulp of an fp32 log10

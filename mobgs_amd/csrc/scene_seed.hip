@@ -24,7 +24,7 @@
 // The sampling rules are stated in two more places, which change with this file: the float64 composition for host
 // tensors (mobgs_amd/scene_init.py: _seed_maps_host and the host branch of track_trajectories) and the restatement the
 // tests compare against (tests/seed_restatement.py).
-#include "common.h"
+#include "reduce_shared.h"
 
 namespace mobgs {
 
@@ -34,17 +34,7 @@ constexpr int SEED_CHUNK = 1024;           // track start positions per LDS chun
 
 __host__ __device__ inline int seed_tiles(int H, int W) { return (H * W + SEED_BLOCK - 1) / SEED_BLOCK; }
 
-// sum over the workgroup in a fixed order: butterfly inside each wave, then the waves in index order (thread 0)
-__device__ __forceinline__ float seed_block_sum(float v, float* s_wave) {
-#pragma unroll
-    for (int off = MOBGS_WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, MOBGS_WAVE);
-    if ((threadIdx.x & (MOBGS_WAVE - 1)) == 0) s_wave[threadIdx.x / MOBGS_WAVE] = v;
-    __syncthreads();
-    float total = s_wave[0];
-#pragma unroll
-    for (int w = 1; w < SEED_WAVES; ++w) total += s_wave[w];
-    return total;   // (the same value in every lane)
-}
+static_assert(SEED_WAVES == 4, "block_sum4 adds four wave sums");
 
 __global__ void __launch_bounds__(SEED_BLOCK) seed_consistency_kernel(
     int V, int H, int W, const float* __restrict__ images, const float* __restrict__ depths,
@@ -103,7 +93,7 @@ __global__ void __launch_bounds__(SEED_BLOCK) seed_consistency_kernel(
         acc += contrib;
     }
     if (valid) accum_error[(size_t)i * HW + p] = acc;
-    const float total = seed_block_sum(valid ? acc : 0.f, s_wave);
+    const float total = block_sum4(valid ? acc : 0.f, s_wave);
     if (threadIdx.x == 0) partials[(size_t)i * gridDim.x + blockIdx.x] = total;
 }
 
@@ -119,7 +109,7 @@ __global__ void __launch_bounds__(SEED_BLOCK) seed_classify_kernel(
     // ---- the view's mean: lane t takes partials t, t + 256, ... in order, then the fixed-order workgroup sum ----------
     float part = 0.f;
     for (int k = threadIdx.x; k < tiles; k += SEED_BLOCK) part += partials[(size_t)i * tiles + k];
-    const float mean = seed_block_sum(part, s_wave) / (float)HW;
+    const float mean = block_sum4(part, s_wave) / (float)HW;
     if (blockIdx.x == 0 && threadIdx.x == 0) mean_out[i] = mean;
 
     const int p = blockIdx.x * SEED_BLOCK + threadIdx.x;

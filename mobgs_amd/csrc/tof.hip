@@ -28,7 +28,7 @@
 // sums and the 2x2 solve are float64 (OpenCV's are too).  Built with -ffp-contract=off.
 #include <math.h>
 
-#include "common.h"
+#include "reduce_shared.h"
 
 namespace mobgs {
 
@@ -50,7 +50,6 @@ __device__ __forceinline__ int tof_reflect101(int i, int n) {
     i = i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i);
     return tof_clampi(i, n);
 }
-__device__ __forceinline__ float tof_clamp01(float x) { return x < 0.f ? 0.f : (x > 1.f ? 1.f : x); }
 
 // INTER_LINEAR source position of destination index d: s = (d + 0.5) src / dst - 0.5, clamped to [0, src - 1]
 __device__ __forceinline__ void tof_resize_tap(int d, int src, int dst, int& i0, float& frac) {
@@ -70,8 +69,8 @@ __device__ __forceinline__ void tof_resize_tap(int d, int src, int dst, int& i0,
 
 // ---- grey ------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int tof_to_u8(float x, int clamp, int quantize) {
-    if (clamp) x = tof_clamp01(x);
-    if (quantize) x = floorf(tof_clamp01(x) * 255.f) / 255.f;
+    if (clamp) x = clamp01(x);
+    if (quantize) x = quantize8(x);
     const float t = truncf(x * 255.f);                              // (gt_img * 255.0).astype(np.uint8), saturated
     return t < 0.f ? 0 : (t > 255.f ? 255 : (int)t);
 }
@@ -376,18 +375,6 @@ static inline int tof_score_blocks(const TofCrop& c) {
     return (int)(((size_t)c.h * c.w + TOF_SCORE_PER_BLOCK - 1) / TOF_SCORE_PER_BLOCK);
 }
 
-__device__ __forceinline__ double tof_block_sum(double v, double* s_wave) {
-#pragma unroll
-    for (int off = MOBGS_WAVE / 2; off > 0; off >>= 1) v += __shfl_down(v, off, MOBGS_WAVE);
-    if ((threadIdx.x & (MOBGS_WAVE - 1)) == 0) s_wave[threadIdx.x / MOBGS_WAVE] = v;
-    __syncthreads();
-    double total = s_wave[0];
-#pragma unroll
-    for (int k = 1; k < TOF_WAVES; ++k) total += s_wave[k];
-    __syncthreads();
-    return total;
-}
-
 // partial [P, blocks, 2] = {sum |a - b|_2 mask, sum mask}
 __global__ void __launch_bounds__(TOF_BLOCK) tof_score_kernel(int H, int W, TofCrop c, const float* __restrict__ fa,
                                                               const float* __restrict__ fb, const float* __restrict__ mask,
@@ -406,8 +393,8 @@ __global__ void __launch_bounds__(TOF_BLOCK) tof_score_kernel(int H, int W, TofC
         sd += sqrt(du * du + dv * dv) * m;
         sm += m;
     }
-    sd = tof_block_sum(sd, s_wave);
-    sm = tof_block_sum(sm, s_wave);
+    sd = block_sum<TOF_WAVES>(sd, s_wave);
+    sm = block_sum<TOF_WAVES>(sm, s_wave);
     if (threadIdx.x == 0) {
         double* o = partial + ((size_t)p * gridDim.x + blockIdx.x) * 2;
         o[0] = sd;
@@ -419,18 +406,9 @@ __global__ void __launch_bounds__(TOF_BLOCK) tof_score_finish_kernel(int P, int 
                                                                      const double* __restrict__ partial,
                                                                      double* __restrict__ out) {
     __shared__ double s_wave[TOF_WAVES];
-    const int per = (blocks + TOF_BLOCK - 1) / TOF_BLOCK;
-    const int r0 = threadIdx.x * per < blocks ? threadIdx.x * per : blocks;
-    const int r1 = r0 + per < blocks ? r0 + per : blocks;
     for (int p = 0; p < P; ++p) {
         const double* q = partial + (size_t)p * blocks * 2;
-        double sd = 0.0, sm = 0.0;
-        for (int r = r0; r < r1; ++r) {
-            sd += q[2 * r];
-            sm += q[2 * r + 1];
-        }
-        sd = tof_block_sum(sd, s_wave);
-        sm = tof_block_sum(sm, s_wave);
+        const double sd = rows_sum<TOF_BLOCK>(q, blocks, 2, s_wave), sm = rows_sum<TOF_BLOCK>(q + 1, blocks, 2, s_wave);
         if (threadIdx.x == 0) out[p] = masked ? sd / sm : sd / n;
     }
 }
@@ -441,7 +419,6 @@ static bool tof_image_ok(int H, int W) {
 }
 static bool tof_level_ok(int h, int w) { return h >= 2 && w >= 2 && h <= TOF_MAX_EDGE && w <= TOF_MAX_EDGE; }
 static bool tof_count_ok(int n) { return n >= 1 && n <= TOF_MAX_F; }
-static bool tof_aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 static int tof_levels_host(int H, int W, MobgsTofLevel* out) {
     double scale = 1.0;
@@ -609,7 +586,7 @@ int mobgs_tof_grey(int F, int H, int W, const float* rgb, int flags, float* grey
                   H, W, TOF_MAX_F, TOF_MAX_EDGE, flags);
         return MOBGS_E_INVALID;
     }
-    if (!rgb || !grey || !tof_aligned(rgb, 4) || !tof_aligned(grey, 4)) {
+    if (!rgb || !grey || !aligned(rgb, 4) || !aligned(grey, 4)) {
         set_error("mobgs_tof_grey: NULL or misaligned rgb / grey");
         return MOBGS_E_INVALID;
     }
@@ -633,7 +610,7 @@ int mobgs_tof_pyramid_level(int F, int H, int W, const float* grey, const MobgsT
                   level->width, level->height, level->taps, level->sigma, W, H);
         return MOBGS_E_INVALID;
     }
-    if (!grey || !out || !tof_aligned(grey, 4) || !tof_aligned(out, 4)) {
+    if (!grey || !out || !aligned(grey, 4) || !aligned(out, 4)) {
         set_error("mobgs_tof_pyramid_level: NULL or misaligned grey / out");
         return MOBGS_E_INVALID;
     }
@@ -647,7 +624,7 @@ int mobgs_tof_polyexp(int F, int h, int w, const float* img, float* R, void* str
                   TOF_MAX_EDGE);
         return MOBGS_E_INVALID;
     }
-    if (!img || !R || !tof_aligned(img, 4) || !tof_aligned(R, 4)) {
+    if (!img || !R || !aligned(img, 4) || !aligned(R, 4)) {
         set_error("mobgs_tof_polyexp: NULL or misaligned img / R");
         return MOBGS_E_INVALID;
     }
@@ -666,7 +643,7 @@ int mobgs_tof_update_matrices(int P, int h, int w, const float* R, const float* 
         set_error("mobgs_tof_update_matrices: a flow of %d x %d cannot seed a level of %d x %d", src_w, src_h, w, h);
         return MOBGS_E_INVALID;
     }
-    if (!R || !M || !tof_aligned(R, 4) || !tof_aligned(M, 4) || !tof_aligned(flow, 4) || !tof_aligned(flow_out, 4)) {
+    if (!R || !M || !aligned(R, 4) || !aligned(M, 4) || !aligned(flow, 4) || !aligned(flow_out, 4)) {
         set_error("mobgs_tof_update_matrices: NULL R / M or a misaligned pointer");
         return MOBGS_E_INVALID;
     }
@@ -680,8 +657,8 @@ int mobgs_tof_blur_solve(int P, int h, int w, const float* M_in, float* flow, co
                   TOF_MAX_EDGE);
         return MOBGS_E_INVALID;
     }
-    if (!M_in || !flow || (M_out && !R) || M_out == M_in || !tof_aligned(M_in, 4) || !tof_aligned(flow, 4) ||
-        !tof_aligned(R, 4) || !tof_aligned(M_out, 4)) {
+    if (!M_in || !flow || (M_out && !R) || M_out == M_in || !aligned(M_in, 4) || !aligned(flow, 4) ||
+        !aligned(R, 4) || !aligned(M_out, 4)) {
         set_error("mobgs_tof_blur_solve: NULL M_in / flow, M_out without R or equal to M_in, or a misaligned pointer");
         return MOBGS_E_INVALID;
     }
@@ -695,7 +672,7 @@ int mobgs_tof_flow(int F, int H, int W, const float* grey, void* scratch, float*
                   TOF_MIN_EDGE, TOF_MAX_EDGE);
         return MOBGS_E_INVALID;
     }
-    if (!grey || !scratch || !flow_out || !tof_aligned(grey, 4) || !tof_aligned(scratch, 256) || !tof_aligned(flow_out, 4)) {
+    if (!grey || !scratch || !flow_out || !aligned(grey, 4) || !aligned(scratch, 256) || !aligned(flow_out, 4)) {
         set_error("mobgs_tof_flow: NULL grey / scratch / flow_out, or a misaligned pointer (scratch: 256 bytes)");
         return MOBGS_E_INVALID;
     }
@@ -734,8 +711,8 @@ int mobgs_tof_score(int P, int H, int W, const float* flow_a, const float* flow_
                   TOF_MIN_EDGE, TOF_MAX_EDGE);
         return MOBGS_E_INVALID;
     }
-    if (!flow_a || !flow_b || !partial || !out || !tof_aligned(flow_a, 4) || !tof_aligned(flow_b, 4) ||
-        !tof_aligned(mask, 4) || !tof_aligned(partial, 8) || !tof_aligned(out, 8)) {
+    if (!flow_a || !flow_b || !partial || !out || !aligned(flow_a, 4) || !aligned(flow_b, 4) ||
+        !aligned(mask, 4) || !aligned(partial, 8) || !aligned(out, 8)) {
         set_error("mobgs_tof_score: NULL flow_a / flow_b / partial / out, or a misaligned pointer (partial, out: 8 bytes)");
         return MOBGS_E_INVALID;
     }

@@ -193,8 +193,7 @@ def exposure_ratio(cam_flow, latent_flow, q=0.01, scale=1.0, out=None):
     for name, t in (("cam_flow", cam_flow), ("latent_flow", latent_flow)):
         if not torch.is_tensor(t) or t.dim() < 1 or t.shape[-1] != 2 or t.numel() == 0:
             raise ValueError(f"exposure_ratio: {name} must be a non-empty [...,2] tensor")
-        if not t.is_cuda:
-            raise RuntimeError("exposure_ratio: tensors must live on a HIP device (device='cuda'); there is no CPU path")
+        _lib.device_tensor("exposure_ratio", name, t)
     if cam_flow.numel() != latent_flow.numel() or cam_flow.device != latent_flow.device:
         raise ValueError("exposure_ratio: the two flow maps must have the same number of pixels and share a device")
     if not 0.0 <= float(q) <= 1.0:
@@ -271,9 +270,7 @@ class _RegTerms(torch.autograd.Function):
 def _reg_map(what, name, t):
     if not torch.is_tensor(t) or t.numel() == 0:
         raise ValueError(f"{what}: {name} must be a non-empty tensor")
-    if not t.is_cuda:
-        raise RuntimeError(f"{what}: tensors must live on a HIP device (device='cuda'); there is no CPU path")
-    return t
+    return _lib.device_tensor(what, name, t)
 
 
 def entropy_loss(alpha):

@@ -38,7 +38,7 @@ from typing import List, NamedTuple, Optional
 import torch
 
 from . import _lib
-from ._lib import check, f32c, ptr, stream
+from ._lib import check, device_tensor, f32c, ptr, stream
 
 CIN, COUT = (3, 64, 192, 384, 256), (64, 192, 384, 256, 256)
 KS, STRIDE, PAD = (11, 5, 3, 3, 3), (4, 1, 1, 1, 1), (2, 2, 1, 1, 1)
@@ -131,12 +131,12 @@ def check_state_dicts(trunk, heads):
     return ws, bs, ls
 
 
+def _flags(clamp, quantize) -> int:
+    return UNIT_RANGE | (CLAMP if clamp else 0) | (QUANTIZE if quantize else 0)
+
+
 def _pair(what, a, b):
-    for name, t in (("the first image", a), ("the second image", b)):
-        if not torch.is_tensor(t):
-            raise TypeError(f"{what}: {name} must be a tensor")
-        if not t.is_cuda:
-            raise RuntimeError(f"{what}: tensors must live on a HIP device (device='cuda'); there is no CPU path")
+    device_tensor(what, "the first image", a), device_tensor(what, "the second image", b)
     if a.dim() == 3:
         a = a[None]
     if b.dim() == 3:
@@ -154,10 +154,7 @@ def _mask(what, mask, like):
     [B,H,W] fp32 contiguous on the images' device."""
     if mask is None:
         return None
-    if not torch.is_tensor(mask):
-        raise TypeError(f"{what}: the mask must be a tensor")
-    if not mask.is_cuda:
-        raise RuntimeError(f"{what}: tensors must live on a HIP device (device='cuda'); there is no CPU path")
+    device_tensor(what, "the mask", mask)
     B, _, H, W = like.shape
     if mask.dim() == 4:
         mask = mask[:, 0]
@@ -264,8 +261,7 @@ class LpipsAlex:
         a pair has the same bits with and without want_map, whatever the batch and the chunking."""
         p, g = _pair("LpipsAlex.spatial", pred, gt)
         m = _mask("LpipsAlex.spatial", mask, p)
-        flags = UNIT_RANGE | (CLAMP if clamp else 0) | (QUANTIZE if quantize else 0)
-        out, fmap = self._run_spatial(g, p, m, flags, want_map)
+        out, fmap = self._run_spatial(g, p, m, _flags(clamp, quantize), want_map)
         return LpipsSpatial(fmap, out[:, 0], out[:, 1], out[:, 5], out[:, 6:11], out[:, 11:16], out[:, 16:21], out[:, 2],
                             out[:, 3], out[:, 4])
 
@@ -294,8 +290,7 @@ class LpipsAlex:
         """pred, gt [B,3,H,W] (or [3,H,W]) in [0, 1].  clamp: both are clamped to [0, 1] first; quantize: the prediction is
         then replaced by floor(clip(pred, 0, 1) * 255) / 255 (eval.py:162): the score of the written PNG."""
         p, g = _pair("LpipsAlex", pred, gt)
-        flags = UNIT_RANGE | (CLAMP if clamp else 0) | (QUANTIZE if quantize else 0)
-        out = self._run(g, p, flags)                      # the reference's order (metrics.py:130): ground truth first
+        out = self._run(g, p, _flags(clamp, quantize))    # the reference's order (metrics.py:130): ground truth first
         return LpipsResult(out[:, 0], out[:, 1:])
 
     @torch.no_grad()

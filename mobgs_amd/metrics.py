@@ -33,7 +33,7 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib
-from ._lib import check, f32c, ptr, stream
+from ._lib import check, device_tensor, f32c, ptr, stream
 
 ARMS = {"box": _lib._DEFINES["MOBGS_METRICS_BOX"], "gauss": _lib._DEFINES["MOBGS_METRICS_GAUSS"]}
 CLAMP, QUANTIZE = _lib._DEFINES["MOBGS_METRICS_CLAMP"], _lib._DEFINES["MOBGS_METRICS_QUANTIZE"]
@@ -54,12 +54,8 @@ class ImageMetrics(NamedTuple):
     mask_sum: torch.Tensor
 
 
-def _device_image(what, name, t):
-    if not torch.is_tensor(t):
-        raise TypeError(f"{what}: {name} must be a tensor")
-    if not t.is_cuda:
-        raise RuntimeError(f"{what}: tensors must live on a HIP device (device='cuda'); there is no CPU path")
-    return t
+def _flags(clamp, quantize) -> int:
+    return (CLAMP if clamp else 0) | (QUANTIZE if quantize else 0)
 
 
 @torch.no_grad()
@@ -73,7 +69,7 @@ def image_metrics(pred, gt, mask=None, *, data_range, clamp=False, quantize=Fals
     (ValueError otherwise).  Two or three launches on the current stream, no synchronisation, no allocation that depends on
     the data: the call can be recorded into a graph.  Bit-identical from run to run, and per image whatever the batch."""
     what = "image_metrics"
-    pred, gt = _device_image(what, "pred", pred), _device_image(what, "gt", gt)
+    pred, gt = device_tensor(what, "pred", pred), device_tensor(what, "gt", gt)
     if pred.dim() == 3:
         pred, gt = pred[None], gt[None] if gt.dim() == 3 else gt
     if pred.dim() != 4 or pred.shape[1] != 3 or pred.shape != gt.shape:
@@ -90,7 +86,7 @@ def image_metrics(pred, gt, mask=None, *, data_range, clamp=False, quantize=Fals
     if not (float(data_range) > 0.0 and math.isfinite(float(data_range))):
         raise ValueError(f"{what}: data_range must be positive and finite, got {data_range}")
     if mask is not None:
-        _device_image(what, "mask", mask)
+        device_tensor(what, "mask", mask)
         if mask.numel() != B * H * W or mask.shape[-2:] != (H, W):
             raise ValueError(f"{what}: mask must be [B,H,W] or [B,1,H,W], got {tuple(mask.shape)}")
         mask = f32c(mask.detach().reshape(B, H, W))
@@ -100,9 +96,8 @@ def image_metrics(pred, gt, mask=None, *, data_range, clamp=False, quantize=Fals
     partial = torch.empty(int(lib.mobgs_image_metrics_scratch_doubles(B, H, W)), dtype=torch.float64, device=dev)
     out = torch.empty(B, COLUMNS, dtype=torch.float64, device=dev)
     bits = sum({ARMS[a] for a in arms})
-    flags = (CLAMP if clamp else 0) | (QUANTIZE if quantize else 0)
     with torch.cuda.device(dev):
-        check(lib.mobgs_image_metrics(B, H, W, ptr(pred), ptr(gt), ptr(mask), bits, flags, float(data_range), ptr(partial),
+        check(lib.mobgs_image_metrics(B, H, W, ptr(pred), ptr(gt), ptr(mask), bits, _flags(clamp, quantize), float(data_range), ptr(partial),
                                       ptr(out), stream()), "mobgs_image_metrics")
     col = out.unbind(1)
     box, gauss = "box" in arms, "gauss" in arms
@@ -116,7 +111,7 @@ def _chw(what, name, img):
     """[H,W,3] array or tensor -> [1,3,H,W] device tensor (an array is uploaded; a host TENSOR is refused like everywhere)."""
     if not torch.is_tensor(img):
         img = torch.as_tensor(img).to("cuda")
-    _device_image(what, name, img)
+    device_tensor(what, name, img)
     if img.dim() != 3 or img.shape[-1] != 3:
         raise ValueError(f"{what}: {name} must be [H,W,3], got {tuple(img.shape)}")
     return img.permute(2, 0, 1)[None]
@@ -128,7 +123,7 @@ def _hw_mask(what, mask, like):
         return None
     if not torch.is_tensor(mask):
         mask = torch.as_tensor(mask).to(like.device)
-    _device_image(what, "mask", mask)
+    device_tensor(what, "mask", mask)
     if mask.dim() == 3:
         mask = mask[..., 0]
     if mask.shape != like.shape[-2:]:
@@ -223,7 +218,7 @@ TOF_SCRATCH_BUDGET = 1 << 30         # bytes of scratch per mobgs_tof_flow call;
 
 
 def _tof_frames(what, name, t, channels):
-    _device_image(what, name, t)
+    device_tensor(what, name, t)
     want = "[F,3,H,W]" if channels else "[F,H,W]"
     if t.dim() != (4 if channels else 3) or (channels and t.shape[1] != 3):
         raise ValueError(f"{what}: {name} must be {want}, got {tuple(t.shape)}")
@@ -258,9 +253,8 @@ def grey_frames(frames, *, clamp=False, quantize=False):
     frames = _tof_frames(what, "frames", frames, True)
     F_, _, H, W = frames.shape
     grey = torch.empty(F_, H, W, dtype=torch.float32, device=frames.device)
-    flags = (CLAMP if clamp else 0) | (QUANTIZE if quantize else 0)
     with torch.cuda.device(frames.device):
-        check(_lib.load().mobgs_tof_grey(F_, H, W, ptr(frames), flags, ptr(grey), stream()), "mobgs_tof_grey")
+        check(_lib.load().mobgs_tof_grey(F_, H, W, ptr(frames), _flags(clamp, quantize), ptr(grey), stream()), "mobgs_tof_grey")
     return grey
 
 
@@ -298,14 +292,14 @@ def flow_distance(flow_a, flow_b, mask=None):
     """Two flow stacks [P,H,W,2] (mask [P,H,W] of weights, or None) -> [P] float64 on the device: per pair the mean of
     |flow_a - flow_b|_2 over crop_8x8's window, or sum(. mask) / sum(mask) (metrics.py:18-29).  Two launches."""
     what = "flow_distance"
-    _device_image(what, "flow_a", flow_a), _device_image(what, "flow_b", flow_b)
+    device_tensor(what, "flow_a", flow_a), device_tensor(what, "flow_b", flow_b)
     if flow_a.dim() != 4 or flow_a.shape[-1] != 2 or flow_a.shape != flow_b.shape:
         raise ValueError(f"{what}: flows must both be [P,H,W,2], got {tuple(flow_a.shape)} and {tuple(flow_b.shape)}")
     P, H, W, _ = flow_a.shape
     if P < 1 or H < TOF_MIN_EDGE or W < TOF_MIN_EDGE:
         raise ValueError(f"{what}: needs P >= 1 and H, W >= {TOF_MIN_EDGE}, got {tuple(flow_a.shape)}")
     if mask is not None:
-        _device_image(what, "mask", mask)
+        device_tensor(what, "mask", mask)
         if mask.numel() != P * H * W or mask.shape[-2:] != (H, W):
             raise ValueError(f"{what}: mask must be [P,H,W] or [P,1,H,W], got {tuple(mask.shape)}")
         mask = f32c(mask.detach().reshape(P, H, W))
@@ -352,7 +346,7 @@ def temporal_of(pred, gt, mask=None, *, clamp=False, quantize=False):
                              f"{tuple(flows.shape)}")
         target = gt.flows
     else:
-        _device_image(what, "gt", gt)
+        device_tensor(what, "gt", gt)
         if gt.shape != pred.shape:
             raise ValueError(f"{what}: pred and gt must have one shape, got {tuple(pred.shape)} and {tuple(gt.shape)}")
         target = farneback_flow(grey_frames(gt.to(flows.device), clamp=clamp))
@@ -362,7 +356,7 @@ def temporal_of(pred, gt, mask=None, *, clamp=False, quantize=False):
 def _grey_hw(what, name, img):
     if not torch.is_tensor(img):
         img = torch.as_tensor(img).to("cuda")
-    _device_image(what, name, img)
+    device_tensor(what, name, img)
     if img.dim() != 2:
         raise ValueError(f"{what}: {name} must be a [H,W] grey image, got {tuple(img.shape)}")
     return img.float()

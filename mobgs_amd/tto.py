@@ -30,17 +30,9 @@ from typing import List, NamedTuple, Optional
 import torch
 
 from . import _lib
-from ._lib import check, f32c, ptr, stream
+from ._lib import check, device_tensor, f32c, ptr, stream
 
 BETAS, EPS = (0.9, 0.999), 1e-8          # torch.optim.Adam's defaults: eval.py:105-110 passes none
-
-
-def _device(what, name, t):
-    if not torch.is_tensor(t):
-        raise TypeError(f"{what}: {name} must be a tensor")
-    if not t.is_cuda:
-        raise RuntimeError(f"{what}: tensors must live on a HIP device (device='cuda'); there is no CPU path")
-    return t
 
 
 # ---- pytorch3d.transforms ---------------------------------------------------------------------------------------------
@@ -110,14 +102,14 @@ class _PoseMatrix(torch.autograd.Function):
 def pose_matrix(q: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
     """q [4] (real part first, not normalised), t [3] -> w2c [4,4] = [[quaternion_to_matrix(q), t], [0 0 0 1]]: eval.py:122-123
     in one launch, with the exact Jacobian in one more.  For callers who write their own loop."""
-    _device("pose_matrix", "q", q), _device("pose_matrix", "t", t)
+    device_tensor("pose_matrix", "q", q), device_tensor("pose_matrix", "t", t)
     if q.shape != (4,) or t.shape != (3,):
         raise ValueError(f"pose_matrix: q must be [4] and t [3], got {tuple(q.shape)} and {tuple(t.shape)}")
     return _PoseMatrix.apply(q, t)
 
 
 def _loss_pair(what, pred, gt):
-    _device(what, "pred", pred), _device(what, "gt", gt)
+    device_tensor(what, "pred", pred), device_tensor(what, "gt", gt)
     if pred.shape != gt.shape or pred.numel() == 0:
         raise ValueError(f"{what}: pred and gt must have one non-empty shape, got {tuple(pred.shape)} and {tuple(gt.shape)}")
 
@@ -196,7 +188,7 @@ def refine_pose(cam, gt, stat_pc, dyn_pc, pipe, bg, *, steps, decay_start, lr_p,
     render() itself does."""
     from .gaussian_renderer import render
     what = "refine_pose"
-    gt = f32c(_device(what, "gt", gt).detach())
+    gt = f32c(device_tensor(what, "gt", gt).detach())
     H, W = int(cam.image_height), int(cam.image_width)
     if gt.shape != (3, H, W):
         raise ValueError(f"{what}: gt must be [3,{H},{W}] like the camera's image, got {tuple(gt.shape)}")
@@ -295,7 +287,7 @@ def render_test_tto(H, W, scene, test_cams, save_dir, gt_images, tto_steps=25, d
         boosted = bool(initialize_from_previous_camera) and k == 0          # the long first pass at the full rate
         step_factor = initialize_from_previous_step_factor if boosted else 1
         lr_factor = 1.0 if boosted else initialize_from_previous_lr_factor
-        gt = _device(what, "gt_images", gt).to(device).float()
+        gt = device_tensor(what, "gt_images", gt).to(device).float()
         if gt.shape != (3, H, W):
             raise ValueError(f"{what}: ground truth {k} must be [3,{H},{W}], got {tuple(gt.shape)}")
         solved = refine_pose(cam, gt, stat_pc, dyn_pc, pipe, bg, steps=tto_steps * step_factor, decay_start=decay_start,

@@ -75,6 +75,27 @@ def load(name):
     return load_npz(os.path.join(GOLDEN, name + ".npz"))
 
 
+_BIT_VIEWS = {torch.float16: torch.int16, torch.bfloat16: torch.int16, torch.float32: torch.int32,
+              torch.float64: torch.int64}
+
+
+def _host(t):
+    return torch.as_tensor(t.copy() if isinstance(t, np.ndarray) else t).detach().cpu().contiguous()
+
+
+def bits(t):
+    """The raw bit pattern of a tensor or array (any device, any layout): a host integer tensor of its shape.  A floating
+    dtype is viewed as the integer of its width; an integer or bool input is its own bit pattern."""
+    t = _host(t)
+    return t.view(_BIT_VIEWS[t.dtype]) if t.dtype.is_floating_point else t
+
+
+def same_bits(a, b):
+    """Equal in shape, dtype and every bit (so +0 and -0 differ, and a NaN equals the NaN of the same pattern)."""
+    a, b = _host(a), _host(b)
+    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(bits(a), bits(b))
+
+
 def scene_from_fixture(fx, device="cpu", requires_grad=True):
     """-> cam, stat_pc, dyn_pc, bg, w2c (all on `device`)."""
     T = torch.from_numpy

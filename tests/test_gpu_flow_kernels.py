@@ -36,6 +36,7 @@ import pytest
 import torch
 
 import flow_cases as C
+from helpers import same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -62,10 +63,6 @@ def _run(c, dev, combine=True, v=None, inputs=None):
     out = {k: t[k].grad.detach().cpu() for k in C.NAMES}
     out["loss"] = loss.detach().cpu()
     return out
-
-
-def _same_bits(a, b):
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
 
 
 def _report(name, build, needs):
@@ -98,7 +95,7 @@ def test_flow_warp_loss_matches_float64(hip_device, name):
             _report(name, build, sink)
         plain[combine] = got
     for k in C.PLAIN + ("loss",):  # one value per element, no atomics: the same bits with and without merged taps
-        assert _same_bits(plain[True][k], plain[False][k]), k
+        assert same_bits(plain[True][k], plain[False][k]), k
 
 
 def test_build_query():
@@ -123,7 +120,7 @@ def test_plain_stores_are_bit_reproducible_and_atomic_sums_stay_in_bound(hip_dev
     for run in ("second", "third"):
         again = _run(c, hip_device, True)
         for k in C.PLAIN + ("loss",):
-            assert _same_bits(first[k], again[k]), (run, k)
+            assert same_bits(first[k], again[k]), (run, k)
         C.compare(name, rows, again, f"{name} {run} run", keys=C.SCATTER, loss=False)  # atomic sums: the bound, each time
 
 
@@ -164,13 +161,13 @@ def test_gradient_subsets_at_the_c_abi(hip_device, name):
     C.compare(name, rows, full, f"{name} C ABI, all six")
     for key in C.NAMES:
         rc, one = _abi_call(c, hip_device, (key,), scratch=key in C.SCATTER)
-        assert rc == 0 and _same_bits(one["loss"], full["loss"]), key
+        assert rc == 0 and same_bits(one["loss"], full["loss"]), key
         if key in C.SCATTER:
             C.compare(name, rows, one, f"{name} C ABI, g_{key} alone", keys=(key,), loss=False)
         else:
-            assert _same_bits(one[key], full[key]), key
+            assert same_bits(one[key], full[key]), key
     rc, four = _abi_call(c, hip_device, C.PLAIN, scratch=False)
-    assert rc == 0 and all(_same_bits(four[k], full[k]) for k in C.PLAIN)
+    assert rc == 0 and all(same_bits(four[k], full[k]) for k in C.PLAIN)
 
 
 def test_image_gradient_without_scratch_is_refused(hip_device):
@@ -189,9 +186,9 @@ def test_gradients_are_linear_in_the_cotangent(hip_device, name):
     """v and 2 v: a power of two, so the plain-store gradients double exactly; the loss does not move."""
     c = C.case(name)
     one, two = _run(c, hip_device, True, v=c.v), _run(c, hip_device, True, v=2 * c.v)
-    assert _same_bits(one["loss"], two["loss"])
+    assert same_bits(one["loss"], two["loss"])
     for k in C.PLAIN:
-        assert one[k].abs().max() > 0 and _same_bits(2 * one[k], two[k]), k
+        assert one[k].abs().max() > 0 and same_bits(2 * one[k], two[k]), k
     rows = _build(c, True)
     half = {k: 0.5 * two[k] for k in C.SCATTER}  # exact halves: the atomic sums of 2 v, held to the bound of v
     C.compare(name, rows, half, f"{name} at 2 v, halved", keys=C.SCATTER, loss=False)
@@ -216,7 +213,7 @@ def test_other_layouts_and_alignments(hip_device):
     for shifts in ((1, 1, 1, 1, 1, 1), (3, 2, 1, 3, 2, 1), (0, 1, 3, 2, 0, 3)):
         got = _run(c, dev, True, inputs={k: shifted(c.inputs[k], s) for k, s in zip(C.NAMES, shifts)})
         for k in C.PLAIN + ("loss",):
-            assert _same_bits(got[k], plain[k]), (shifts, k)
+            assert same_bits(got[k], plain[k]), (shifts, k)
         C.compare(c.name, rows, got, f"smooth_a shifted by {shifts}", keys=C.SCATTER, loss=False)
     # channel / component slices of wider tensors, and a permuted coordinate map
     wide = {"ori": torch.rand(c.B, 5, c.H, c.W), "latent": torch.rand(c.B, c.K, 4, c.H, c.W),
@@ -238,6 +235,6 @@ def test_other_layouts_and_alignments(hip_device):
     got["m2e"] = m2e.grad.permute(0, 1, 3, 4, 2).cpu()
     got["loss"] = loss.detach().cpu()
     for k in C.PLAIN + ("loss",):
-        assert _same_bits(got[k], plain[k]), k
+        assert same_bits(got[k], plain[k]), k
     C.compare(c.name, rows, got, "smooth_a as views", keys=C.SCATTER, loss=False)
     assert float(wide["ori"].grad[:, 0].abs().max()) == 0.0 and float(wide["e2m"].grad[..., 0].abs().max()) == 0.0

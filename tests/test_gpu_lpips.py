@@ -11,7 +11,7 @@ import pytest
 import torch
 
 import lpips_restatement as LR
-from helpers import load
+from helpers import load, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -54,12 +54,6 @@ def table(r):
     assert r.total.dtype == r.per_layer.dtype == torch.float64 and r.total.is_cuda and r.per_layer.is_cuda
     assert r.total.shape == (B,) and r.per_layer.shape == (B, 5)
     return torch.cat([r.total[:, None], r.per_layer], 1).cpu().numpy()
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    view = np.int64 if a.dtype == np.float64 else np.int32
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(view), b.view(view))
 
 
 @pytest.mark.parametrize("i", range(len(LR.CASES)))

@@ -14,8 +14,8 @@ import torch
 
 import lpips_restatement as LR
 import lpips_spatial_restatement as LS
-from helpers import load
-from test_gpu_lpips import same_bits, synthetic  # noqa: F401  (the synthetic scene is built afresh by this module)
+from helpers import load, same_bits
+from test_gpu_lpips import synthetic  # noqa: F401  (the synthetic scene is built afresh by this module)
 
 pytestmark = pytest.mark.gpu
 ROW = ("mean", "masked_mean", "masked_total", "masked_per_layer", "numerators", "denominators", "map_mask_sum", "mask_sum",

@@ -11,7 +11,7 @@ import pytest
 import torch
 
 import metrics_restatement as MR
-from helpers import GOLDEN, load
+from helpers import GOLDEN, load, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -45,11 +45,6 @@ def table(m):
     cols = [getattr(m, k) for k in MR.METRICS]
     assert all(t is None or (t.dtype == torch.float64 and t.shape == (B,) and t.is_cuda) for t in cols)
     return torch.stack([torch.full((B,), math.nan, dtype=torch.float64) if t is None else t.cpu() for t in cols], 1).numpy()
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype == np.float64 and np.array_equal(a.view(np.int64), b.view(np.int64))
 
 
 @pytest.mark.parametrize("i", range(len(MR.CASES)))

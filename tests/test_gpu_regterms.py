@@ -6,7 +6,7 @@ import pytest
 import torch
 
 import regterms_restatement as RR
-from helpers import load
+from helpers import load, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -14,14 +14,6 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(scope="module")
 def fx():
     return load("regterms")
-
-
-def bits(t):
-    return t.detach().cpu().contiguous().view(torch.int32)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(bits(a), bits(b))
 
 
 def run(c, dev, images=True, need=(True, True), cotangent=None):

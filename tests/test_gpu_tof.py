@@ -18,6 +18,7 @@ import pytest
 import torch
 
 import tof_restatement as TR
+from helpers import same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -43,13 +44,6 @@ def rel_err(got, want):
     got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
     assert got.shape == want.shape, (got.shape, want.shape)
     return float(np.abs(got - want).max() / np.abs(want).max())
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(a.view(torch.int32) if a.dtype == torch.float32
-                                                                      else a.view(torch.int64),
-                                                                      b.view(torch.int32) if b.dtype == torch.float32
-                                                                      else b.view(torch.int64))
 
 
 @pytest.fixture(scope="module")

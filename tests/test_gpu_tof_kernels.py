@@ -13,7 +13,8 @@ import torch
 
 import tof_cases as TC
 import tof_restatement as TR
-from test_gpu_tof import allowed, call, level_record, rel_err, same_bits
+from helpers import same_bits
+from test_gpu_tof import allowed, call, level_record, rel_err
 
 pytestmark = pytest.mark.gpu
 

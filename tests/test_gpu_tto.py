@@ -14,17 +14,10 @@ import pytest
 import torch
 
 import tto_restatement as TR
+from helpers import bits, same_bits
 
 pytestmark = pytest.mark.gpu
 F64 = torch.float64
-
-
-def bits(t):
-    return t.detach().cpu().contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int64)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(bits(a), bits(b))
 
 
 # ---- the head ----------------------------------------------------------------------------------------------------------

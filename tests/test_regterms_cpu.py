@@ -8,7 +8,7 @@ import pytest
 import torch
 
 import regterms_restatement as RR
-from helpers import load
+from helpers import load, same_bits
 
 GRADS = ("g_depth", "g_alpha", "g_entropy", "g_sparsity")
 
@@ -16,10 +16,6 @@ GRADS = ("g_depth", "g_alpha", "g_entropy", "g_sparsity")
 @pytest.fixture(scope="module")
 def fx():
     return load("regterms")
-
-
-def bits(t):
-    return torch.as_tensor(t).contiguous().view(torch.int32)
 
 
 LOG_FREE = ("depth_loss", "sparsity", "g_depth", "g_sparsity")     # +, -, *, /, abs, sign: the same bits on every CPU
@@ -31,7 +27,7 @@ def same_log_as_the_generator(fx):
     gave for the 3922 arguments of case 1: where this machine gives the same, it evaluates the reference's statements
     as the generator did."""
     c, _ = RR.fixture_case(fx, 1)
-    return torch.equal(bits(torch.log(c["alpha"].reshape(-1) + RR.EPS)), bits(fx["log_probe"]))
+    return same_bits(torch.log(c["alpha"].reshape(-1) + RR.EPS), fx["log_probe"])
 
 
 @pytest.mark.parametrize("i", range(len(RR.CASES)))
@@ -50,7 +46,7 @@ def test_fp32_restatement_reproduces_the_reference(fx, i):
         ref = torch.from_numpy(want["ref_" + k])
         mine = got[k].reshape(ref.shape)
         if same_log or k in LOG_FREE:
-            assert torch.equal(bits(mine), bits(ref)), k
+            assert same_bits(mine, ref), k
         elif k == "psnr":
             assert RR.db_gap(mine, ref) <= RR.FLOOR_DB, k
         else:
