@@ -178,6 +178,23 @@ class DeblurTrainer:
                                       time=i / (n - 1.0), world_view_transform=view_pose(i).transpose(0, 1).contiguous())
                 for i in range(n)]
 
+    def report(self, report_dir, iteration, seconds):
+        """train.py:776-790 for the training views: the report sheets of mobgs_amd.scene_utils.render_training_image
+        (image, decomp, nine flow colours and nine latent frames per view) under <report_dir>/fine_render/train/images.
+        Between two iterations and outside any capture.  -> the paths of the image sheets."""
+        import types
+
+        from mobgs_amd.scene_utils import render_training_image
+        for v, c in enumerate(self.cams):   # what the reference reads from a training view
+            c.image_name, c.original_image = f"view{v:02d}", self.targets[v]
+            c.normal, c.depth = self.normals[v][0], self.depths[v]
+            c.metadata = types.SimpleNamespace(focal_length=self.meta.scale_factor_x, skew=self.meta.skew,
+                                               principal_point_x=self.meta.principal_point_x,
+                                               principal_point_y=self.meta.principal_point_y)
+        return render_training_image(types.SimpleNamespace(model_path=report_dir), self.stat, self.dyn, self.cams, render,
+                                     None, self.bg, "fine", iteration, seconds, "synthetic", is_train=True,
+                                     blcekernel=self.blce)
+
     def estimate_exposure(self):
         """train.py:474-492 for every view of the batch: exposure_time_expo[uid] from the static flow between the view's
         neighbours and the static flow over its own exposure, halved for the first and the last view (:490).  Device
@@ -381,7 +398,8 @@ class DeblurTrainer:
 
 
 def train(dev="cuda:0", iters=40, ns=4000, nd=2000, width=256, height=192, n_views=2, seed=0, lambda_flow=1e-2,
-          shard=None, log=None, graph=False, prune_control_every=0, from_views=False, estimate_exposure=0):
+          shard=None, log=None, graph=False, prune_control_every=0, from_views=False, estimate_exposure=0,
+          report_dir=None, report_every=0):
     """graph=True (single process): forward + losses + backward of the iteration recorded ONCE as a HIP graph
     (mobgs_amd.graphed.GraphedCallable) and replayed, the Adam step outside -- for small images / few Gaussians, where an
     iteration is ~1400 launches and bound by the host (the reference's own 512x288 / 30 k operating point: 9.5 -> 7.5 ms).
@@ -393,7 +411,12 @@ def train(dev="cuda:0", iters=40, ns=4000, nd=2000, width=256, height=192, n_vie
     instead of being sampled directly.
     estimate_exposure=N > 0: before every N-th iteration each view's exposure_time_expo entry is re-estimated from rendered
     static flow (DeblurTrainer.estimate_exposure; train.py:474-492 does it every 10th).  In place and on the device, so a
-    recorded iteration reads the new values."""
+    recorded iteration reads the new values.
+    report_dir, report_every=K > 0: after every K-th iteration (and after the last) rank 0 writes the report sheets of the
+    training views (DeblurTrainer.report: mobgs_amd.scene_utils.render_training_image, as train.py:776-790 does on its
+    testing iterations)."""
+    import time
+    started = time.time()
     t = DeblurTrainer(dev, ns, nd, width, height, n_views, seed, lambda_flow, shard, iters, from_views)
     history = []
     prune_views = t.prune_viewpoints() if prune_control_every else None
@@ -426,6 +449,9 @@ def train(dev="cuda:0", iters=40, ns=4000, nd=2000, width=256, height=192, n_vie
             pruned = t.dyn.onedown_control_pts(prune_views)
             if t.shard.rank == 0:
                 print(f"it {it:4d}  one control point down on {int(pruned)} rows  MinCtrl {int(t.dyn.current_control_num.min())}")
+        if report_dir and report_every and (it % report_every == 0 or it == iters) and t.shard.rank == 0:
+            sheets = t.report(report_dir, it, time.time() - started)
+            print(f"it {it:4d}  report sheets of {len(sheets)} views under {os.path.dirname(sheets[0])}")
         if it == 2:   # everything long-lived exists now: keep Python's cyclic collector off it (66 ms per generation-2
             import gc  # pass over a torch process's objects on this host, in the middle of an iteration: DESIGN section 5)
             gc.collect()
@@ -449,6 +475,10 @@ if __name__ == "__main__":
                     help="build both sets through scene_initialization from synthetic views instead of sampling them")
     ap.add_argument("--estimate-exposure", type=int, default=0, metavar="N",
                     help="every N iterations re-estimate each view's exposure time from rendered static flow (0 = never)")
+    ap.add_argument("--report-dir", default=None, metavar="DIR",
+                    help="write the report sheets of the training views (render_training_image) under DIR")
+    ap.add_argument("--report-every", type=int, default=0, metavar="K",
+                    help="with --report-dir: after every K-th iteration and after the last (0 = never)")
     a = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -457,4 +487,5 @@ if __name__ == "__main__":
         torch.cuda.set_device(local)
         dist.init_process_group("nccl", device_id=torch.device("cuda", local))
     train(dev=f"cuda:{local}", iters=a.iters, ns=a.ns, nd=a.nd, width=a.width, height=a.height, log=10, graph=a.graph,
-          prune_control_every=a.prune_control_every, from_views=a.from_views, estimate_exposure=a.estimate_exposure)
+          prune_control_every=a.prune_control_every, from_views=a.from_views, estimate_exposure=a.estimate_exposure,
+          report_dir=a.report_dir, report_every=a.report_every)

@@ -1175,6 +1175,76 @@ int mobgs_tof_flow(int F, int H, int W, const float* grey, void* scratch, float*
 int mobgs_tof_score(int P, int H, int W, const float* flow_a, const float* flow_b, const float* mask, double* partial,
                     double* out, void* stream);
 
+/* ---- K26: report sheets: the panels of render_training_image composed as 8-bit images on the device -----------------
+ * What the reference's utils/scene_utils.py:15-260 builds on the host, one .cpu().numpy() round trip per panel: here a
+ * sheet is laid out as uint8 on the device and copied once (csrc/report.hip, built with -ffp-contract=off).  Entry points
+ * only: MOBGS_ABI_VERSION stays as it is.  Two launches per sheet on the caller's stream; neither synchronises,
+ * allocates or reads back, so both can be recorded into a graph.  Every input is fp32, only read, finite (NaN handling is
+ * not defined), 4-byte aligned (flow maps, [H,W,2]: 8).  The records are HOST arrays; their pointers are device pointers.
+ *
+ * mobgs_report_stats: for map m of stats_host, stats[2 m] = its minimum and stats[2 m + 1] = its maximum, bit-equal to
+ *   torch.amin / torch.amax of the same fp32 expression (min and max do not depend on an order; integer atomics on the
+ *   ordered bit patterns).  kind MINMAX: the n values of a.  SQERR: (a[i] - b[i])^2, the difference and the square each
+ *   rounded to fp32; the error map is not stored.  FLOW_RAD: a is [n,2]; sqrt(u u + v v) with every operation rounded as
+ *   numpy's float32 statements round it (no fused multiply-add, the correctly rounded root), after clipping u and v to
+ *   [0, clip] if clip >= 0 (flow_vis' clip_flow); the maximum is flow_to_color's rad_max.
+ *   stats: mobgs_report_stats_floats(n_stats) floats (a host computation; 0 for a count outside 1 .. MAX_STATS): the
+ *   2 n_stats results, then words the call zeroes and merges into.  1 memset + 1 launch.
+ * mobgs_report_compose: sheet (uint8, fully written) = the n_panels panels side by side, [H, n_panels W, 3] (row-major,
+ *   channel-last, as PIL.Image.fromarray takes it), or with vertical != 0 one below the other, [n_panels H, W, 3], so that
+ *   every panel is a contiguous [H,W,3] image.  Every panel ends in (np.clip(x, 0, 1) * 255).astype('uint8'), i.e.
+ *   floor(clamp01(x) 255).  kind:
+ *     RGB           a [3,H,W]
+ *     GREY          a [1,H,W], repeated over the three channels
+ *     GREY_DIV_MAX  a [1,H,W] / max, max = stats[2 slot + 1] (scene_utils.py:177-179); 0 where max is 0 (the reference
+ *                   divides by zero there)
+ *     ERROR         (e - min) / max(max - min, 1e-8), e = (a - b)^2 per channel, a and b [3,H,W], (min, max) = the slot's
+ *                   pair (scene_utils.py:187-188)
+ *     SIGNED3       (a + 1) / 2, a [3,H,W]
+ *     NORMALS_FD    a = depth [1,H,W]; scene_utils.py:130-163, :185: z = depth + 1e-6; directions ((px - cx - y skew) /
+ *                   focal, y = (py - cy) / focal, 1), px = column + pixel_offset; forward differences along the row and
+ *                   the column, the last column / row repeating its neighbour's; the cross product as written,
+ *                   F.normalize (eps 1e-12), (n + 1) / 2.  Needs H, W >= 2.  (Not main_utils.get_normals: K15.)
+ *     FLOW          a [H,W,2]; flow_vis.flow_to_color (convert_to_bgr = False): with rad_max = stats[2 slot + 1],
+ *                   u, v (clipped to [0, clip] if clip >= 0) divided by rad_max + 1e-5; rad = sqrt(u u + v v);
+ *                   a = atan2f(-v, -u) / pi_f; fk = (a + 1) / 2 * 54; k0 = floor(fk), k1 = k0 + 1 (55 -> 0), f = fk - k0;
+ *                   per channel col = (1 - f) wheel[k0] / 255 + f wheel[k1] / 255, then 1 - rad (1 - col).  The wheel: 55
+ *                   entries, segments RY 15, YG 6, GC 4, CB 11, BM 13, MR 6.  flow_vis could not be run where this was
+ *                   written: a restatement (README, "UNPINNED"; tests/report_restatement.py is the same text in float64).
+ *   A sheet has at most 2^30 pixels.  1 launch; a lane stores 12 bytes as three aligned dwords.
+ * Refused with MOBGS_E_INVALID before any launch, under the entry point's name: a count or size outside its range, an
+ *   unknown kind, a NULL or misaligned pointer (b and stats may be NULL where no panel reads them), a statistics slot
+ *   outside 0 .. n_stats - 1, a NORMALS_FD panel with H < 2, W < 2 or focal == 0. */
+#define MOBGS_REPORT_RGB 0
+#define MOBGS_REPORT_GREY 1
+#define MOBGS_REPORT_GREY_DIV_MAX 2
+#define MOBGS_REPORT_ERROR 3
+#define MOBGS_REPORT_SIGNED3 4
+#define MOBGS_REPORT_NORMALS_FD 5
+#define MOBGS_REPORT_FLOW 6
+#define MOBGS_REPORT_MAX_PANELS 16
+#define MOBGS_REPORT_STAT_MINMAX 0
+#define MOBGS_REPORT_STAT_SQERR 1
+#define MOBGS_REPORT_STAT_FLOW_RAD 2
+#define MOBGS_REPORT_MAX_STATS 32
+#define MOBGS_REPORT_WHEEL 55
+typedef struct MobgsReportStat {
+    int32_t kind;
+    int64_t n;
+    const float *a, *b;
+    float clip;
+} MobgsReportStat;
+typedef struct MobgsReportPanel {
+    int32_t kind, slot;
+    const float *a, *b;
+    float clip;
+} MobgsReportPanel;
+size_t mobgs_report_stats_floats(int n_stats);
+int mobgs_report_stats(int n_stats, const MobgsReportStat* stats_host, float* stats, void* stream);
+int mobgs_report_compose(int H, int W, int n_panels, const MobgsReportPanel* panels_host, const float* stats,
+                         int n_stats, float focal, float cx, float cy, float skew, float pixel_offset, int vertical,
+                         uint8_t* sheet, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

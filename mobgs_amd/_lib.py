@@ -151,6 +151,16 @@ class MobgsTofLevel(ctypes.Structure):
     _fields_ = _STRUCTS["MobgsTofLevel"]
 
 
+class MobgsReportStat(ctypes.Structure):
+    """include/mobgs_hip.h MobgsReportStat: one map of mobgs_report_stats (kind, element count, device pointers, clip)."""
+    _fields_ = _STRUCTS["MobgsReportStat"]
+
+
+class MobgsReportPanel(ctypes.Structure):
+    """include/mobgs_hip.h MobgsReportPanel: one panel of a report sheet (kind, statistics slot, device pointers, clip)."""
+    _fields_ = _STRUCTS["MobgsReportPanel"]
+
+
 def _bind(lib, name, restype, argtypes):
     fn = getattr(lib, name)
     fn.restype = restype
