@@ -37,11 +37,17 @@ from mobgs_amd.gaussian_renderer import render  # noqa: E402
 from mobgs_amd.helper_model import Sandwich  # noqa: E402
 from mobgs_amd.loss_utils import flow_warp_loss, l1_loss, photometric_loss  # noqa: E402
 from mobgs_amd.ops import LeafGradSink  # noqa: E402
-from mobgs_amd.optim import fused_adam_step  # noqa: E402
+from mobgs_amd.optim import DeviceAdam, MultiplicativeLR, fused_adam_step  # noqa: E402
 from mobgs_amd.synth import SynthCamera, dynamic_extras, gaussian_cloud  # noqa: E402
 from train_synth import Opt  # noqa: E402  (examples/ is on sys.path when run as a script or from the test)
 
 K = 9
+
+
+class ScheduledOpt(Opt):
+    """Opt with the values the reference's xyz schedule is built from (arguments/__init__.py:121-123)."""
+    position_lr_final = 0.0000016
+    position_lr_max_steps = 20_000
 
 
 def view_pose(i):
@@ -115,7 +121,7 @@ class DeblurTrainer:
     Adam on both Gaussian sets (incl. the decoder) and the BLCE parameters.  bench.py times it at full size."""
 
     def __init__(self, dev="cuda:0", ns=4000, nd=2000, width=256, height=192, n_views=2, seed=0, lambda_flow=1e-2,
-                 shard=None, iters=40, from_views=False):
+                 shard=None, iters=40, from_views=False, lr_schedule=False):
         from mobgs_amd.main_utils import get_normals
         self.get_normals = get_normals
         self.shard = shard = shard or SubframeShard()
@@ -156,9 +162,13 @@ class DeblurTrainer:
         self.gt = torch.stack(self.targets)
         torch.manual_seed(seed + 1)
         self.blce = blceKernel(num_views=n_views, num_warp=K, iteration=max(iters, 1)).to(dev)
-        self.opt = opt = Opt()
+        self.opt = opt = ScheduledOpt() if lr_schedule else Opt()
         stat.training_setup(opt)
         dyn.training_setup(opt)
+        self.lr_schedule = bool(lr_schedule)
+        if lr_schedule:   # gaussian_model.py:646-661: the schedules update_learning_rate() evaluates
+            stat.setup_schedules(opt)
+            dyn.setup_schedules(opt)
         dyn.optimizer.param_groups = [gr for gr in dyn.optimizer.param_groups if gr["name"] != "decoder"]
         params = [p for gr in stat.optimizer.param_groups + dyn.optimizer.param_groups for p in gr["params"]] \
             + list(self.blce.model.get_params())
@@ -255,6 +265,21 @@ class DeblurTrainer:
         photo = self.forward_backward()
         self.optimizer_step()
         return photo
+
+    def update_learning_rate(self, iteration):
+        """train.py:312-313, before the iteration's renders (lr_schedule=True only)."""
+        self.dyn.update_learning_rate(iteration)
+        self.stat.update_learning_rate(iteration)
+
+    def device_adam(self, first_iteration, horizon):
+        """The three optimisers as ONE mobgs_amd.optim.DeviceAdam plan whose steps run the rates of iterations
+        first_iteration, first_iteration + 1, ...: the Gaussian sets' schedules as update_learning_rate() applies them, the
+        blur kernel's rate as blcekernel.adjust_lr() leaves it after each step (train.py:807), starting from its present
+        value.  Gradients are the views of self.bucket, which stay where they are."""
+        schedules = list(self.stat.schedules().items()) + list(self.dyn.schedules().items()) \
+            + [(g, MultiplicativeLR(g["lr"], self.blce.lr_factor, first_iteration)) for g in self.blce.optimizer.param_groups]
+        return DeviceAdam([self.stat.optimizer, self.dyn.optimizer, self.blce.optimizer], schedules, horizon=horizon,
+                          first_iteration=first_iteration)
 
     def optimizer_step(self):
         # train.py:790-807 steps the three optimisers one after the other (~26 one-tensor groups x 8 launches); here
@@ -399,10 +424,16 @@ class DeblurTrainer:
 
 def train(dev="cuda:0", iters=40, ns=4000, nd=2000, width=256, height=192, n_views=2, seed=0, lambda_flow=1e-2,
           shard=None, log=None, graph=False, prune_control_every=0, from_views=False, estimate_exposure=0,
-          report_dir=None, report_every=0):
+          report_dir=None, report_every=0, lr_schedule=False, graph_optimizer=False):
     """graph=True (single process): forward + losses + backward of the iteration recorded ONCE as a HIP graph
     (mobgs_amd.graphed.GraphedCallable) and replayed, the Adam step outside -- for small images / few Gaussians, where an
     iteration is ~1400 launches and bound by the host (the reference's own 512x288 / 30 k operating point: 9.5 -> 7.5 ms).
+    lr_schedule=True: the loop also does what train.py:312-313 and :807 do around the step -- update_learning_rate(iteration)
+    on both sets before the iteration (the xyz rate decays as the reference's does) and blcekernel.adjust_lr() after it.
+    graph_optimizer=True (with graph=True; implies lr_schedule): the Adam step is recorded INTO the graph as well --
+    mobgs_amd.optim.DeviceAdam, whose rates and bias corrections are tabulated on the host and indexed on the device -- and
+    the host does after_replay() per iteration instead of the walk over the parameter groups.  Same loss history, bit for
+    bit, as lr_schedule=True run eagerly.
     prune_control_every=K > 0: every K iterations, between two iterations and outside any capture, the dynamic set drops
     one spline control point where that moves the projected trajectory by at most dyn.error_threshold pixels
     (TrainableGaussians.onedown_control_pts; in place, so a recorded iteration stays valid) and the smallest count is
@@ -417,8 +448,11 @@ def train(dev="cuda:0", iters=40, ns=4000, nd=2000, width=256, height=192, n_vie
     testing iterations)."""
     import time
     started = time.time()
-    t = DeblurTrainer(dev, ns, nd, width, height, n_views, seed, lambda_flow, shard, iters, from_views)
-    history = []
+    lr_schedule = lr_schedule or graph_optimizer
+    t = DeblurTrainer(dev, ns, nd, width, height, n_views, seed, lambda_flow, shard, iters, from_views, lr_schedule)
+    if graph_optimizer and (not graph or t.shard.collective):
+        raise ValueError("graph_optimizer=True needs graph=True and a single process")
+    history, adam = [], None
     prune_views = t.prune_viewpoints() if prune_control_every else None
     fb, pending = None, []
     for it in range(1, iters + 1):
@@ -426,10 +460,24 @@ def train(dev="cuda:0", iters=40, ns=4000, nd=2000, width=256, height=192, n_vie
             t.estimate_exposure()
         if graph and it == 2 and not t.shard.collective:   # (iteration 1 ran eagerly: arenas and hints exist)
             from mobgs_amd.graphed import GraphedCallable
-            fb = GraphedCallable(t.forward_backward, warmup=0)
+            if graph_optimizer:
+                adam = t.device_adam(first_iteration=it, horizon=iters)
+
+                def forward_backward_step():
+                    loss = t.forward_backward()
+                    adam.step()
+                    return loss
+                fb = GraphedCallable(forward_backward_step, warmup=0)
+            else:
+                fb = GraphedCallable(t.forward_backward, warmup=0)
+        if lr_schedule and adam is None:
+            t.update_learning_rate(it)
         if fb is not None:
             photo = fb()
-            t.optimizer_step()
+            if adam is not None:
+                adam.after_replay()
+            else:
+                t.optimizer_step()
             # the counts of the replays land in pinned rows: check() sees the replays that have COMPLETED.  The host enqueues a
             # replay in a fraction of its run time, so it is kept at most two iterations ahead (an event per iteration) -- an
             # arena outgrown by the moving scene (its frame saw empty lists: a background image, no splat gradients) is then
@@ -441,10 +489,14 @@ def train(dev="cuda:0", iters=40, ns=4000, nd=2000, width=256, height=192, n_vie
                 pending.pop(0).synchronize()
             if not fb.check():
                 torch.cuda.synchronize()
+                if adam is not None:   # (nothing was resized: the same pointers again, the counters carried over)
+                    adam.rebuild()
                 fb.recapture()
             history.append(float(photo))
         else:
             history.append(float(t.iteration()))
+        if lr_schedule and adam is None:
+            t.blce.adjust_lr()
         if prune_control_every and it % prune_control_every == 0:
             pruned = t.dyn.onedown_control_pts(prune_views)
             if t.shard.rank == 0:
@@ -458,6 +510,8 @@ def train(dev="cuda:0", iters=40, ns=4000, nd=2000, width=256, height=192, n_vie
             gc.freeze()
         if log and (it % log == 0 or it == 1) and t.shard.rank == 0:
             print(f"it {it:4d}  photometric {history[-1]:.5f}")
+    if adam is not None:   # the optimisers' host state as the eager loop would have left it
+        adam.sync_to_host()
     return history, t.stat, t.dyn, t.blce, t.bucket
 
 
@@ -469,6 +523,13 @@ if __name__ == "__main__":
     ap.add_argument("--width", type=int, default=512)
     ap.add_argument("--height", type=int, default=288)
     ap.add_argument("--graph", action="store_true", help="replay forward + backward as one HIP graph (single process)")
+    ap.add_argument("--lr-schedule", action="store_true",
+                    help="update_learning_rate(iteration) before and blcekernel.adjust_lr() after every iteration")
+    ap.add_argument("--graph-optimizer", action="store_true",
+                    help="with --graph: record the Adam step into the graph as well (DeviceAdam; implies --lr-schedule)")
+    ap.add_argument("--lambda-flow", type=float, default=1e-2,
+                    help="weight of the flow-consistency term (0, the shipped configs: every kernel of the iteration is "
+                         "deterministic and two runs give the same history bit for bit)")
     ap.add_argument("--prune-control-every", type=int, default=0, metavar="K",
                     help="every K iterations drop one spline control point where the trajectory moves <= 1 px (0 = never)")
     ap.add_argument("--from-views", action="store_true",
@@ -488,4 +549,5 @@ if __name__ == "__main__":
         dist.init_process_group("nccl", device_id=torch.device("cuda", local))
     train(dev=f"cuda:{local}", iters=a.iters, ns=a.ns, nd=a.nd, width=a.width, height=a.height, log=10, graph=a.graph,
           prune_control_every=a.prune_control_every, from_views=a.from_views, estimate_exposure=a.estimate_exposure,
-          report_dir=a.report_dir, report_every=a.report_every)
+          report_dir=a.report_dir, report_every=a.report_every, lr_schedule=a.lr_schedule,
+          graph_optimizer=a.graph_optimizer, lambda_flow=a.lambda_flow)

@@ -1245,6 +1245,45 @@ int mobgs_report_compose(int H, int W, int n_panels, const MobgsReportPanel* pan
                          int n_stats, float focal, float cx, float cy, float skew, float pixel_offset, int vertical,
                          uint8_t* sheet, void* stream);
 
+/* ---- K27: the Adam step of K16 with its factors formed ON THE DEVICE, from tables and counters in device memory ------
+ * mobgs_adam_step (K16) takes step_size = lr / (1 - beta1^t) and bias2_sqrt = sqrt(1 - beta2^t) per tensor from the host:
+ * recorded into a graph they freeze, and so does a learning rate set on the host.  Here the host tabulates once -- the
+ * learning rate of every iteration, and 1 - beta1^t and sqrt(1 - beta2^t) for every step count t, all as float64, each
+ * formed by the host statements the eager path uses -- and the device only indexes (csrc/adam_dev.hip).  Entry points
+ * and structs only: MOBGS_ABI_VERSION stays as it is.  Two launches per step on the caller's stream; neither synchronises,
+ * allocates or reads back, and no argument changes between steps, so both can be recorded into a graph and replayed.
+ * Every pointer below is a DEVICE pointer, the descriptor arrays included.
+ *
+ * mobgs_adam_dev_factors: counters = [iteration, step_0 .. step_{n-1}] (int32).  For tensor i, with row = iteration
+ *   clamped to 0 .. lr_rows - 1 and t = step_i + 1 clamped to 0 .. bc_rows - 1:
+ *     factors[2 i]     = (float)(lr[row * lr_stride] / bc1[t])      (the correctly rounded double quotient, rounded to
+ *     factors[2 i + 1] = (float)bc2s[t]                              fp32 as a host c_float is: K16's host factors, bit for bit)
+ *   then step_i and iteration advance by one.  lr_stride = 0: a constant rate (one value).  The clamps keep every read
+ *   inside the tables; refusing a step past the last row is the caller's job.  One workgroup, integer state, no atomics.
+ * mobgs_adam_dev_step: K16's update (csrc/adam_shared.h: the same float4 body, scalar tail and alignment test) on
+ *   n_tensors tensors, descriptor and factors read from device memory by the block's tensor index: no limit of 64.
+ *   w1 = (float)(1 - beta1), beta2, w2 = (float)(1 - beta2) and eps travel in the descriptor, so tensors of several
+ *   (betas, eps) classes share a launch.  longest: the largest n among the descriptors (sizes the grid; a tensor is
+ *   never accessed at or beyond its own n whatever longest says).  n = 0: nothing is read or written.
+ * Refused with MOBGS_E_INVALID before any launch: a negative count, n_tensors > 65535 (the grid's second dimension), a
+ *   NULL array with n_tensors > 0, a negative longest or one that needs more than 2^31 - 1 workgroups. */
+typedef struct MobgsAdamDevSchedule {
+    const double *lr, *bc1, *bc2s;
+    int32_t lr_stride, lr_rows, bc_rows, reserved;
+} MobgsAdamDevSchedule;
+typedef struct MobgsAdamDevTensor {
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    int64_t n;
+    float w1, beta2, w2, eps;
+} MobgsAdamDevTensor;
+int mobgs_adam_dev_factors(int n_tensors, const MobgsAdamDevSchedule* schedules_dev, int32_t* counters_dev,
+                           float* factors_dev, void* stream);
+int mobgs_adam_dev_step(int n_tensors, const MobgsAdamDevTensor* tensors_dev, const float* factors_dev, int64_t longest,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -147,6 +147,74 @@ class TrainableGaussians(GaussianParams):
         from .optim import FusedAdam   # torch.optim.Adam whose step() is ONE launch (the caller's loop stays unchanged)
         self.optimizer = FusedAdam(groups, lr=0.0, eps=1e-15)
 
+    # ---- learning-rate schedules (reference :625-661 and :663-680) ---------------------------------------------------
+    _SCHEDULES = ("xyz_scheduler_args", "grid_scheduler_args", "deformation_scheduler_args", "pose_scheduler_args")
+
+    def setup_schedules(self, training_args, stage="coarse"):
+        """The schedules the reference's training_setup builds next to its optimiser: xyz from position_lr_init / _final,
+        deformation and grid from their own pairs (all three times spatial_lr_scale), posenet from pose_lr_init (a tenth of
+        it in the fine stage) / pose_lr_final; every one over position_lr_max_steps.  A schedule whose values the
+        arguments do not carry is left out, and update_learning_rate() raises if a group then asks for it.
+        training_setup() does not call this: its result stays what it was."""
+        from .general_utils import get_expon_lr_func
+        o, scale = training_args, self.spatial_lr_scale
+        has = lambda *names: all(hasattr(o, n) for n in names)  # noqa: E731
+        for name in self._SCHEDULES:
+            self.__dict__.pop(name, None)
+        if not has("position_lr_max_steps"):
+            return self
+        steps = o.position_lr_max_steps
+        if has("position_lr_init", "position_lr_final"):
+            self.xyz_scheduler_args = get_expon_lr_func(lr_init=o.position_lr_init * scale,
+                                                        lr_final=o.position_lr_final * scale, max_steps=steps)
+        if has("deformation_lr_init", "deformation_lr_final"):
+            self.deformation_scheduler_args = get_expon_lr_func(lr_init=o.deformation_lr_init * scale,
+                                                                lr_final=o.deformation_lr_final * scale, max_steps=steps)
+        if has("grid_lr_init", "grid_lr_final"):
+            self.grid_scheduler_args = get_expon_lr_func(lr_init=o.grid_lr_init * scale, lr_final=o.grid_lr_final * scale,
+                                                         max_steps=steps)
+        if has("pose_lr_init", "pose_lr_final"):
+            self.pose_scheduler_args = get_expon_lr_func(
+                lr_init=o.pose_lr_init / 10 if stage == "fine" else o.pose_lr_init, lr_final=o.pose_lr_final,
+                max_steps=steps)
+        return self
+
+    def schedule_of(self, group_name: str):
+        """The schedule update_learning_rate() applies to a group of this name (the reference's tests, in its order:
+        == "xyz", "grid" in name, == "deformation", == "posenet"), or None for a group that keeps its rate."""
+        if group_name == "xyz":
+            attr = "xyz_scheduler_args"
+        elif "grid" in group_name:
+            attr = "grid_scheduler_args"
+        elif group_name == "deformation":
+            attr = "deformation_scheduler_args"
+        elif group_name == "posenet":
+            attr = "pose_scheduler_args"
+        else:
+            return None
+        fn = getattr(self, attr, None)
+        if fn is None:
+            raise AttributeError(f"TrainableGaussians: the group {group_name!r} is scheduled by {attr}, which does not "
+                                 "exist: call setup_schedules(training_args) with arguments that carry its rates")
+        return fn
+
+    def update_learning_rate(self, iteration):
+        """gaussian_model.py:663-680: the scheduled groups' rates for this iteration."""
+        for group in self.optimizer.param_groups:
+            fn = self.schedule_of(group["name"])
+            if fn is not None:
+                group["lr"] = fn(iteration)
+
+    def schedules(self) -> dict:
+        """{(optimizer, group name): schedule} for the scheduled groups the optimiser holds now: what
+        mobgs_amd.optim.DeviceAdam takes."""
+        out = {}
+        for group in self.optimizer.param_groups:
+            fn = self.schedule_of(group["name"])
+            if fn is not None:
+                out[(self.optimizer, group["name"])] = fn
+        return out
+
     def adopt_optimizer_state(self):
         """Move the Adam moments torch allocated on the first step() into table fields (so that they are resized with
         the parameters).  Called lazily by every resize."""

@@ -169,8 +169,17 @@ class GraphedCallable:
         trainer.iteration()                              # an ordinary eager iteration first: arenas and hints exist
         fb = GraphedCallable(trainer.forward_backward, warmup=0)   # reads parameters / cameras / targets, writes the gradients
         loss = fb()                                      # first call: capture + one replay; then: one graph launch
-        fused_adam_step(optimizers)                      # NOT inside: its bias corrections are host scalars of the step count
+        fused_adam_step(optimizers)                      # outside: ITS bias corrections are host scalars of the step count
         fb.check() / fb.recapture()                      # as GraphedRenderStep
+
+    The Adam step CAN be recorded as well, through optim.DeviceAdam: its learning rates and bias corrections are tabulated on
+    the host once and looked up on the device by counters that live there, so nothing of the step is a host scalar --
+
+        adam = DeviceAdam(optimizers, schedules, horizon)
+        fb = GraphedCallable(lambda: (trainer.forward_backward(), adam.step())[0], warmup=0)
+        loss = fb(); adam.after_replay()                 # per iteration: one graph launch + the host side of the step
+
+    (examples/train_deblur_synth.py --graph --graph-optimizer; recapture(): adam.rebuild() first when tensors were resized).
 
     Contract for `fn`: no arguments; everything it reads lives in tensors that are updated IN PLACE between calls (parameters
     by the optimiser, cameras / targets by .copy_); its gradient destination is persistent (FlatGradients / LeafGradSink or
