@@ -1284,6 +1284,58 @@ int mobgs_adam_dev_factors(int n_tensors, const MobgsAdamDevSchedule* schedules_
 int mobgs_adam_dev_step(int n_tensors, const MobgsAdamDevTensor* tensors_dev, const float* factors_dev, int64_t longest,
                         void* stream);
 
+/* ---- K28: the HexPlane grid regularisers: smoothness along h, total variation, |1 - t| of the time planes -------------
+ * The reference's scene/regulation.py:13-28 (compute_plane_tv, compute_plane_smoothness) and scene/gaussian_model.py:
+ * 1373-1415 (_plane_regulation, _time_regulation, _l1_regulation, compute_regulation) for ALL planes of a call at once
+ * (csrc/gridreg.hip, built with -ffp-contract=off).  Entry points and a struct only: MOBGS_ABI_VERSION stays as it is.
+ * Two launches forward, one backward, on the caller's stream; none synchronises, allocates, zero-fills or reads back and
+ * there are no atomics, so all can be recorded into a graph, and the same planes give the same bits.
+ *
+ * planes_host: a HOST array of n_planes records; t and grad are DEVICE pointers.  A plane is [C, h, w] fp32 with element
+ *   strides sc, sh, sw, one of which must be the unit direction: sc == 1 (channels-last; C == 1 counts) or sw == 1 (NCHW;
+ *   w == 1 counts); anything else is the caller's to copy.  h is the direction the differences run along.  kind:
+ *     SMOOTH     S0 = sum of sd^2, sd[k] = (t[k+2] - t[k+1]) - (t[k+1] - t[k]) along h, every difference rounded to fp32 as
+ *                the reference's statements round it, the square and the sum in float64; out[slot] += S0 inv0
+ *                (inv0 = 1 / (C (h - 2) w) for the reference's mean).  Needs h >= 3: the reference yields NaN below.
+ *     TV         S0 = sum of squared first differences along h, S1 = along w; out[slot] += 2 (S0 inv0 + S1 inv1)
+ *                (compute_plane_tv: inv0 = 1 / (C (h - 1) w + 1e-6), inv1 = 1 / (C h (w - 1) + 1e-6))
+ *     L1         S1 = sum of |1 - t| (the difference in fp32); out[slot] += S1 inv1
+ *     SMOOTH_L1  both on one read of the plane: out[slot] += S0 inv0, out[slot + 1] += S1 inv1
+ *   Several records may share a slot (the planes of a term; the images of a batch, each with the batch's count).
+ * mobgs_gridreg_blocks: workgroups of the streaming launch for this table (a host computation; 0 for a table that
+ *   would be refused).  partial: scratch, [blocks, 2] doubles, contents irrelevant on entry.
+ * mobgs_gridreg_fwd: out[0 .. n_slots) = the slots' float64 sums rounded to fp32 once.  weights (DEVICE, [n_slots]) and
+ *   total (one float), both given or both NULL: *total = ((weights[0] out[0]) + weights[1] out[1]) + ... in fp32, left to
+ *   right.  grad is not read.
+ * mobgs_gridreg_bwd: grad of every record, fully written (no zero-fill needed), DENSE in the plane's arm: [h][w][C] for a
+ *   channels-last plane, [C][h][w] for an NCHW one.  The cotangent of slot s is v_out[s], or with weights
+ *   v_out[0] weights[s] (v_out is then the cotangent of the weighted total); read from device memory.  An element is
+ *   (float)(2 inv0 cot (sd[j-2] - 2 sd[j-1] + sd[j]) - inv1 cot' sign(1 - t[j])), the combination in float64 and rounded
+ *   once, with sd = 0 where the window leaves the plane and sign(0) = 0 as torch.abs has it; TV:
+ *   (float)(4 inv0 cot (dh[j-1] - dh[j]) + 4 inv1 cot (dw[i-1] - dw[i])).
+ * Refused with MOBGS_E_INVALID before any launch, under the entry point's name: n_planes outside 1 .. MAX_PLANES,
+ *   n_slots outside 1 .. MAX_SLOTS, a NULL table, plane, partial, out or v_out (grad: backward only), a misaligned
+ *   pointer, a non-positive C, h or w, a negative stride, no unit-stride direction, an unknown kind, a slot outside the
+ *   outputs, h < 3 with a smoothness kind, a negative or NaN reciprocal, a plane spanning 2^31 elements or more. */
+#define MOBGS_GRIDREG_SMOOTH 0
+#define MOBGS_GRIDREG_TV 1
+#define MOBGS_GRIDREG_L1 2
+#define MOBGS_GRIDREG_SMOOTH_L1 3
+#define MOBGS_GRIDREG_MAX_PLANES 32
+#define MOBGS_GRIDREG_MAX_SLOTS 4
+typedef struct MobgsGridPlane {
+    const float* t;
+    float* grad;
+    int32_t C, h, w, kind, slot, reserved;
+    int64_t sc, sh, sw;
+    double inv0, inv1;
+} MobgsGridPlane;
+int mobgs_gridreg_blocks(int n_planes, const MobgsGridPlane* planes_host, int n_slots);
+int mobgs_gridreg_fwd(int n_planes, const MobgsGridPlane* planes_host, int n_slots, const float* weights,
+                      double* partial, float* out, float* total, void* stream);
+int mobgs_gridreg_bwd(int n_planes, const MobgsGridPlane* planes_host, int n_slots, const float* weights,
+                      const float* v_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

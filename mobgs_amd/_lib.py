@@ -161,6 +161,12 @@ class MobgsReportPanel(ctypes.Structure):
     _fields_ = _STRUCTS["MobgsReportPanel"]
 
 
+class MobgsGridPlane(ctypes.Structure):
+    """include/mobgs_hip.h MobgsGridPlane: one plane of a grid-regulariser call (device pointers, sizes, element strides,
+    term kind, output slot, reciprocal counts)."""
+    _fields_ = _STRUCTS["MobgsGridPlane"]
+
+
 def _bind(lib, name, restype, argtypes):
     fn = getattr(lib, name)
     fn.restype = restype

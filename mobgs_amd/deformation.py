@@ -34,7 +34,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 import torch.nn.init as init
 
-from . import _lib
+from . import _lib, regulation
 from ._lib import check, f32c, ptr, stream
 
 COMBS = list(itertools.combinations(range(4), 2))
@@ -355,6 +355,28 @@ class deform_network(nn.Module):
 
     def get_grid_parameters(self):
         return self.deformation_net.get_grid_parameters()
+
+    # ---- the grid regulariser (the reference's scene/gaussian_model.py:1373-1415, there on GaussianModel) -------------
+    def _plane_regulation(self):
+        """Sum of compute_plane_smoothness over the spatial planes 0, 1, 3 of every level (the smoothness function, not
+        the TV one, as in the reference).  For logging: this and the two methods below each run the whole 18-plane
+        forward and keep one of its three terms (and indexing adds a select to the backward); a caller that wants more
+        than one calls regulation.regulation_terms(grids) once, a loss uses compute_regulation."""
+        return regulation.regulation_terms(self.deformation_net.grid.grids)[0]
+
+    def _time_regulation(self):
+        """The same sum over the time planes 2, 4, 5."""
+        return regulation.regulation_terms(self.deformation_net.grid.grids)[1]
+
+    def _l1_regulation(self):
+        """Sum of mean |1 - t| over the time planes."""
+        return regulation.regulation_terms(self.deformation_net.grid.grids)[2]
+
+    def compute_regulation(self, time_smoothness_weight, l1_time_planes_weight, plane_tv_weight):
+        """plane_tv_weight plane + time_smoothness_weight time + l1_time_planes_weight l1: one autograd node, one forward
+        launch plus finish and one backward launch for all 18 planes (mobgs_amd/regulation.py)."""
+        return regulation.grid_regulation(self.deformation_net.grid.grids, time_smoothness_weight,
+                                          l1_time_planes_weight, plane_tv_weight)
 
 
 class SeesawArgs:
