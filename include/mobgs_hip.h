@@ -1336,6 +1336,38 @@ int mobgs_gridreg_fwd(int n_planes, const MobgsGridPlane* planes_host, int n_slo
 int mobgs_gridreg_bwd(int n_planes, const MobgsGridPlane* planes_host, int n_slots, const float* weights,
                       const float* v_out, void* stream);
 
+/* ---- K29: one-launch snapshot / restore of a per-splat table (training checkpoints, mobgs_amd/checkpoint.py) -----------
+ * The table of K13 (parameters, Adam moments, statistics, the uint8 deformation table, the integer knot counts) as ONE
+ * packed block and back (csrc/snapshot.hip).  Entry points and a struct only: MOBGS_ABI_VERSION stays as it is.  One launch
+ * each on the caller's stream; neither synchronises, allocates or reads back.  Not meant to be recorded into a graph: n
+ * changes with every densification.  fields_dev is a DEVICE array of n_fields records; rows, block and sum_dev are device
+ * pointers.
+ *
+ * Packed layout: field f occupies the slot [offset, offset + round16(n row_bytes)) of the block; every offset and the
+ *   block's base are multiples of 16, slots do not overlap (the caller lays them out: checkpoint.pack_layout).  The copy
+ *   is byte-wise, whatever the element type.  A 16-byte lane is one access where the field's base is 16-byte aligned, four
+ *   4-byte accesses where it is 4-byte aligned, bytes otherwise; the lane with the field's last bytes goes byte by byte.
+ * mobgs_rows_snapshot: slot_f = rows_f[0, n row_bytes) followed by zeros to the slot's end (< 16 bytes), for every field;
+ *   nothing of a field is read at or beyond n row_bytes and nothing of the block is written outside the slots.
+ *   *sum_dev += the sum of the 32-bit words of all slots as an unsigned 64-bit integer (one atomic add per workgroup; an
+ *   integer sum has no order); the caller zeroes it beforehand.  zero_new is not read.
+ * mobgs_rows_restore: rows_f[0, n row_bytes) = the slot's first n row_bytes bytes; a field with zero_new != 0 also gets
+ *   zeros in rows [n, capacity); rows [n, capacity) of every other field are not written.
+ * longest_row_bytes: the largest row_bytes among the records (sizes the grid; a field is never touched beyond its own
+ *   size whatever this says).  n = 0 or row_bytes = 0: nothing of that field is read or written.
+ * Refused with MOBGS_E_INVALID before any launch: n_fields outside 0 .. 65535, a negative n or longest_row_bytes, capacity
+ *   below n, a NULL table, block or sum, a block that is not 16-byte aligned, sizes that overflow 63 bits, more than
+ *   2^31 - 1 workgroups.  The records live in device memory and are the caller's to get right. */
+typedef struct MobgsRowsField {
+    void* rows;
+    int64_t row_bytes, offset;
+    int32_t zero_new, reserved;
+} MobgsRowsField;
+int mobgs_rows_snapshot(int n_fields, const MobgsRowsField* fields_dev, int64_t n, int64_t longest_row_bytes, void* block,
+                        uint64_t* sum_dev, void* stream);
+int mobgs_rows_restore(int n_fields, const MobgsRowsField* fields_dev, int64_t n, int64_t capacity,
+                       int64_t longest_row_bytes, const void* block, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

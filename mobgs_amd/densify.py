@@ -420,6 +420,19 @@ class TrainableGaussians(GaussianParams):
             pc.rgbdecoder.load_state_dict(torch.load(pt, map_location=device))
         return pc
 
+    # ---- training checkpoints (mobgs_amd/checkpoint.py; include/mobgs_hip.h K29) -----------------------------------------
+    def state_dict(self) -> dict:
+        """The whole table (parameters, Adam moments, statistics, deformation table) as ONE packed device block with its
+        checksum, the field list and the optimiser's rates / step counts: checkpoint.set_state_dict."""
+        from . import checkpoint
+        return checkpoint.set_state_dict(self)
+
+    def load_state_dict(self, state: dict):
+        """state_dict()'s result back into this set (any row count; the optimiser, if both have one, is re-keyed)."""
+        from . import checkpoint
+        checkpoint.load_set_state(self, state)
+        return self
+
     # ---- creation from data (scene/gaussian_model.py:495-582, :406-493) ------------------------------------------------
     @classmethod
     def _from_init(cls, params, extras, spatial_lr_scale, is_dynamic, device, decoder, capacity_factor, spatial_sort):
