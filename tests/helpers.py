@@ -96,6 +96,24 @@ def same_bits(a, b):
     return a.shape == b.shape and a.dtype == b.dtype and torch.equal(bits(a), bits(b))
 
 
+def check_tile_order(tile_order, nt, tile_offsets=None):
+    """What include/mobgs_hip.h promises of a tile schedule, and no more: every tile appears exactly once, or exactly 4
+    times with the heavy bit (1 << 30) set; with the lists' offsets also: at most sched_max_heavy(nt) heavy tiles (all of
+    them on grids of <= 1024 tiles, an eighth beyond) and no heavy list shorter than a light one."""
+    order = np.asarray(tile_order)
+    ids = order[order >= 0]
+    heavy = ids[(ids & (1 << 30)) != 0] & ~(1 << 30)
+    light = ids[(ids & (1 << 30)) == 0]
+    assert len(np.unique(heavy)) * 4 == len(heavy)
+    assert len(np.unique(light)) == len(light)
+    assert sorted(np.unique(heavy).tolist() + light.tolist()) == list(range(nt))
+    if tile_offsets is not None:
+        assert len(np.unique(heavy)) <= (nt if nt <= 1024 else nt // 8)
+        lens = np.diff(np.asarray(tile_offsets).astype(np.int64))
+        if len(heavy) and len(light):
+            assert lens[heavy].min() >= lens[light].max()
+
+
 def scene_from_fixture(fx, device="cpu", requires_grad=True):
     """-> cam, stat_pc, dyn_pc, bg, w2c (all on `device`)."""
     T = torch.from_numpy

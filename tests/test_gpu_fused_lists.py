@@ -51,13 +51,8 @@ def _slots(tl, n_box):
 
 
 def _check_order(tl, nt):
-    order = tl.tile_order.cpu().numpy()
-    ids = order[order >= 0]
-    heavy = ids[(ids & (1 << 30)) != 0] & ~(1 << 30)
-    light = ids[(ids & (1 << 30)) == 0]
-    assert len(np.unique(heavy)) * 4 == len(heavy)
-    assert len(np.unique(light)) == len(light)
-    assert sorted(np.unique(heavy).tolist() + light.tolist()) == list(range(nt))
+    from helpers import check_tile_order
+    check_tile_order(tl.tile_order.cpu().numpy(), nt)
 
 
 def _compare(a, b, n_box, n_isects, nt):
