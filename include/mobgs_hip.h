@@ -1101,6 +1101,51 @@ int mobgs_lpips_alex_spatial(int B, int H, int W, const float* img0, const float
                              const float* mask, int flags, void* scratch, size_t scratch_bytes, float* map, double* out,
                              void* stream);
 
+/* ---- K24, backward: the gradient of the LPIPS total with respect to the images (LPIPS as a training loss) -----------
+ * What autograd gives the reference's lpips_loss (utils/loss_utils.py:228-230) through PNetLin.forward, for the images only
+ * (the trunk and the heads are constants).  Same trunk, weights, flags and layout as mobgs_lpips_alex, whose results keep
+ * their bits (csrc/lpips.hip).  Entry points only: MOBGS_ABI_VERSION stays.
+ *
+ * taps: a HOST array of the five device pointers that a mobgs_lpips_alex call with the same B, H, W, images, weights and
+ *   flags filled ([2B, h_l, w_l, C_l], channel-last); only read.
+ * v_total [B] fp32: the cotangent of column 0 of the forward's row, per pair.
+ * g_img0 / g_img1 [B,3,H,W] fp32, fully written: the gradient with respect to img0 / img1 as the caller passed them (through
+ *   the scaling layer, the 2 x - 1 of MOBGS_LPIPS_UNIT_RANGE and the clamp of MOBGS_LPIPS_CLAMP, which passes the gradient
+ *   where 0 <= img <= 1, bounds included, as torch.clamp does).  NULL = that side is not wanted: only the wanted images are
+ *   walked.  Both NULL is refused.  MOBGS_LPIPS_QUANTIZE with a wanted g_img1 is refused: the truncation has no gradient.
+ * bwd_weights (host struct, device pointers, 16-byte aligned): w2 .. w5, the weights of layers 2 .. 5 packed for the
+ *   backward-data pass [Cout k k, Cin]: row (ky k + kx) Cout + co holds weight[co, ci, k - 1 - ky, k - 1 - kx] in column ci
+ *   (the taps flipped, the channel axes exchanged).  mobgs_lpips_bwd_pack_k(layer) = Cout k k for layer = 2 .. 5 (4800, 3456,
+ *   2304, 2304: multiples of the K step), 0 for another value.  Layer 1 reads the forward's w1.
+ * tap_grads: NULL, or a HOST array of five device pointers (16-byte aligned) that receive the gradient with respect to the
+ *   five pre-activations (the ReLU mask applied), [n B, h_l, w_l, C_l] channel-last, n = the number of wanted sides: image
+ *   n b + k is the k-th wanted side of pair b.  The image gradients have the same bits with and without it.
+ * scratch: mobgs_lpips_bwd_scratch_bytes(B, H, W) bytes, 256-byte aligned, contents irrelevant on entry; 0 for a refused
+ *   shape.
+ *
+ * Per tap and pixel, with u the wanted side's vector and v the other one: a = |u| + 1e-10, b = |v| + 1e-10,
+ *   e = u / a - v / b, s = 2 lin e, dd/du = s / a - u (sum s u) / (a^2 |u|), times v_total / (h_l w_l); fp32, one wave per
+ *   pixel.  Where |u| = 0 the second term is DEFINED as 0 (autograd's sqrt gives inf 0 = NaN there); the ReLU mask u > 0
+ *   removes the first.  The backward-data pass of layers 5 .. 2 is the forward's implicit GEMM (rows = the wanted images'
+ *   pixels) with an epilogue that adds the tap's own distance gradient and applies the mask; max-pool backward is a gather:
+ *   a position takes the gradient of each of its <= 2 x 2 windows whose maximum it is, the FIRST one in row-major order on
+ *   ties (torch's rule); layer 1 is a direct gather per image pixel.  No float atomics, no hand-off between workgroups; every
+ *   sum has an order fixed by the shapes: a pair's gradient is bit-identical from run to run, whatever B, the pair's place in
+ *   the batch and the set of wanted sides, and exactly +0 for equal images (v_total >= 0).  Pixels in no window of the first
+ *   convolution and pixels the clamp cuts get exactly 0.
+ * Refused with MOBGS_E_INVALID before any launch, under the entry point's name: as mobgs_lpips_alex, and the above.
+ * 11 launches and one per wanted side (5 distance kernels, 4 GEMMs, 2 pool gathers; the image kernel), no
+ * synchronisation, no read-back. */
+typedef struct MobgsLpipsBwdWeights {
+    const float *w2, *w3, *w4, *w5;
+} MobgsLpipsBwdWeights;
+size_t mobgs_lpips_bwd_scratch_bytes(int B, int H, int W);
+int mobgs_lpips_bwd_pack_k(int layer);
+int mobgs_lpips_alex_bwd(int B, int H, int W, const float* img0, const float* img1, const MobgsLpipsWeights* weights,
+                         const MobgsLpipsBwdWeights* bwd_weights, int flags, const float* const* taps,
+                         const float* v_total, void* scratch, size_t scratch_bytes, float* g_img0, float* g_img1,
+                         float* const* tap_grads, void* stream);
+
 /* ---- K25: tOF, the temporal optical-flow metric: dense Farneback flow and the distance of two flow fields -----------
  * What the reference's metrics.py:14-47 and :108-120 evaluate: cv2.calcOpticalFlowFarneback(prev, next, None, 0.5, 3, 15,
  * 3, 5, 1.2, 0) between consecutive 8-bit grey frames, for the prediction and for the ground truth, and the mean of

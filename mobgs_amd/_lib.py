@@ -146,6 +146,12 @@ class MobgsLpipsWeights(ctypes.Structure):
     _fields_ = _STRUCTS["MobgsLpipsWeights"]
 
 
+class MobgsLpipsBwdWeights(ctypes.Structure):
+    """include/mobgs_hip.h MobgsLpipsBwdWeights: the weights of layers 2 .. 5 packed for the backward-data pass (device
+    pointers)."""
+    _fields_ = _STRUCTS["MobgsLpipsBwdWeights"]
+
+
 class MobgsTofLevel(ctypes.Structure):
     """include/mobgs_hip.h MobgsTofLevel: one scale of the Farneback pyramid (width, height, taps, sigma)."""
     _fields_ = _STRUCTS["MobgsTofLevel"]

@@ -1,5 +1,5 @@
 // K24: LPIPS (net-lin, AlexNet trunk, version 0.1, spatial average) of a batch of image pairs (include/mobgs_hip.h): the
-// reference's models/networks_basic.py:68-105 over models/pretrained_networks.py:57-95.  Forward only.  gfx950 only.
+// reference's models/networks_basic.py:68-105 over models/pretrained_networks.py:57-95.  Forward, and the gradient with respect to the images.  gfx950 only.
 //
 //   lpips_conv_kernel<FIRST>   a convolution + bias + ReLU as an implicit GEMM on v_mfma_f32_32x32x2_f32: M = the output
 //                              pixels of all 2B images, N = Cout, K = Cin k k.  One workgroup (4 waves) owns a 128 x 64 tile
@@ -27,6 +27,13 @@
 //                              fp32 sum in layer order, an optional store, float64 sums of map m, m and map: thread,
 //                              wave butterfly, workgroup, one partial row per 1024 pixels of a pair.
 //   lpips_spatial_finish_kernel  one workgroup, one wave per pair: the sums in lpips_finish_kernel's order, the row.
+//
+// The backward pass (mobgs_lpips_alex_bwd: the gradient of the total with respect to the images, LPIPS as a loss):
+//   lpips_dist_bwd_kernel      the distance head's gradient per tap, one wave per pixel of a wanted image.
+//   lpips_conv_kernel<LP_BWD_TAP / LP_BWD_POOL>  the backward-data pass of layers 5 .. 2: the same GEMM body over the
+//                              flipped, channel-exchanged weight; the epilogue adds the tap's distance gradient and masks.
+//   lpips_pool_bwd_kernel      max-pool backward as a gather (first maximum in row-major order on ties).
+//   lpips_first_bwd_kernel     layer 1 into [B,3,H,W], with the scaling layer, 2 x - 1 and the clamp.
 //
 // Every output of a convolution is one k-ordered fmaf chain (the fp32 MFMA adds nothing wider), the same chain whatever tile
 // or row of a tile the pixel falls into; the workgroups of the distance kernel are cut per pair.  No float atomic, no
@@ -64,7 +71,16 @@ struct LpConvArgs {
     const float *w, *bias;           // [Kpad, Cout], [Cout]
     float* out;                      // [N, Ho, Wo, Cout]
     int N, Hi, Wi, Cin, Ho, Wo, Cout, ks, stride, pad, Kpad, M, flags;
+    // the backward-data arms: `in` and `out` hold the wanted images alone, image q of them is image q n_stride + n_off of tap
+    const float* tap;                // [2B, Ho, Wo, Cout]: the forward's ReLU map at the output (LP_BWD_TAP)
+    int n_stride, n_off;
 };
+
+// the arms of lpips_conv_kernel: what is staged and what the epilogue does.  The K loop is one text for all of them.
+constexpr int LP_FIRST = 0;          // layer 1: the slab is gathered from the images; bias + ReLU
+constexpr int LP_FWD = 1;            // layers 2 .. 5: bias + ReLU
+constexpr int LP_BWD_TAP = 2;        // backward-data onto a tap: out already holds the tap's distance gradient; add, mask
+constexpr int LP_BWD_POOL = 3;       // backward-data onto a pooled map: a plain store
 
 // the value the first convolution sees at (image n = 2 b + s, channel c, y, x): inside the image only
 __device__ __forceinline__ float lp_input(const LpConvArgs& a, int n, int c, int y, int x) {
@@ -79,8 +95,9 @@ __device__ __forceinline__ float lp_input(const LpConvArgs& a, int n, int c, int
     return (v - shift) / scale;
 }
 
-template <bool FIRST>
+template <int MODE>
 __global__ void __launch_bounds__(LP_THREADS) lpips_conv_kernel(LpConvArgs a) {
+    constexpr bool FIRST = MODE == LP_FIRST;
     __shared__ float sA[LP_BM * LP_APITCH];
     __shared__ __attribute__((aligned(16))) float sB[LP_BK * LP_BN];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -159,16 +176,28 @@ __global__ void __launch_bounds__(LP_THREADS) lpips_conv_kernel(LpConvArgs a) {
         }
     }
     // ---- bias + ReLU; accumulator register i of lane l is row (i & 3) + 8 (i >> 2) + 4 (l >> 5), column l & 31 ----
+    // the backward arms: out = the tap's distance gradient + the sum, where the tap is positive (LP_BWD_TAP); the sum (LP_BWD_POOL)
     const int col = n0 + wn + (lane & 31);
-    const float bias = a.bias[col];
+    const float bias = MODE <= LP_FWD ? a.bias[col] : 0.f;
+    const int P = a.Ho * a.Wo;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             const int m = m0 + wm + 32 * h + (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5);
             if (m < a.M) {
-                const float v = acc[h][i] + bias;
-                a.out[(size_t)m * a.Cout + col] = v > 0.f ? v : 0.f;
+                if (MODE <= LP_FWD) {
+                    const float v = acc[h][i] + bias;
+                    a.out[(size_t)m * a.Cout + col] = v > 0.f ? v : 0.f;
+                } else if (MODE == LP_BWD_TAP) {
+                    const int q = m / P;
+                    const float f = a.tap[((size_t)(q * a.n_stride + a.n_off) * P + (m - q * P)) * a.Cout + col];
+                    float* o = a.out + (size_t)m * a.Cout + col;
+                    const float v = *o + acc[h][i];
+                    *o = f > 0.f ? v : 0.f;
+                } else {
+                    a.out[(size_t)m * a.Cout + col] = acc[h][i];
+                }
             }
         }
     }
@@ -441,6 +470,182 @@ __global__ void __launch_bounds__(LP_FINISH_THREADS) lpips_spatial_finish_kernel
     }
 }
 
+// ---- the backward pass (mobgs_lpips_alex_bwd): the gradient of the total with respect to the images ---------------------
+// Only the wanted images are walked: the gradient maps hold n = 1 or 2 images per pair, image q = n b + k of them being
+// image q n_stride + n_off of the taps ((1, 0) with both sides wanted, (2, side) with one).
+
+// One wave per pixel of a wanted image, in lpips_dist_kernel's layout.  x: the image's own vector, y: the other side's.
+//   a = |x| + 1e-10, b = |y| + 1e-10, e = x / a - y / b, s = 2 w e, g = (s / a - x (sum s x) / (a^2 |x|)) v_total / P
+// and g = 0 where x = 0 (the ReLU mask; it also removes s / a where |x| = 0, and the second term is defined as 0 there).
+// With equal images e is x / a - x / a = +0 for either side, and every later value is +0.
+// feat [2B, P, C]; grad [n B, P, C]; grid (ceil(P / 64), n B).
+__global__ void __launch_bounds__(LP_THREADS) lpips_dist_bwd_kernel(const float* __restrict__ feat,
+                                                                    const float* __restrict__ lin,
+                                                                    const float* __restrict__ v_total, int P, int C,
+                                                                    int n_stride, int n_off, float* __restrict__ grad) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const size_t q = blockIdx.y, n = q * n_stride + n_off;
+    const float* fx = feat + n * (size_t)P * C;
+    const float* fy = feat + (n ^ 1) * (size_t)P * C;
+    float* g = grad + q * (size_t)P * C;
+    const int nj = C / MOBGS_WAVE;                       // 1, 3, 6, 4, 4
+    const float scale = v_total[n >> 1] / (float)P;
+    float w[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) w[j] = j < nj ? lin[lane + MOBGS_WAVE * j] : 0.f;
+    for (int i = 0; i < LP_DPIX / 4; ++i) {
+        const int p = blockIdx.x * LP_DPIX + 4 * i + wave;
+        if (p >= P) break;                               // (uniform over the wave)
+        float x[6], y[6], sx = 0.f, sy = 0.f;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            x[j] = j < nj ? fx[(size_t)p * C + lane + MOBGS_WAVE * j] : 0.f;
+            y[j] = j < nj ? fy[(size_t)p * C + lane + MOBGS_WAVE * j] : 0.f;
+            sx += x[j] * x[j];
+            sy += y[j] * y[j];
+        }
+        const float nx = sqrtf(wave_sum(sx)), a = nx + 1e-10f, b = sqrtf(wave_sum(sy)) + 1e-10f;
+        float s[6], dot = 0.f;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            s[j] = 2.f * w[j] * (x[j] / a - y[j] / b);
+            dot += s[j] * x[j];
+        }
+        dot = wave_sum(dot);
+        const float k = nx > 0.f ? dot / (a * a * nx) : 0.f;
+#pragma unroll
+        for (int j = 0; j < 6; ++j)
+            if (j < nj) g[(size_t)p * C + lane + MOBGS_WAVE * j] = x[j] > 0.f ? (s[j] / a - x[j] * k) * scale : 0.f;
+    }
+}
+
+// maxpool(3, 2) backward as a gather onto a tap.  tap [2B, Hi, Wi, C]; gp [nB, Ho, Wo, C]: the gradient of the pooled map;
+// grad [nB, Hi, Wi, C]: holds the tap's distance gradient on entry, the tap's gradient on exit.  A position lies in at most
+// 2 x 2 windows; it takes a window's gradient if it is the window's maximum, the FIRST one in row-major order on ties
+// (v > best moves the choice, as torch's kernels do), recomputed from the tap.  The windows are added in (oy, ox) order; a
+// row or column that no window covers keeps the distance gradient; then the ReLU mask.  Four channels per thread.
+__global__ void __launch_bounds__(LP_THREADS) lpips_pool_bwd_kernel(const float* __restrict__ tap,
+                                                                    const float* __restrict__ gp, float* __restrict__ grad,
+                                                                    int Hi, int Wi, int Ho, int Wo, int C4, int n_stride,
+                                                                    int n_off, size_t total) {
+    const size_t idx = (size_t)blockIdx.x * LP_THREADS + threadIdx.x;
+    if (idx >= total) return;
+    const int c = (int)(idx % C4);
+    size_t r = idx / C4;
+    const int x = (int)(r % Wi);
+    r /= Wi;
+    const int y = (int)(r % Hi);
+    const size_t q = r / Hi, n = q * n_stride + n_off;
+    const float4* t = reinterpret_cast<const float4*>(tap) + n * Hi * Wi * C4 + c;
+    const float4* g = reinterpret_cast<const float4*>(gp) + q * Ho * Wo * C4 + c;
+    const int here = y * Wi + x;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    const int oy0 = max((y - 1) >> 1, 0), oy1 = min(y >> 1, Ho - 1);      // 2 oy <= y <= 2 oy + 2
+    const int ox0 = max((x - 1) >> 1, 0), ox1 = min(x >> 1, Wo - 1);
+    for (int oy = oy0; oy <= oy1; ++oy) {
+        for (int ox = ox0; ox <= ox1; ++ox) {
+            const int first = 2 * oy * Wi + 2 * ox;
+            const float4 v0 = t[(size_t)first * C4];
+            float best[4] = {v0.x, v0.y, v0.z, v0.w};
+            int at[4] = {first, first, first, first};
+#pragma unroll
+            for (int dy = 0; dy < 3; ++dy) {
+#pragma unroll
+                for (int dx = 0; dx < 3; ++dx) {
+                    const int pos = first + dy * Wi + dx;
+                    const float4 v4 = t[(size_t)pos * C4];
+                    const float v[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        if (v[k] > best[k]) {
+                            best[k] = v[k];
+                            at[k] = pos;
+                        }
+                    }
+                }
+            }
+            const float4 g4 = g[((size_t)oy * Wo + ox) * C4];
+            const float gv[4] = {g4.x, g4.y, g4.z, g4.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (at[k] == here) acc[k] += gv[k];
+        }
+    }
+    const float4 f = t[(size_t)here * C4];
+    float4* o = reinterpret_cast<float4*>(grad) + idx;
+    const float4 d = *o;
+    float4 out;
+    out.x = f.x > 0.f ? d.x + acc[0] : 0.f;
+    out.y = f.y > 0.f ? d.y + acc[1] : 0.f;
+    out.z = f.z > 0.f ? d.z + acc[2] : 0.f;
+    out.w = f.w > 0.f ? d.w + acc[3] : 0.f;
+    *o = out;
+}
+
+// The first layer's backward-data pass, a direct gather: one thread per pixel (y, x) of a wanted image, its three colour
+// channels.  The outputs whose 11 x 11 window holds the pixel are oy with 4 oy - 2 <= y <= 4 oy + 8 (at most 3, ky = y + 2 -
+// 4 oy), columns alike; per output 64 channels, read as float4 against the forward's packed weight (row (c 11 + ky) 11 + kx,
+// 64 contiguous columns).  One fmaf chain per channel in (oy, ox, co) order.  Then the chain through the scaling layer
+// (1 / scale_c), 2 x - 1 (MOBGS_LPIPS_UNIT_RANGE) and the clamp: the gradient passes where 0 <= v <= 1, bounds included, as
+// torch.clamp does.  A pixel in no window gets +0.
+// The threads of a workgroup share the pixel's place (py, px) in its 4 x 4 cell: ky = (py + 2) mod 4 + 4 i and kx are then
+// uniform over the workgroup, so the weight reads are uniform (one row for all lanes) and a lane's own reads are its outputs'
+// 64 channels.  (One thread per pixel in image order spent half the backward pass in this kernel at 1352 x 1014: four
+// vector loads per four channels.)
+// g1 [nB, h1, w1, 64]; img, gimg [B, 3, H, W]; grid (ceil(cells / 256), 16, B), cells = ceil(H / 4) ceil(W / 4).
+__global__ void __launch_bounds__(LP_THREADS) lpips_first_bwd_kernel(const float* __restrict__ g1,
+                                                                     const float* __restrict__ w1,
+                                                                     const float* __restrict__ img, float* __restrict__ gimg,
+                                                                     int H, int W, int h1, int w1n, int n_stride_q,
+                                                                     int n_off_q, int flags) {
+    const int cells_x = (W + 3) >> 2, cells_y = (H + 3) >> 2;
+    const int cell = blockIdx.x * LP_THREADS + threadIdx.x;
+    if (cell >= cells_x * cells_y) return;
+    const int py = blockIdx.y >> 2, px = blockIdx.y & 3;                        // (uniform)
+    const int cy = cell / cells_x, cx = cell - cy * cells_x;
+    const int y = 4 * cy + py, x = 4 * cx + px;
+    if (y >= H || x >= W) return;
+    const size_t b = blockIdx.z, q = b * n_stride_q + n_off_q;
+    float acc[3] = {0.f, 0.f, 0.f};
+    for (int iy = 2; iy >= 0; --iy) {                                            // ky falls, oy rises
+        const int ky = ((py + 2) & 3) + 4 * iy;
+        if (ky > 10) continue;
+        const int oy = (y + 2 - ky) >> 2;                                        // (y + 2 - ky is a multiple of 4)
+        for (int ix = 2; ix >= 0; --ix) {
+            const int kx = ((px + 2) & 3) + 4 * ix;
+            if (kx > 10) continue;
+            const int ox = (x + 2 - kx) >> 2;
+            if (oy < 0 || oy >= h1 || ox < 0 || ox >= w1n) continue;             // (per lane: the image's border)
+            const float4* g = reinterpret_cast<const float4*>(g1 + ((q * h1 + oy) * w1n + ox) * 64);
+            const float4* wr = reinterpret_cast<const float4*>(w1 + (size_t)(ky * 11 + kx) * 64);
+#pragma unroll 4
+            for (int c4 = 0; c4 < 16; ++c4) {
+                const float4 gv = g[c4];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const float4 wv = wr[c * (121 * 16) + c4];
+                    acc[c] = fmaf(gv.x, wv.x, acc[c]);
+                    acc[c] = fmaf(gv.y, wv.y, acc[c]);
+                    acc[c] = fmaf(gv.z, wv.z, acc[c]);
+                    acc[c] = fmaf(gv.w, wv.w, acc[c]);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const size_t at = ((b * 3 + c) * H + y) * W + x;
+        const float scale = c == 0 ? .458f : (c == 1 ? .448f : .450f);
+        float v = acc[c] / scale;
+        if (flags & MOBGS_LPIPS_UNIT_RANGE) v = 2.f * v;
+        if (flags & MOBGS_LPIPS_CLAMP) {
+            const float p = img[at];
+            v = (p >= 0.f && p <= 1.f) ? v : 0.f;
+        }
+        gimg[at] = v;
+    }
+}
+
 // ---- host: sizes and the scratch layout ------------------------------------------------------------------------------
 struct LpPlan {
     int h[LP_LAYERS], w[LP_LAYERS];      // the taps
@@ -589,9 +794,9 @@ static int lp_run(const char* name, const LpPlan& p, const LpSpatialPlan* sp, in
         a.flags = flags;
         const unsigned blocks = (unsigned)((a.M + LP_BM - 1) / LP_BM) * (unsigned)(a.Cout / LP_BN);
         if (l == 0)
-            hipLaunchKernelGGL(lpips_conv_kernel<true>, dim3(blocks), dim3(LP_THREADS), 0, s, a);
+            hipLaunchKernelGGL(lpips_conv_kernel<LP_FIRST>, dim3(blocks), dim3(LP_THREADS), 0, s, a);
         else
-            hipLaunchKernelGGL(lpips_conv_kernel<false>, dim3(blocks), dim3(LP_THREADS), 0, s, a);
+            hipLaunchKernelGGL(lpips_conv_kernel<LP_FWD>, dim3(blocks), dim3(LP_THREADS), 0, s, a);
         const int P = p.h[l] * p.w[l];
         LpMapArgs ma = {};
         if (sp) {
@@ -675,6 +880,139 @@ static int lp_run(const char* name, const LpPlan& p, const LpSpatialPlan* sp, in
     return check_launch(name);
 }
 
+// the backward call's scratch: the five tap gradients and the gradients of the two pooled maps, sized for both sides
+struct LpBwdPlan {
+    size_t off_grad[LP_LAYERS], off_pool[2], bytes;
+};
+
+static bool lp_bwd_plan(int B, int H, int W, LpPlan& p, LpBwdPlan& q) {
+    if (!lp_plan(B, H, W, p)) return false;
+    const size_t N = 2 * (size_t)B;
+    size_t at = 0;
+    for (int l = 0; l < LP_LAYERS; ++l) {
+        q.off_grad[l] = at;
+        at += lp_align(N * p.h[l] * p.w[l] * LP_COUT[l] * sizeof(float));
+    }
+    for (int i = 0; i < 2; ++i) {
+        q.off_pool[i] = at;
+        at += lp_align(N * p.ph[i] * p.pw[i] * LP_COUT[i] * sizeof(float));
+    }
+    q.bytes = at;
+    return true;
+}
+
+static int lp_bwd_pack_k(int layer) {
+    if (layer < 2 || layer > LP_LAYERS) return 0;
+    return LP_COUT[layer - 1] * LP_KS[layer - 1] * LP_KS[layer - 1];
+}
+
+static int lp_bwd_run(const char* name, const LpPlan& p, const LpBwdPlan& bp, int B, int H, int W, const float* img0,
+                      const float* img1, const MobgsLpipsWeights* weights, const MobgsLpipsBwdWeights* bwd_weights, int flags,
+                      const float* const* taps, const float* v_total, void* scratch, size_t scratch_bytes, float* g_img0,
+                      float* g_img1, float* const* tap_grads, void* stream) {
+    if (flags & ~(MOBGS_LPIPS_UNIT_RANGE | MOBGS_LPIPS_CLAMP | MOBGS_LPIPS_QUANTIZE)) {
+        set_error("%s: flags = %d has unknown bits", name, flags);
+        return MOBGS_E_INVALID;
+    }
+    if (!img0 || !img1 || !weights || !bwd_weights || !taps || !v_total || !scratch) {
+        set_error("%s: NULL img0, img1, weights, bwd_weights, taps, v_total or scratch", name);
+        return MOBGS_E_INVALID;
+    }
+    if (!g_img0 && !g_img1) {
+        set_error("%s: g_img0 and g_img1 are both NULL: no gradient is wanted", name);
+        return MOBGS_E_INVALID;
+    }
+    if ((flags & MOBGS_LPIPS_QUANTIZE) && g_img1) {
+        set_error("%s: MOBGS_LPIPS_QUANTIZE with g_img1: the 8-bit truncation of img1 has no gradient", name);
+        return MOBGS_E_INVALID;
+    }
+    const float* lin[LP_LAYERS] = {weights->lin1, weights->lin2, weights->lin3, weights->lin4, weights->lin5};
+    const float* bw[LP_LAYERS] = {weights->w1, bwd_weights->w2, bwd_weights->w3, bwd_weights->w4, bwd_weights->w5};
+    for (int l = 0; l < LP_LAYERS; ++l) {
+        if (!bw[l] || !lin[l] || !taps[l] || (tap_grads && !tap_grads[l])) {
+            set_error("%s: NULL weight, head, tap or tap-gradient pointer of layer %d", name, l + 1);
+            return MOBGS_E_INVALID;
+        }
+        if (((uintptr_t)bw[l] & 15) || ((uintptr_t)lin[l] & 3) || ((uintptr_t)taps[l] & 15) ||
+            (tap_grads && ((uintptr_t)tap_grads[l] & 15))) {
+            set_error("%s: layer %d: packed weights, taps and tap gradients must be 16-byte aligned, heads 4-byte", name,
+                      l + 1);
+            return MOBGS_E_INVALID;
+        }
+    }
+    if (((uintptr_t)img0 & 3) || ((uintptr_t)img1 & 3) || ((uintptr_t)g_img0 & 3) || ((uintptr_t)g_img1 & 3) ||
+        ((uintptr_t)v_total & 3) || ((uintptr_t)scratch & 255)) {
+        set_error("%s: images, gradients and v_total must be 4-byte aligned, scratch 256-byte aligned", name);
+        return MOBGS_E_INVALID;
+    }
+    if (scratch_bytes < bp.bytes) {
+        set_error("%s: scratch_bytes = %zu, mobgs_lpips_bwd_scratch_bytes(%d, %d, %d) = %zu", name, scratch_bytes, B, H, W,
+                  bp.bytes);
+        return MOBGS_E_INVALID;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    char* base = (char*)scratch;
+    const int ns = (g_img0 ? 1 : 0) + (g_img1 ? 1 : 0);      // wanted sides
+    const int n_stride = ns == 2 ? 1 : 2, n_off = ns == 2 ? 0 : (g_img1 ? 1 : 0);
+    const int NQ = ns * B;
+    float* grad[LP_LAYERS];
+    for (int l = 0; l < LP_LAYERS; ++l) grad[l] = tap_grads ? tap_grads[l] : (float*)(base + bp.off_grad[l]);
+    float* gpool[2] = {(float*)(base + bp.off_pool[0]), (float*)(base + bp.off_pool[1])};
+    // the distance gradients of the five taps
+    for (int l = 0; l < LP_LAYERS; ++l) {
+        const int P = p.h[l] * p.w[l];
+        hipLaunchKernelGGL(lpips_dist_bwd_kernel, dim3((unsigned)p.rows[l], (unsigned)NQ), dim3(LP_THREADS), 0, s, taps[l],
+                           lin[l], v_total, P, LP_COUT[l], n_stride, n_off, grad[l]);
+    }
+    // layers 5 .. 2: the gradient of layer l's output -> the gradient of its input (tap l - 1, or the pooled map in front)
+    for (int l = LP_LAYERS - 1; l >= 1; --l) {
+        const bool pooled = l <= 2;                          // layers 3 and 2 read a pooled map
+        LpConvArgs a = {};
+        a.in = grad[l];
+        a.w = bw[l];
+        a.out = pooled ? gpool[l - 1] : grad[l - 1];
+        a.tap = taps[l - 1];
+        a.n_stride = n_stride;
+        a.n_off = n_off;
+        a.N = NQ;
+        a.Hi = p.h[l];                                       // stride 1, k - 1 - pad = pad: input and output sizes agree
+        a.Wi = p.w[l];
+        a.Cin = LP_COUT[l];
+        a.Ho = p.h[l];
+        a.Wo = p.w[l];
+        a.Cout = LP_CIN[l];
+        a.ks = LP_KS[l];
+        a.stride = 1;
+        a.pad = LP_PAD[l];
+        a.Kpad = lp_bwd_pack_k(l + 1);
+        a.M = NQ * p.h[l] * p.w[l];
+        a.flags = flags;
+        const unsigned blocks = (unsigned)((a.M + LP_BM - 1) / LP_BM) * (unsigned)(a.Cout / LP_BN);
+        if (pooled) {
+            hipLaunchKernelGGL(lpips_conv_kernel<LP_BWD_POOL>, dim3(blocks), dim3(LP_THREADS), 0, s, a);
+            const int t = l - 1, C4 = LP_COUT[t] / 4;        // the tap in front of the pool
+            const size_t total = (size_t)NQ * p.h[t] * p.w[t] * C4;
+            hipLaunchKernelGGL(lpips_pool_bwd_kernel, dim3((unsigned)((total + LP_THREADS - 1) / LP_THREADS)),
+                               dim3(LP_THREADS), 0, s, taps[t], (const float*)gpool[t], grad[t], p.h[t], p.w[t], p.ph[t],
+                               p.pw[t], C4, n_stride, n_off, total);
+        } else {
+            hipLaunchKernelGGL(lpips_conv_kernel<LP_BWD_TAP>, dim3(blocks), dim3(LP_THREADS), 0, s, a);
+        }
+    }
+    // layer 1, per wanted side
+    const unsigned cell_blocks = (unsigned)(((long long)((H + 3) / 4) * ((W + 3) / 4) + LP_THREADS - 1) / LP_THREADS);
+    int k = 0;
+    for (int side = 0; side < 2; ++side) {
+        float* g = side ? g_img1 : g_img0;
+        if (!g) continue;
+        // the truncation of img1 (refused above when its gradient is wanted) does not touch img0's clamp
+        hipLaunchKernelGGL(lpips_first_bwd_kernel, dim3(cell_blocks, 16, (unsigned)B), dim3(LP_THREADS), 0, s,
+                           (const float*)grad[0], weights->w1, side ? img1 : img0, g, H, W, p.h[0], p.w[0], ns, k, flags);
+        ++k;
+    }
+    return check_launch(name);
+}
+
 }  // namespace mobgs
 
 using namespace mobgs;
@@ -722,6 +1060,29 @@ int mobgs_lpips_alex_spatial(int B, int H, int W, const float* img0, const float
     }
     return lp_run("mobgs_lpips_alex_spatial", p, &q, B, H, W, img0, img1, weights, mask, flags, scratch, scratch_bytes, map,
                   out, nullptr, stream);
+}
+
+size_t mobgs_lpips_bwd_scratch_bytes(int B, int H, int W) {
+    LpPlan p;
+    LpBwdPlan q;
+    return lp_bwd_plan(B, H, W, p, q) ? q.bytes : 0;
+}
+
+int mobgs_lpips_bwd_pack_k(int layer) { return lp_bwd_pack_k(layer); }
+
+int mobgs_lpips_alex_bwd(int B, int H, int W, const float* img0, const float* img1, const MobgsLpipsWeights* weights,
+                         const MobgsLpipsBwdWeights* bwd_weights, int flags, const float* const* taps,
+                         const float* v_total, void* scratch, size_t scratch_bytes, float* g_img0, float* g_img1,
+                         float* const* tap_grads, void* stream) {
+    LpPlan p;
+    LpBwdPlan q;
+    if (!lp_bwd_plan(B, H, W, p, q)) {
+        set_error("mobgs_lpips_alex_bwd: B = %d, H = %d, W = %d outside 1 <= B <= %d, %d <= H, W <= %d, 2 B h1 w1 <= 2^30 "
+                  "(below 31 the second pool has no output)", B, H, W, LP_MAX_B, LP_MIN_EDGE, LP_MAX_EDGE);
+        return MOBGS_E_INVALID;
+    }
+    return lp_bwd_run("mobgs_lpips_alex_bwd", p, q, B, H, W, img0, img1, weights, bwd_weights, flags, taps, v_total, scratch,
+                      scratch_bytes, g_img0, g_img1, tap_grads, stream);
 }
 
 }  // extern "C"

@@ -12,7 +12,8 @@ both masked L1 terms -- as one forward and one backward kernel (csrc/flowloss.hi
 `exposure_ratio` is the statistic of train.py:482-491 on two flow maps (csrc/exposure.hip): no sort, no read-back.
 `entropy_loss` and `sparsity_loss` (utils/loss_utils.py:264-295) and `regularisation_terms` -- the depth, entropy and
 sparsity terms of train.py:651-655 with the PSNR of :622 next to them -- are one forward launch pair and one backward
-launch of csrc/regterms.hip.
+launch of csrc/regterms.hip.  `lpips_loss` (utils/loss_utils.py:228-230) is the perceptual term: LpipsAlex.loss, forward and
+backward on csrc/lpips.hip.
 """
 from __future__ import annotations
 
@@ -166,6 +167,13 @@ def flow_warp_loss(ori_image_tensor, latent_img_final_tensor, exp2mid_coord_fina
                                mid2exp_coord_final_tensor, latent_alpha_final_tensor.reshape(B, K, H, W),
                                d_alpha_tensor.reshape(B, H, W), combine_taps)
     return lambda_flow_loss * loss
+
+
+def lpips_loss(img1, img2, lpips_model):
+    """/root/reference/utils/loss_utils.py:228-230: the mean over the batch of the perceptual distance, inputs in [-1, 1]
+    as the reference's model takes them.  lpips_model: a mobgs_amd.lpips.LpipsAlex; the gradient reaches whichever image
+    requires one (csrc/lpips.hip, forward and backward)."""
+    return lpips_model.loss(img1, img2, normalize=False).mean()
 
 
 @torch.no_grad()

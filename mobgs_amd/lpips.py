@@ -11,11 +11,21 @@ pairs in one call, without the reference's models/ package, torchvision or a Dat
     s = model.spatial(pred, gt, mask)                   # LpipsSpatial: map [B,1,H,W] fp32, mean, masked_mean, ... float64
     m = model.forward_spatial(in0, in1)                 # PerceptualLoss(spatial=True).forward: [B,1,H,W] fp32
     v = model.forward_masked(in0, in1, mask)            # PNetLin.forward(mask=): a 0-dim fp32 tensor
+    l = model.loss(pred, gt, clamp=False, normalize=True)   # [B] fp32 WITH a gradient for pred and / or gt (a training loss)
 
 mirrors /root/reference/models/networks_basic.py:16-28 and :68-105 (spatial_average, upsample, PNetLin.forward,
 ScalingLayer), models/pretrained_networks.py:57-95 (the five slices of torchvision's alexnet().features),
-models/__init__.py:26-44, metrics.py:49-51 and dycheck_metrics.py:203-244.  Forward only, under no_grad; tensors must live
-on a HIP device.
+models/__init__.py:26-44, metrics.py:49-51 and dycheck_metrics.py:203-244.  Everything but loss() is forward only, under
+no_grad; tensors must live on a HIP device.
+
+THE LOSS (utils/loss_utils.py:228-230 of the reference, mobgs_amd.loss_utils.lpips_loss here): loss() is an autograd
+function over mobgs_lpips_alex (which stores the five ReLU maps) and mobgs_lpips_alex_bwd -- the distance heads' backward,
+the backward-data pass of layers 5 .. 2 on the forward's GEMM body, max-pool backward as a gather, the first layer into the
+image.  Its value has the bits of model(pred, gt).total.float(); the gradient goes to whichever of pred / gt requires one,
+only those images are walked, and it is bit-identical from run to run, whatever the batch and the chunking, and exactly
++0 for equal images.  Two deliberate conventions: where a feature vector is all zero the reference's autograd
+gives NaN (the derivative of sqrt at 0 times 0); here that pixel's gradient is 0.  Max-pool ties go to the first maximum in
+row-major order of the window, torch's rule.  The trunk and the heads are constants: they get no gradient.
 
 THE MAP is defined at H x W for every size: bilinear, align_corners=False, with the scale h / H (nn.Upsample(size=)).  The
 reference passes scale_factor = H / h, for which torch sizes the output as floor(h * scale_factor): H - 1 for some sizes
@@ -27,7 +37,8 @@ the classifier's, are ignored) and the reference's v0.1/alex.pth for the heads (
 packed once, at construction, into the K-major layout the convolution kernel reads.  The value a user compares with the
 published one rests on that trunk file (README, "UNPINNED").
 
-Not here: the VGG and SqueezeNet trunks, gradients, reduced precision.  forward() itself keeps refusing mask= and
+Not here: the VGG and SqueezeNet trunks, gradients of the spatial map and of the masked forms, gradients with respect to the
+trunk or the heads, reduced precision.  forward() itself keeps refusing mask= and
 spatial=True (NotImplementedError): forward_masked and forward_spatial are those calls.
 """
 from __future__ import annotations
@@ -100,6 +111,21 @@ def pack_conv_weight(weight: torch.Tensor, layer: int) -> torch.Tensor:
     return packed.contiguous()
 
 
+def bwd_pack_k(layer: int) -> int:
+    """Rows of layer `layer`'s weight packed for the backward-data pass (2 .. 5): Cout k k, a multiple of the K step."""
+    return COUT[layer - 1] * KS[layer - 1] ** 2
+
+
+def pack_conv_weight_bwd(weight: torch.Tensor, layer: int) -> torch.Tensor:
+    """[Cout, Cin, k, k] -> [Cout k k, Cin] for the backward-data pass of layers 2 .. 5 (include/mobgs_hip.h K24, backward):
+    row (ky k + kx) Cout + co holds weight[co, ci, k - 1 - ky, k - 1 - kx] in column ci.  Plain torch, any device."""
+    cout, cin, k = COUT[layer - 1], CIN[layer - 1], KS[layer - 1]
+    if layer < 2 or tuple(weight.shape) != (cout, cin, k, k):
+        raise ValueError(f"pack_conv_weight_bwd: layer {layer} (2 .. 5) needs [{cout}, {cin}, {k}, {k}], got "
+                         f"{tuple(weight.shape)}")
+    return weight.flip(2, 3).permute(2, 3, 0, 1).reshape(-1, cin).contiguous()
+
+
 def unpack_conv_weight(packed: torch.Tensor, layer: int) -> torch.Tensor:
     """The inverse of pack_conv_weight (the padding rows are dropped)."""
     cout, cin, k = COUT[layer - 1], CIN[layer - 1], KS[layer - 1]
@@ -168,6 +194,28 @@ def _mask(what, mask, like):
     return f32c(mask.detach())
 
 
+class _LpipsLoss(torch.autograd.Function):
+    """img0, img1 [B,3,H,W] fp32 contiguous -> the totals [B] fp32.  The forward keeps the five ReLU maps of all images."""
+
+    @staticmethod
+    def forward(ctx, img0, img1, model, flags):
+        a, b = img0.detach(), img1.detach()
+        out, taps, chunk = model._loss_forward(a, b, flags)
+        ctx.model, ctx.flags, ctx.chunk = model, flags, chunk
+        ctx.save_for_backward(a, b, *taps)
+        return out[:, 0].float()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, v_total):
+        a, b, *taps = ctx.saved_tensors
+        want0, want1 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (want0 or want1):
+            return None, None, None, None
+        g0, g1, _ = ctx.model._loss_backward(a, b, ctx.flags, taps, f32c(v_total), want0, want1, chunk=ctx.chunk)
+        return g0, g1, None, None
+
+
 class LpipsAlex:
     """The model, with its weights packed on one device.  Calls run on the current stream with 13 launches per chunk, no
     synchronisation, no read-back and no allocation that depends on the data: they can be recorded into a graph.  A pair's
@@ -194,6 +242,12 @@ class LpipsAlex:
             fields[f"b{l + 1}"] = self.biases[l].data_ptr()
             fields[f"lin{l + 1}"] = self.heads[l].data_ptr()
         self._record = _lib.MobgsLpipsWeights(**fields)
+        for l in range(2, 6):
+            if int(lib.mobgs_lpips_bwd_pack_k(l)) != bwd_pack_k(l) or bwd_pack_k(l) % K_STEP:
+                raise RuntimeError(f"LpipsAlex: the library packs layer {l}'s backward weight to "
+                                   f"{lib.mobgs_lpips_bwd_pack_k(l)} rows, this module to {bwd_pack_k(l)}")
+        self.bwd_weights = [pack_conv_weight_bwd(ws[l - 1], l).to(self.device) for l in range(2, 6)]
+        self._bwd_record = _lib.MobgsLpipsBwdWeights(**{f"w{l}": self.bwd_weights[l - 2].data_ptr() for l in range(2, 6)})
 
     @classmethod
     def from_files(cls, trunk, heads, device="cuda"):
@@ -233,6 +287,84 @@ class LpipsAlex:
                                            flags, ptr(scratch), nbytes, ptr(out[b0:b1]), tap_ptrs, stream()),
                       "mobgs_lpips_alex")
         return out
+
+    # ---- the loss: forward with the taps kept, backward through mobgs_lpips_alex_bwd --------------------------------------
+
+    def _loss_chunk(self, B, H, W):
+        """The largest number of pairs whose scratch (the larger of the two calls') and taps fit max_scratch_bytes."""
+        lib = _lib.load()
+        per_pair = 2 * 4 * sum(h * w * c for (h, w), c in zip(tap_sizes(H, W), COUT))
+        def need(n):
+            return max(int(lib.mobgs_lpips_scratch_bytes(n, H, W)), int(lib.mobgs_lpips_bwd_scratch_bytes(n, H, W))) + \
+                n * per_pair
+        n = B
+        while n > 1 and need(n) > self.max_scratch_bytes:
+            n = (n + 1) // 2
+        if int(lib.mobgs_lpips_bwd_scratch_bytes(n, H, W)) == 0:
+            raise ValueError(f"LpipsAlex: B = {n}, H = {H}, W = {W} is outside what mobgs_lpips_alex accepts")
+        return n
+
+    def _loss_forward(self, img0, img1, flags):
+        """-> (out [B, COLUMNS] float64, the five taps [2B,h,w,C] of the whole batch, the chunk), chunked like _run."""
+        lib = _lib.load()
+        B, _, H, W = img0.shape
+        dev = img0.device
+        n = self._loss_chunk(B, H, W)
+        out = torch.empty(B, COLUMNS, dtype=torch.float64, device=dev)
+        taps = [torch.empty(2 * B, h, w, c, dtype=torch.float32, device=dev) for (h, w), c in zip(tap_sizes(H, W), COUT)]
+        nbytes = int(lib.mobgs_lpips_scratch_bytes(n, H, W))
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            for b0 in range(0, B, n):
+                b1 = min(B, b0 + n)
+                tap_ptrs = (ctypes.c_void_p * 5)(*[t[2 * b0:2 * b1].data_ptr() for t in taps])
+                check(lib.mobgs_lpips_alex(b1 - b0, H, W, ptr(img0[b0:b1]), ptr(img1[b0:b1]), ctypes.byref(self._record),
+                                           flags, ptr(scratch), nbytes, ptr(out[b0:b1]), tap_ptrs, stream()),
+                      "mobgs_lpips_alex")
+        return out, taps, n
+
+    def _loss_backward(self, img0, img1, flags, taps, v_total, want0, want1, chunk=None, want_tap_grads=False):
+        """-> (g_img0, g_img1 [B,3,H,W] fp32 or None, tap gradients or None): one mobgs_lpips_alex_bwd call per chunk.  The
+        tap gradients ([n B, h, w, C] channel-last, n wanted sides per pair) are for tests and debugging."""
+        lib = _lib.load()
+        B, _, H, W = img0.shape
+        dev = img0.device
+        n = chunk or self._loss_chunk(B, H, W)
+        sides = int(want0) + int(want1)
+        g0 = torch.empty_like(img0) if want0 else None
+        g1 = torch.empty_like(img1) if want1 else None
+        tg = None
+        if want_tap_grads:
+            tg = [torch.empty(sides * B, h, w, c, dtype=torch.float32, device=dev)
+                  for (h, w), c in zip(tap_sizes(H, W), COUT)]
+        nbytes = int(lib.mobgs_lpips_bwd_scratch_bytes(n, H, W))
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            for b0 in range(0, B, n):
+                b1 = min(B, b0 + n)
+                tap_ptrs = (ctypes.c_void_p * 5)(*[t[2 * b0:2 * b1].data_ptr() for t in taps])
+                tg_ptrs = None if tg is None else (ctypes.c_void_p * 5)(*[t[sides * b0:sides * b1].data_ptr() for t in tg])
+                check(lib.mobgs_lpips_alex_bwd(b1 - b0, H, W, ptr(img0[b0:b1]), ptr(img1[b0:b1]),
+                                               ctypes.byref(self._record), ctypes.byref(self._bwd_record), flags, tap_ptrs,
+                                               ptr(v_total[b0:b1]), ptr(scratch), nbytes,
+                                               ptr(None if g0 is None else g0[b0:b1]),
+                                               ptr(None if g1 is None else g1[b0:b1]), tg_ptrs, stream()),
+                      "mobgs_lpips_alex_bwd")
+        return g0, g1, tg
+
+    def loss(self, pred, gt, *, clamp=False, normalize=True) -> torch.Tensor:
+        """LPIPS as a training loss: pred, gt [B,3,H,W] (or [3,H,W]) in [0, 1] (normalize=False: in [-1, 1], as
+        PerceptualLoss.forward takes them) -> [B] fp32 with the bits of self(pred, gt, clamp=clamp).total.float(), and a
+        gradient for whichever of pred / gt requires one.  clamp: both are clamped to [0, 1] first; the gradient passes
+        where 0 <= value <= 1.  There is no quantize here: the 8-bit truncation has no gradient.  13 launches forward, 12 or
+        13 backward per chunk, no synchronisation, no read-back, no allocation that depends on the data: a forward +
+        backward can be recorded into a graph (GraphedCallable)."""
+        device_tensor("LpipsAlex.loss", "the first image", pred), device_tensor("LpipsAlex.loss", "the second image", gt)
+        p = pred[None] if pred.dim() == 3 else pred
+        g = gt[None] if gt.dim() == 3 else gt
+        _pair("LpipsAlex.loss", p, g)                    # the forward's checks
+        flags = (UNIT_RANGE if normalize else 0) | (CLAMP if clamp else 0)
+        return _LpipsLoss.apply(f32c(g), f32c(p), self, flags)   # the reference's order: ground truth first
 
     def _run_spatial(self, img0, img1, mask, flags, want_map):
         """-> (out [B, SPATIAL_COLUMNS] float64, map [B,1,H,W] fp32 or None), chunked like _run."""
