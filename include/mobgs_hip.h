@@ -111,7 +111,10 @@ extern "C" {
  *                      per evaluated 8x8 quadrant) and v_colors[.., 6..] of those rows is written as 0.  Every other
  *                      output is BIT-identical (fma(0, v, acc) = acc).  The zeros are verified per staged entry (an entry
  *                      whose dead channels are not all +-0 takes the full body): a wrong statement about the DATA costs
- *                      nothing; a caller that does want d/d(colour 6..8) of such rows must leave this at 0.
+ *                      nothing; a caller that does want d/d(colour 6..8) of such rows must leave this at 0.  Only
+ *                      the quadrant kernel has such a body: the matrix-pipe (bwd_mfma) and block-walk kernels ignore the
+ *                      field, and mobgs_amd's compositing nodes write the zeros themselves after the reduction, for every static
+ *                      row (also one whose dead channels are not zero, where the quadrant kernel returns the gradient).
  *   cover_slots        (round 6) mobgs_raster_bwd / mobgs_raster_bwd_decode, default 0 / -1 = off.  1: the caller did NOT
  *                      zero-fill grad_slots (108 MB at 1352x1014 / 300 k splats: a 15-us fill per render, 9 of them per
  *                      blurry view) -- the kernel writes the slot of EVERY entry of its lists, zeros where no pixel blended

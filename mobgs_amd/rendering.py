@@ -703,16 +703,27 @@ def _lists_total_addr(tl) -> int:
 _path_bits_cache = {}
 
 
-def _raster_path_bits(D: int, nt: int) -> int:
-    """mobgs_raster_path(D, 0, nt, tuning) -- which kernels a plain pass takes -- cached per (D, grid, policy fields): the
-    backward node asks once per call, and a ctypes call + a pointer object cost the host ~5 us each time."""
-    key = (int(D), int(nt), tuning.heavy_tile_len, tuning.bwd_mfma, tuning.bwd_block_walk, tuning.block_walk)
+def _raster_path_bits(D: int, nt: int, class_filter: int = 0) -> int:
+    """mobgs_raster_path(D, class_filter, nt, tuning) -- which kernels a plain (class) pass takes -- cached per (D, grid,
+    policy fields): the backward node asks once per call, and a ctypes call + a pointer object cost the host ~5 us each time."""
+    key = (int(D), int(nt), tuning.heavy_tile_len, tuning.bwd_mfma, tuning.bwd_block_walk, tuning.block_walk, class_filter)
     bits = _path_bits_cache.get(key)
     if bits is None:
         if len(_path_bits_cache) > 256:
             _path_bits_cache.clear()
-        bits = _path_bits_cache[key] = int(_lib_().mobgs_raster_path(int(D), 0, int(nt), tuning.ref()))
+        bits = _path_bits_cache[key] = int(_lib_().mobgs_raster_path(int(D), class_filter, int(nt), tuning.ref()))
     return bits
+
+
+def _zero_dead_channels(v_colors, static_rows, D, bits):
+    """MobgsTuning.static_rows: v_colors[.., 6..8] of the static rows of a 10-channel pass is returned as 0.  Only the
+    quadrant backward kernel has the short blend body that leaves those sums at their cleared zeros; the matrix-pipe and
+    block-walk kernels (bits & 3 != 0) never read the field and return the real gradient, so the zeros are written here --
+    whatever the rows hold: the quadrant kernel still returns the real gradient of a static row whose dead channels are
+    not zero, these arms do not (found by tests/test_gpu_raster_kernels.py; the selection of the benchmark's grid is the quadrant kernel: no extra
+    launch there)."""
+    if static_rows > 0 and D == 10 and (bits & 3) != 0:
+        v_colors[:, :static_rows, 6:9] = 0.0
 
 
 def _refuse_token(colors, packed, who):
@@ -1135,6 +1146,7 @@ class _Rasterize(torch.autograd.Function):
                                 (C, N, channels, has_extra, width, height), tn, cover)
             v_means2d, v_conics, v_opac, v_colors, v_extra = _reduce_slots(tl, records, slots, flag_source, C, N, channels,
                                                                            has_extra)
+            _zero_dead_channels(v_colors, tn.static_rows, D, _raster_path_bits(D, nt))
         v_bg = None
         if ctx.bg_needs_grad:
             v_bg = (v_render * (1.0 - alphas).unsqueeze(-1)).sum(dim=(1, 2))
@@ -1348,6 +1360,9 @@ class _RasterizeClasses(torch.autograd.Function):
                            width, height)
         # (any_record: the lists' total -- zero when an arena overflowed without a host in the loop: no slot is read then)
         v_means2d, v_conics, v_opac, v_colors, v_extra = _reduce_slots(tl, records, slots, "total", C, N, channels, True)
+        if (mask >> 1) & 1:   # (only the static class pass touches the static rows' sums)
+            _zero_dead_channels(v_colors, min(ctx.static_rows, Ns) if STATIC_ROWS else 0, D,
+                                _raster_path_bits(D, tl.C * tl.tile_w * tl.tile_h, 1))
         return (v_means2d, v_conics, _fold_cameras(v_colors, colors_per_camera, C),
                 _fold_cameras(v_opac, opac_per_camera, C), v_extra, None, None, None, None, None, None, None, None, None)
 
