@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <atomic>
+
 #include "../../include/mobgs_hip.h"
 
 #define MOBGS_WAVE 64
@@ -19,6 +21,17 @@ inline int check_launch(const char* what) {
         return MOBGS_E_LAUNCH;
     }
     return MOBGS_OK;
+}
+
+// Host: lets kernel `fn` take `bytes` of dynamic LDS.  hipFuncSetAttribute is per device, so `done` (one static word
+// per kernel at the call site) keeps one flag per device ordinal and the call is made once per (kernel, device).
+inline void grant_dynamic_lds(const void* fn, int bytes, std::atomic<unsigned long long>& done) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (done.load(std::memory_order_acquire) & bit) return;
+    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    done.fetch_or(bit, std::memory_order_release);
 }
 
 __host__ __device__ inline int record_stride(int channels) { return (6 + channels + 3) & ~3; }

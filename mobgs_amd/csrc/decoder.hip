@@ -94,19 +94,7 @@ decoder_fwd_kernel(int P, int CF, int has_depth, int width, const float* __restr
     }
 }
 
-__device__ inline float wave_sum_f(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-__device__ __forceinline__ void dec_wave_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // v_feat_hw [P, CF] is fully written (channels >= 10 get 0); v_alphas [P] written when has_depth;
 // v_rays [6,P] written when non-null; weight gradients go to w_partial [gridDim.x, NRED] (summed by the next kernel).
@@ -279,13 +267,13 @@ decoder_bwd_kernel(int P, int CF, int has_depth, int width, const float* __restr
             }
         }
         // g_w1 += vh^T x over this wave's 64 pixels (pixels past the end contribute vh = 0)
-        dec_wave_fence();  // the previous iteration's operand reads are done
+        wave_lds_fence();  // the previous iteration's operand reads are done
         reinterpret_cast<float4*>(s_a[wv][lane])[0] = make_float4(vh[0], vh[1], vh[2], vh[3]);
         reinterpret_cast<float4*>(s_a[wv][lane])[1] = make_float4(vh[4], vh[5], 0.f, 0.f);
         reinterpret_cast<float4*>(s_b[wv][lane])[0] = make_float4(x[0], x[1], x[2], x[3]);
         reinterpret_cast<float4*>(s_b[wv][lane])[1] = make_float4(x[4], x[5], x[6], x[7]);
         reinterpret_cast<float4*>(s_b[wv][lane])[2] = make_float4(x[8], x[9], x[10], x[11]);
-        dec_wave_fence();
+        wave_lds_fence();
 #pragma unroll
         for (int s4 = 0; s4 < 16; ++s4) {
             const int px = 4 * s4 + kq;
@@ -303,7 +291,7 @@ decoder_bwd_kernel(int P, int CF, int has_depth, int width, const float* __restr
     }
 #pragma unroll
     for (int k = 0; k < NACC; ++k) {
-        const float sum = wave_sum_f(gw[k]);
+        const float sum = wave_sum(gw[k]);
         if (lane == 0) red[wv][72 + k] = sum;
     }
     __syncthreads();
@@ -342,7 +330,7 @@ __global__ void __launch_bounds__(256) decoder_wgrad_reduce_kernel(int nblocks, 
     w_partial += (size_t)first * NRED;
     float s = 0.f;
     for (int b = threadIdx.x; b < count; b += 256) s += w_partial[(size_t)b * NRED + k];
-    s = wave_sum_f(s);
+    s = wave_sum(s);
     __shared__ float red[4];
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();

@@ -5,6 +5,7 @@
 // so a fused and a separate decode give bit-identical images.
 #pragma once
 #include "common.h"
+#include "wave_shared.h"
 
 namespace mobgs {
 
@@ -225,8 +226,7 @@ __device__ inline void wgrad_column_sum(const WgradFinish& f, int k, int img) {
     const float* wp = f.w_partial + (size_t)first * WGRAD_NRED;
     float s = 0.f;
     for (int b = threadIdx.x; b < count; b += 256) s += wp[(size_t)b * WGRAD_NRED + k];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    MOBGS_WAVE_FOLD(s, MOBGS_WAVE_ADD);
     __shared__ float wgrad_red[4];
     if ((threadIdx.x & 63) == 0) wgrad_red[threadIdx.x >> 6] = s;
     __syncthreads();

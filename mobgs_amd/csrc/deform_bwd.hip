@@ -19,7 +19,6 @@
 //               (deterministic: no float atomics).
 // All GEMMs are v_mfma_f32_32x32x2_f32: exact fp32 products and accumulation (bitwise an fmaf chain), the vector
 // fp32 rate (157 TFLOP/s on MI355X) without spending VALU issue slots on it.
-#include <atomic>
 
 #include "common.h"
 
@@ -549,16 +548,6 @@ __global__ void __launch_bounds__(256) mlp_grad_reduce_kernel(int n_part, const 
     out[i] = (s0 + s1) + (s2 + s3);
 }
 
-// hipFuncSetAttribute is per device: one flag per (kernel, device ordinal)
-static void allow_dynamic_lds(const void* fn, int bytes, std::atomic<unsigned long long>& done) {
-    int dev = 0;
-    hipGetDevice(&dev);
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (done.load(std::memory_order_acquire) & bit) return;
-    hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    done.fetch_or(bit, std::memory_order_release);
-}
-
 }  // namespace mobgs
 
 using namespace mobgs;
@@ -575,7 +564,7 @@ int mobgs_deform_mlp_fwd(int N, const float* feat, const float* pts, const float
     }
     if (N == 0) return MOBGS_OK;
     static std::atomic<unsigned long long> attr_done{0};
-    allow_dynamic_lds(reinterpret_cast<const void*>(deform_mlp_fwd_kernel), (int)sizeof(FwdLds), attr_done);
+    grant_dynamic_lds(reinterpret_cast<const void*>(deform_mlp_fwd_kernel), (int)sizeof(FwdLds), attr_done);
     const int tiles = (N + TP - 1) / TP;
     const int grid = tiles < 256 ? tiles : 256;
     hipLaunchKernelGGL(deform_mlp_fwd_kernel, dim3(grid), dim3(512), sizeof(FwdLds), (hipStream_t)stream, N, tiles, feat,
@@ -606,7 +595,7 @@ int mobgs_deform_mlp_bwd(int N, const float* feat, const float* pts, const float
         return MOBGS_OK;
     }
     static std::atomic<unsigned long long> attr_done{0};
-    allow_dynamic_lds(reinterpret_cast<const void*>(deform_mlp_bwd_kernel), (int)sizeof(BwdLds), attr_done);
+    grant_dynamic_lds(reinterpret_cast<const void*>(deform_mlp_bwd_kernel), (int)sizeof(BwdLds), attr_done);
     const int tiles = (N + TP - 1) / TP;
     const int grid = mobgs_deform_mlp_bwd_blocks(N);
     MlpWeights Wt{W0t, b0, W1t, b1, W0, W1, W2pad};

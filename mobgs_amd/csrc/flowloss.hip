@@ -181,12 +181,6 @@ __device__ __forceinline__ float from_left(float v, int lane) {
     return lane == 0 ? 0.f : r;
 }
 
-__device__ __forceinline__ void fl_wave_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // Per-wave queue of stray contributions (address of channel 0 + the three channel values).  What an atomic costs here
 // is the INSTRUCTION, not the lane (measured: the backward pass's time follows the number of atomic instructions
 // issued, one lane active or sixty-four): the few contributions per row that no neighbour absorbs -- the right-hand
@@ -200,7 +194,7 @@ struct StrayQueue {
     size_t plane;
 
     __device__ __forceinline__ void drain(int lane) {
-        fl_wave_fence();
+        wave_lds_fence();
         for (int i = lane; i < count; i += 64) {
             float* a = addr[i];
 #pragma unroll
@@ -210,7 +204,7 @@ struct StrayQueue {
             }
         }
         count = 0;
-        fl_wave_fence();
+        wave_lds_fence();
     }
     __device__ __forceinline__ void push(bool p, float* a, float v0, float v1, float v2, int lane) {
         const unsigned long long m = __builtin_amdgcn_ballot_w64(p);

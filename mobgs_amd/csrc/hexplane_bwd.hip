@@ -23,10 +23,10 @@
 //             run per touched cell instead of one per point, 34 M atomics instead of 230 M at 100 k points.
 //
 // Like torch's (and round 1's) formulation the result is a floating-point sum in an order that is not fixed.
-#include <atomic>
 
 #include "common.h"
 #include "hexplane.h"
+#include "wave_shared.h"
 
 namespace mobgs {
 
@@ -129,8 +129,7 @@ __global__ void __launch_bounds__(1024) hex_scan_blocks_kernel(int n, const int*
     __shared__ int red[16];
     const int i = blockIdx.x * 1024 + threadIdx.x;
     int v = i < n ? count[i] : 0;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    MOBGS_WAVE_FOLD(v, MOBGS_WAVE_ADD);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -179,16 +178,6 @@ __global__ void __launch_bounds__(1024) hex_scan_final_kernel(int n, const int* 
     }
     if (i < n) start[i] = block_sums[blockIdx.x] + buf[threadIdx.x] - v;
     if (i == n - 1) start[n] = block_sums[blockIdx.x] + buf[threadIdx.x];
-}
-
-__device__ inline float half_wave_sum(float v) {
-    // sum over the 32 lanes of a half-wave (the 32 channels of one point)
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, false));
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, false));
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xF, 0xF, false));
-    v += __shfl_xor(v, 16, 64);
-    return v;
 }
 
 // ---- pass 1: per-point rows into the region lists; point / time gradients ---------------------------------------
@@ -336,15 +325,6 @@ hex_pass2_kernel(int n_entries, PlaneSet planes, CellMap cm, PlaneGradSet gplane
     flush();
 }
 
-static void allow_lds(const void* fn, int bytes, std::atomic<unsigned long long>& done) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (done.load(std::memory_order_acquire) & bit) return;
-    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    done.fetch_or(bit, std::memory_order_release);
-}
-
 }  // namespace mobgs
 
 using namespace mobgs;
@@ -416,8 +396,8 @@ int mobgs_hexplane_bwd(int N, const float* pts, const float* times, const float*
     const int n_blocks = (N + PB - 1) / PB;
     const size_t hot_bytes = sizeof(int) * (size_t)cm.hot_total;
     static std::atomic<unsigned long long> done_c{0}, done_p{0};
-    allow_lds(reinterpret_cast<const void*>(hex_count_kernel), (int)sizeof(int) * HOT_MAX, done_c);
-    allow_lds(reinterpret_cast<const void*>(hex_pass1_kernel), (int)sizeof(int) * HOT_MAX, done_p);
+    grant_dynamic_lds(reinterpret_cast<const void*>(hex_count_kernel), (int)sizeof(int) * HOT_MAX, done_c);
+    grant_dynamic_lds(reinterpret_cast<const void*>(hex_pass1_kernel), (int)sizeof(int) * HOT_MAX, done_p);
     hipLaunchKernelGGL(hex_count_kernel, dim3(n_blocks), dim3(WG), hot_bytes, st, N, pts, times, aabb, ps, cm, S.count);
     const int nb = (cm.total + 1023) / 1024;
     hipLaunchKernelGGL(hex_scan_blocks_kernel, dim3(nb), dim3(1024), 0, st, cm.total, S.count, S.block_sums);

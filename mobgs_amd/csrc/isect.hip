@@ -18,6 +18,7 @@
 // and removes ~half of the intersections on anisotropic scenes.  The test is conservative (margin on the
 // threshold); with culling off the lists are exactly upstream's.
 #include "isect_launch.h"
+#include "wave_shared.h"
 
 namespace mobgs {
 
@@ -98,10 +99,7 @@ __device__ inline int lookback_exclusive(uint64_t* status, int chunk, int aggreg
                 const int first = is_prefix ? __builtin_ctzll(is_prefix) : 64;
                 const uint64_t needed = first >= 63 ? ~0ull : ((2ull << first) - 1);
                 if (not_ready & needed) continue;  // a needed predecessor has not published yet: look again
-                int v = lane <= first ? (int)(uint32_t)w : 0;
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-                excl += v;
+                excl += wave_sum(lane <= first ? (int)(uint32_t)w : 0);
                 if (first < 64) break;
                 top -= 64;
             }
@@ -491,8 +489,7 @@ __global__ void __launch_bounds__(TSCAN_THREADS) tile_scan_kernel(int nt, const 
         }
         carry += total;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mx = max(mx, __shfl_xor(mx, off, 64));
+    MOBGS_WAVE_FOLD(mx, max);
     if ((threadIdx.x & 63) == 0) smax[threadIdx.x >> 6] = mx;
     __syncthreads();
     int longest = 0;
@@ -617,12 +614,6 @@ __device__ __forceinline__ void cmpx(uint64_t* a, int lo, int hi, int n) {
     }
 }
 
-__device__ __forceinline__ void wave_lds_order() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // steps j = j_first .. 1 (halving) inside every 128-chunk owned by this wave; no workgroup barrier
 __device__ __forceinline__ void local_halving_steps(uint64_t* a, int n, int n2, int j_first, int wave, int nwaves,
                                                     int lane) {
@@ -631,7 +622,7 @@ __device__ __forceinline__ void local_halving_steps(uint64_t* a, int n, int n2, 
             const int blk = lane / j, l = lane - blk * j;
             const int lo = c + blk * 2 * j + l;
             cmpx(a, lo, lo + j, n);
-            wave_lds_order();
+            wave_lds_fence();
         }
     }
 }
@@ -648,12 +639,12 @@ __device__ inline void bitonic_sort_lds(uint64_t* a, int n) {
             const int hk = k >> 1;
             const int blk = lane / hk, l = lane - blk * hk;
             cmpx(a, c + blk * k + l, c + blk * k + (k - 1 - l), n);
-            wave_lds_order();
+            wave_lds_fence();
             for (int j = k >> 2; j >= 1; j >>= 1) {
                 const int b2 = lane / j, l2 = lane - b2 * j;
                 const int lo = c + b2 * 2 * j + l2;
                 cmpx(a, lo, lo + j, n);
-                wave_lds_order();
+                wave_lds_fence();
             }
         }
     }
@@ -762,15 +753,12 @@ __device__ inline int radix_sort_long(const uint64_t* __restrict__ seg, int n, R
             rank[r] = 0;
             int before = 0;
             if (valid) before = sh.cnt[wv][d];  // every peer reads the same word before the leader updates it
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
+            wave_lds_fence();
             if (valid) {
                 rank[r] = before + __builtin_popcountll(peers & lt);
                 if ((peers & lt) == 0ull) sh.cnt[wv][d] = before + __builtin_popcountll(peers);
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_fence();
         }
         __syncthreads();
         // byte totals -> offsets (byte-major, wave-minor); a byte holding all n entries makes the pass a no-op
@@ -849,10 +837,6 @@ __device__ inline int radix_sort_long(const uint64_t* __restrict__ seg, int n, R
 //   d = 1, 2: quad_perm;  d = 4: row_half_mirror (l -> 7 - l) then the quad reversed;  d = 8: row_ror:8;
 //   d = 16 / 32: v_permlane16_swap / v_permlane32_swap of the register with itself leave the partner row / half in one of
 //   the two results, picked by the lane's own bit.
-template <int CTRL>
-__device__ __forceinline__ uint32_t dpp_mov(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false);
-}
 __device__ __forceinline__ uint32_t lane_xor32(uint32_t v, int d, int lane) {
     if (d == 1) return dpp_mov<0xB1>(v);
     if (d == 2) return dpp_mov<0x4E>(v);
@@ -1350,8 +1334,7 @@ __global__ void __launch_bounds__(TSCAN_THREADS) tile_finish_kernel(int nt, cons
         for (int i = threadIdx.x; i < FIN_LDS_TILES; i += TSCAN_THREADS) s_len[i] = tile_total(tile_count, cstride, i);
         __syncthreads();
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mx = max(mx, __shfl_xor(mx, off, 64));
+    MOBGS_WAVE_FOLD(mx, max);
     if ((threadIdx.x & 63) == 0) smax[threadIdx.x >> 6] = mx;
     __syncthreads();
     int longest = 0;

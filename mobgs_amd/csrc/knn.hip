@@ -19,6 +19,7 @@
 // loads and read back as broadcasts, every lane updating its sorted best-3 in registers (the update is a no-op for
 // lanes that did not need the box).
 #include "common.h"
+#include "wave_shared.h"
 
 namespace mobgs {
 
@@ -40,17 +41,6 @@ __device__ __forceinline__ float box_dist2(float px, float py, float pz, const f
     const float ey = fmaxf(fmaxf(lo.y - py, py - hi.y), 0.f);
     const float ez = fmaxf(fmaxf(lo.z - pz, pz - hi.z), 0.f);
     return (ex * ex + ey * ey) + ez * ez;
-}
-
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v = fminf(v, __shfl_xor(v, s, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v = fmaxf(v, __shfl_xor(v, s, 64));
-    return v;
 }
 
 // One workgroup (4 waves) per super-box; wave w reduces boxes 4w .. 4w+3 of it, lane l rows l, l+64, l+128, l+192 of a box.

@@ -412,12 +412,9 @@ __global__ void __launch_bounds__(LP_THREADS) lpips_upsample_kernel(LpUpArgs a) 
             s_map += (double)val;
         }
     }
-#pragma unroll
-    for (int off = MOBGS_WAVE / 2; off > 0; off >>= 1) {
-        s_mm += __shfl_xor(s_mm, off, MOBGS_WAVE);
-        s_m += __shfl_xor(s_m, off, MOBGS_WAVE);
-        s_map += __shfl_xor(s_map, off, MOBGS_WAVE);
-    }
+    s_mm = wave_sum(s_mm);
+    s_m = wave_sum(s_m);
+    s_map = wave_sum(s_map);
     if (lane == 0) {
         s_wave[3 * wave] = s_mm;
         s_wave[3 * wave + 1] = s_m;

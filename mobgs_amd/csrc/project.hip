@@ -10,6 +10,7 @@
 
 #include "isect_launch.h"
 #include "prep_shared.h"
+#include "wave_shared.h"
 
 namespace mobgs {
 
@@ -260,12 +261,6 @@ project_fwd_kernel(int N, const float* __restrict__ means, const float* __restri
 // ---------------------------------------------------------------------------------------------------
 // backward
 // ---------------------------------------------------------------------------------------------------
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // PREPB (mobgs_project_prep_bwd_fused, one camera): the thread hands its splat's state cotangents -- in registers -- to
 // the prep backward (prep_shared.h prep_bwd_apply: the arithmetic of prep_bwd_kernel, bit for bit) instead of storing
 // v_means / v_quats / v_scales for a second launch to read back; the leaf gradients leave this kernel.

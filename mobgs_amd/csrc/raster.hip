@@ -538,44 +538,8 @@ raster_fwd_blocks_kernel(int n_tiles_total, int n_groups, int tile_w, int tile_h
 // ---------------------------------------------------------------------------------------------------
 // backward, stage 1: per-(tile, splat) gradient records
 // ---------------------------------------------------------------------------------------------------
-// Wave-wide sum of NVP per-lane values with the cross-lane hardware of gfx950, no LDS traffic, no selects:
-//   1. v_permlane32_swap pairs component i with i+NVP/2: one swap + one add leaves the sum over lane bit 5 of
-//      the low-half components in lanes 0-31 and of the high-half components in lanes 32-63;
-//   2. v_permlane16_swap does the same for lane bit 4 (odd/even rows of 16 lanes);
-//   3. the NVP/4 survivors are all-reduced inside each 16-lane row with four DPP adds
-//      (quad_perm xor 1, quad_perm xor 2, row_half_mirror, row_ror:8).
-// Afterwards every lane of row r (= lane >> 4) holds, in v[0 .. NVP/4), the wave totals of components
-//   (r >> 1) * NVP/2 + (r & 1) * NVP/4 + k.
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float v) {
-    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
-}
-__device__ __forceinline__ float row_allreduce(float v) {
-    v = dpp_add<0xB1>(v);   // quad_perm:[1,0,3,2]
-    v = dpp_add<0x4E>(v);   // quad_perm:[2,3,0,1]
-    v = dpp_add<0x141>(v);  // row_half_mirror
-    v = dpp_add<0x128>(v);  // row_ror:8
-    return v;
-}
-template <int NVP>
-__device__ __forceinline__ void wave_reduce_components(float (&v)[NVP]) {
-    static_assert(NVP >= 8 && (NVP & (NVP - 1)) == 0, "NVP must be a power of two >= 8");
-#pragma unroll
-    for (int i = 0; i < NVP / 2; ++i) {
-        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[i]), __float_as_uint(v[i + NVP / 2]), false,
-                                                        false);
-        v[i] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-    }
-#pragma unroll
-    for (int i = 0; i < NVP / 4; ++i) {
-        const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[i]), __float_as_uint(v[i + NVP / 4]), false,
-                                                        false);
-        v[i] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-    }
-#pragma unroll
-    for (int i = 0; i < NVP / 4; ++i) v[i] = row_allreduce(v[i]);
-}
-
+// (wave_reduce_components, wave_reduce_pair, row_allreduce: wave_shared.h)
+//
 // NVP = 16: the same two swap stages, then HALVING steps inside each 16-lane row instead of four all-reduces of
 // four registers: a DPP add written under a bank mask lets the two halves of a row keep different components, so
 // 4 registers -> 2 (row_ror:8, lanes 8-15 take the partner register) -> 1 (row_half_mirror, banks 1/3 take the
@@ -672,18 +636,6 @@ __device__ __forceinline__ float wave_reduce16_scatter(float (&v)[N]) {
         : "=&v"(u0), "=&v"(u1), "=&v"(w), "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]),
           "+v"(v[7]), "+v"(v[8]), "+v"(v[9]), "+v"(v[10]), "+v"(v[11]), "+v"(v[12]), "+v"(v[13]), "+v"(v[14]), "+v"(v[15]));
     return w;
-}
-
-// One or two further components (NV = 17, 18: e.g. 9 features + 2 flow channels + depth) next to the sixteen above:
-// one permlane32 swap + add puts the bit-5 sums of e0 into lanes 0-31 and of e1 into lanes 32-63, four DPP adds
-// all-reduce every 16-lane row, one permlane16 swap of the register with itself + add folds the two rows of each
-// half: 8 instructions, against 80 for the generic 32-component reduction such a kernel used before.  Afterwards
-// lanes 0-31 hold the wave total of e0, lanes 32-63 that of e1.
-__device__ __forceinline__ float wave_reduce_pair(float e0, float e1) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(e0), __float_as_uint(e1), false, false);
-    float x = row_allreduce(__uint_as_float(r[0]) + __uint_as_float(r[1]));
-    const auto q = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return __uint_as_float(q[0]) + __uint_as_float(q[1]);
 }
 
 // One (pixel, splat) pair of the backward pass: rebuilds the transmittance in front of the splat, forms the
@@ -1071,8 +1023,7 @@ __device__ __forceinline__ void composite_bwd(int tile, int quad, int wv, int la
 #pragma unroll
     for (int k = 0; k < PPL; ++k) {
         int t = binf[k];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) t = max(t, __shfl_xor(t, off, 64));
+        MOBGS_WAVE_FOLD(t, max);
         topk[k] = __builtin_amdgcn_readfirstlane(t);
     }
     // ... and of the whole tile
@@ -1836,11 +1787,7 @@ slot_reduce16_kernel(int n_gauss, int channels, int has_extra, const int32_t* __
             acc[i] = dpp_add<0x124>(acc[i]);  // row_ror:4
             acc[i] = dpp_add<0x128>(acc[i]);  // row_ror:8
         } else if (SUBS == 2) {
-            // lane l of an 8-lane group with l ^ 4: row_half_mirror pairs l with 7 - l (other quarter!), so use the
-            // two masked shifts instead: banks {0, 2} take lane + 4, banks {1, 3} lane - 4
-            const float up = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc[i]), 0x104, 0xF, 0x5, true));
-            const float dn = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc[i]), 0x114, 0xF, 0xA, true));
-            acc[i] = acc[i] + (up + dn);
+            acc[i] = dpp_add_xor4(acc[i]);
         }
     }
     if (!live || sub != 0) return;

@@ -322,12 +322,6 @@ struct QuadState {
     }
 };
 
-__device__ __forceinline__ int wave_max_i(int t) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) t = max(t, __shfl_xor(t, off, 64));
-    return __builtin_amdgcn_readfirstlane(t);
-}
-
 // =====================================================================================================================
 // (1) one wave per tile, four pixels per lane
 // =====================================================================================================================
@@ -371,7 +365,7 @@ __device__ __forceinline__ void composite_bwd_mfma(
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
         qs[k].load(k, lane, cam, tx, ty, width, height, backgrounds, render_alphas, last_ids, v_render, v_alphas);
-        topk[k] = wave_max_i(qs[k].binf);
+        topk[k] = __builtin_amdgcn_readfirstlane(wave_max(qs[k].binf));
         top = max(top, topk[k]);
     }
     top = min(top, e - 1);
@@ -505,7 +499,7 @@ __device__ __forceinline__ void composite_bwd_team(
 
     QuadState<CD> qs;
     qs.load(quad, lane, cam, tx, ty, width, height, backgrounds, render_alphas, last_ids, v_render, v_alphas);
-    const int topq = wave_max_i(qs.binf);
+    const int topq = __builtin_amdgcn_readfirstlane(wave_max(qs.binf));
     if (lane == 0) sh.top[wv] = topq;
     __syncthreads();
     int top = max(max(sh.top[0], sh.top[1]), max(sh.top[2], sh.top[3]));

@@ -21,38 +21,10 @@
 
 namespace mobgs {
 
-constexpr float L_ALPHA_MIN = 1.f / 255.f;
-constexpr float L_ALPHA_MAX = 0.999f;
-constexpr float L_T_STOP = 1e-4f;
 constexpr int LPPL = 2;      // pixels per lane
 constexpr int LWAVES = 4;    // waves per workgroup = 2 tiles x 2 halves
 constexpr int LTILES = LWAVES / 2;   // tiles per workgroup
 constexpr int NL = 3;        // layers: 0 = all, 1 = static (flat id % N < Ns), 2 = dynamic
-
-__device__ inline void l_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-struct LEval {
-    float dx, dy, raw, alpha;   // raw = opacity * exp(-sigma), before the clamp
-    bool pass;
-};
-// identical instruction sequence to raster_shared.h's eval_splat (bit-identical alphas); A, B, C, L: the record's
-// exponent form (common.h, write_splat_record)
-__device__ __forceinline__ LEval l_eval(float gx, float gy, float A, float B, float C, float L, float px, float py) {
-    LEval e;
-    e.dx = gx - px;
-    e.dy = gy - py;
-    float s = __fmaf_rn(A * e.dx, e.dx, L);
-    s = __fmaf_rn(C * e.dy, e.dy, s);
-    s = __fmaf_rn(B * e.dx, e.dy, s);
-    e.raw = __builtin_amdgcn_exp2f(s);
-    e.alpha = fminf(L_ALPHA_MAX, e.raw);
-    e.pass = !(s > L || e.alpha < L_ALPHA_MIN);
-    return e;
-}
 
 struct LayerOut {
     float* render[NL];     // [C,H,W,CD] per layer (NULL when the layer is not requested)
@@ -75,12 +47,12 @@ struct LayerState {
 };
 
 template <int CD>
-__device__ __forceinline__ void layer_blend(LayerState<CD>& L, const LEval (&ev)[LPPL], const float (&col)[CD], int idx) {
+__device__ __forceinline__ void layer_blend(LayerState<CD>& L, const Eval (&ev)[LPPL], const float (&col)[CD], int idx) {
 #pragma unroll
     for (int k = 0; k < LPPL; ++k) {
         const bool pass = ev[k].pass && !L.done[k];
         const float nT = L.T[k] * (1.f - ev[k].alpha);
-        const bool stop = pass && (nT <= L_T_STOP);
+        const bool stop = pass && (nT <= T_STOP);
         L.done[k] = L.done[k] || stop;
         const bool blend = pass && !stop;
         const float w = blend ? ev[k].alpha * L.T[k] : 0.f;
@@ -148,7 +120,7 @@ raster_layers_fwd_kernel(int n_tiles_total, int n_groups, int tile_w, int tile_h
 
     for (int b = s; b < e; b += 64) {
         const int n = min(64, e - b);
-        l_fence();
+        wave_lds_fence();
         if (lane < n) {
             const int g = flatten_ids[b + lane];
             const float4* r = reinterpret_cast<const float4*>(records + (size_t)g * RS);
@@ -156,7 +128,7 @@ raster_layers_fwd_kernel(int n_tiles_total, int n_groups, int tile_w, int tile_h
             for (int q = 0; q < RQ; ++q) slab[wv][lane][q] = r[q];
             cls_of[wv][lane] = ((g % N) < Ns) ? 1 : 2;
         }
-        l_fence();
+        wave_lds_fence();
         bool all_done = false;
         for (int j = 0; j < n; ++j) {
             float rec[RS];
@@ -169,9 +141,9 @@ raster_layers_fwd_kernel(int n_tiles_total, int n_groups, int tile_w, int tile_h
                 rec[4 * q + 3] = v.w;
             }
             const int cls = __builtin_amdgcn_readfirstlane(cls_of[wv][j]);
-            LEval ev[LPPL];
+            Eval ev[LPPL];
 #pragma unroll
-            for (int k = 0; k < LPPL; ++k) ev[k] = l_eval(rec[0], rec[1], rec[2], rec[3], rec[4], rec[5], px, py[k]);
+            for (int k = 0; k < LPPL; ++k) ev[k] = eval_splat(rec[0], rec[1], rec[2], rec[3], rec[4], rec[5], px, py[k]);
             float col[CD];
 #pragma unroll
             for (int c = 0; c < CD; ++c) col[c] = rec[6 + c];
@@ -216,47 +188,6 @@ raster_layers_fwd_kernel(int n_tiles_total, int n_groups, int tile_w, int tile_h
 // ---------------------------------------------------------------------------------------------------
 // backward
 // ---------------------------------------------------------------------------------------------------
-template <int CTRL>
-__device__ __forceinline__ float l_dpp_add(float v) {
-    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
-}
-template <int NVP>
-__device__ __forceinline__ void l_wave_reduce(float (&v)[NVP]) {
-#pragma unroll
-    for (int i = 0; i < NVP / 2; ++i) {
-        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[i]), __float_as_uint(v[i + NVP / 2]), false,
-                                                        false);
-        v[i] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-    }
-#pragma unroll
-    for (int i = 0; i < NVP / 4; ++i) {
-        const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[i]), __float_as_uint(v[i + NVP / 4]), false,
-                                                        false);
-        v[i] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-    }
-#pragma unroll
-    for (int i = 0; i < NVP / 4; ++i) {
-        float x = v[i];
-        x = l_dpp_add<0xB1>(x);
-        x = l_dpp_add<0x4E>(x);
-        x = l_dpp_add<0x141>(x);
-        x = l_dpp_add<0x128>(x);
-        v[i] = x;
-    }
-}
-
-__device__ __forceinline__ float l_wave_allreduce(float v) {
-    auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-    r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-    v = l_dpp_add<0xB1>(v);
-    v = l_dpp_add<0x4E>(v);
-    v = l_dpp_add<0x141>(v);
-    v = l_dpp_add<0x128>(v);
-    return v;
-}
-
 template <int CD>
 struct LayerBwd {
     float T[LPPL], Tf[LPPL], va[LPPL], bgdot[LPPL], behind[LPPL];
@@ -267,7 +198,7 @@ struct LayerBwd {
 // XY0 = true (layer 0 only): the position gradient is ALSO accumulated in (e0, e1) -- the reference's
 // `viewspace_points.grad` is the means2d gradient of the combined render alone (:218-223, train.py:634-648)
 template <int CD, int NVP, bool XY0>
-__device__ __forceinline__ bool layer_grad(LayerBwd<CD>& B, const LEval (&ev)[LPPL], const float* rec, int idx,
+__device__ __forceinline__ bool layer_grad(LayerBwd<CD>& B, const Eval (&ev)[LPPL], const float* rec, int idx,
                                            bool has_bg, float (&g)[NVP], float& e0, float& e1) {
     // this kernel still accumulates the conic-weighted terms per pair: conic and 1 / opacity back from the record's
     // exponent form (uniform per entry)
@@ -295,7 +226,7 @@ __device__ __forceinline__ bool layer_grad(LayerBwd<CD>& B, const LEval (&ev)[LP
         v_alpha += B.Tf[k] * ra * B.va[k];
         if (has_bg) v_alpha -= B.Tf[k] * ra * B.bgdot[k];
         const float ov = ev[k].raw;
-        if (ov <= L_ALPHA_MAX) {
+        if (ov <= ALPHA_MAX) {
             const float v_sigma = -ov * v_alpha;
             const float dx = ev[k].dx, dy = ev[k].dy;
             const float gx = v_sigma * (co.ca * dx + co.cb * dy), gy = v_sigma * (co.cb * dx + co.cc * dy);
@@ -398,13 +329,11 @@ raster_layers_bwd_kernel(int n_tiles_total, int n_groups, int tile_w, int tile_h
             B[l].T[k] = B[l].Tf[k];
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) top = max(top, __shfl_xor(top, off, 64));
-    top = min(top, e - 1);
+    top = min(wave_max(top), e - 1);
 
     for (int hi = top; hi >= s; hi -= 64) {
         const int n = min(64, hi - s + 1);
-        l_fence();
+        wave_lds_fence();
         if (lane < n) {
             const int g = flatten_ids[hi - lane];
             const float4* r = reinterpret_cast<const float4*>(records + (size_t)g * RS);
@@ -416,7 +345,7 @@ raster_layers_bwd_kernel(int n_tiles_total, int n_groups, int tile_w, int tile_h
             slot_of[wv][lane] = keep_index(keep_scan, cum_tiles[g] + (ty - tr.y0) * (tr.x1 - tr.x0) + (tx - tr.x0));
             cls_of[wv][lane] = ((g % N) < Ns) ? 1 : 2;
         }
-        l_fence();
+        wave_lds_fence();
         for (int j = 0; j < n; ++j) {
             const int idx = hi - j;
             float rec[RS];
@@ -429,9 +358,9 @@ raster_layers_bwd_kernel(int n_tiles_total, int n_groups, int tile_w, int tile_h
                 rec[4 * q + 3] = v.w;
             }
             const int cls = __builtin_amdgcn_readfirstlane(cls_of[wv][j]);
-            LEval ev[LPPL];
+            Eval ev[LPPL];
 #pragma unroll
-            for (int k = 0; k < LPPL; ++k) ev[k] = l_eval(rec[0], rec[1], rec[2], rec[3], rec[4], rec[5], px, py[k]);
+            for (int k = 0; k < LPPL; ++k) ev[k] = eval_splat(rec[0], rec[1], rec[2], rec[3], rec[4], rec[5], px, py[k]);
             float g[NVP];
 #pragma unroll
             for (int i = 0; i < NVP; ++i) g[i] = 0.f;
@@ -444,9 +373,9 @@ raster_layers_bwd_kernel(int n_tiles_total, int n_groups, int tile_w, int tile_h
                 if (layer_mask & 4) any = layer_grad<CD, NVP, false>(B[2], ev, rec, idx, has_bg, g, dummy0, dummy1) || any;
             }
             if (__builtin_amdgcn_ballot_w64(any) == 0ull) continue;
-            l_wave_reduce<NVP>(g);
-            e0 = l_wave_allreduce(e0);
-            e1 = l_wave_allreduce(e1);
+            wave_reduce_components<NVP>(g);
+            e0 = wave_allreduce(e0);
+            e1 = wave_allreduce(e1);
             if (lane == 0)
                 *reinterpret_cast<float2*>(grad_xy0 + ((size_t)slot_of[wv][j] * 2 + half) * 2) = make_float2(e0, e1);
             constexpr int Q = NVP / 4;

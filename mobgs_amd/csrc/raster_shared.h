@@ -3,6 +3,7 @@
 // ONE instruction sequence for forward and backward, so both see bit-identical alphas.
 #pragma once
 #include "common.h"
+#include "wave_shared.h"
 
 namespace mobgs {
 
@@ -24,13 +25,6 @@ __device__ inline int scheduled_tile(const int32_t* tile_order, int n_groups, in
     if (group >= n_groups) return -1;
     const int tile = group * TILES_PER_WG + wv;
     return tile < n_tiles_total ? tile : -1;
-}
-
-__device__ inline void wave_lds_fence() {
-    // LDS operations of one wave execute in issue order; only the compiler has to be told
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // Optional restriction of a compositing pass to one class of splats: sel = 1 keeps flat ids with (id % N) < Ns

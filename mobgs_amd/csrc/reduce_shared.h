@@ -11,6 +11,7 @@
 //     block sums meet at barriers.  A block sum may be called again at once with the same LDS array: it ends with a barrier.
 #pragma once
 #include "common.h"
+#include "wave_shared.h"
 
 namespace mobgs {
 
@@ -41,14 +42,7 @@ __device__ __forceinline__ double rows_sum(const double* __restrict__ p, int row
     return block_sum<BLOCK / MOBGS_WAVE>(s, s_wave);
 }
 
-// ---- one wave: an xor butterfly (float or double) -----------------------------------------------------------------------
-template <class T>
-__device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-    for (int off = MOBGS_WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, MOBGS_WAVE);
-    return v;
-}
-
+// ---- one wave: wave_sum is the xor butterfly of wave_shared.h (float or double) -----------------------------------------
 // n values at p[0], p[stride], ...: lane l adds its run [l per, min(l per + per, n)), per = ceil(n / 64); wave_sum adds
 // the 64 lane sums
 __device__ __forceinline__ double wave_rows_sum(const double* __restrict__ p, int n, int stride, int lane) {

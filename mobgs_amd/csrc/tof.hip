@@ -144,11 +144,8 @@ __global__ void __launch_bounds__(TOF_BLOCK) tof_polyexp_kernel(TofPolyArgs a) {
         lo = fminf(lo, v);
         hi = fmaxf(hi, v);
     }
-#pragma unroll
-    for (int off = MOBGS_WAVE / 2; off > 0; off >>= 1) {
-        lo = fminf(lo, __shfl_xor(lo, off, MOBGS_WAVE));
-        hi = fmaxf(hi, __shfl_xor(hi, off, MOBGS_WAVE));
-    }
+    lo = wave_min(lo);
+    hi = wave_max(hi);
     if ((threadIdx.x & (MOBGS_WAVE - 1)) == 0) {
         s_lo[threadIdx.x / MOBGS_WAVE] = lo;
         s_hi[threadIdx.x / MOBGS_WAVE] = hi;
