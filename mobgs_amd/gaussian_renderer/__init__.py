@@ -850,6 +850,11 @@ def _get_flow_exposures(cam, stat_pc, dyn_pc, bg_color, deltas, mid):
     e2m = mid.means2d - sp.means2d                                 # [G,N,2]
     img12, alphas = sp.composite(torch.cat([cols, e2m], dim=-1), bg11)   # [G,H,W,12]
     rays = _rays_of(cam)
+    if torch.is_tensor(rays) and rays.requires_grad:
+        # a ray map with a graph (the reference's warped cameras): the decoder kernel writes one map gradient per image
+        # and ops.decode refuses a shared map that needs one, so every image gets its own copy, as ops._decode_args does
+        # for a shared c2w; autograd sums the G gradients through the expand
+        rays = rays.reshape(6, H, W).expand(G, 6, H, W).contiguous()
     outs = []
     # ONE decoder launch for the G images (same camera: shared rays); unbind, not [g]: one autograd node whose backward
     # stacks the G cotangents (a select per g zero-fills and copies the whole array G times)

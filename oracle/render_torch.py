@@ -64,6 +64,11 @@ def _time_tensor(x, like):
     return torch.as_tensor(x, dtype=like.dtype)
 
 
+def _ones_colour(cols):
+    """The ones colour of the reference's coverage passes, [N,1], in the dtype of the splats' colours (float64 runs)."""
+    return torch.ones(cols.shape[0], 1, dtype=cols.dtype)
+
+
 def _dyn_state(dyn_pc, time, max_time, delta):
     """tforpoly [Nd,1], quats (normalised) [Nd,4], means [Nd,3], colors [Nd,9] at time (+delta/max_time)."""
     trbf = dyn_pc.get_trbfcenter
@@ -109,7 +114,7 @@ def render(cam, stat_pc, dyn_pc, bg_color, get_static=False, get_dynamic=False, 
         d_img, _, _ = raster(d_means, d_quats, d_scales, d_opac, d_cols, bg[None], "RGB+ED")
         out["d_depth"] = d_img[..., -1]
         out["d_render"] = decode(d_img)
-        d_a, _, _ = raster(d_means, d_quats, d_scales, d_opac, torch.ones(d_cols.shape[0], 1), bg[0:1][None], "RGB")
+        d_a, _, _ = raster(d_means, d_quats, d_scales, d_opac, _ones_colour(d_cols), bg[0:1][None], "RGB")
         out["d_alpha"] = d_a[..., 0]
         out["d_means3d"] = d_means
 
@@ -142,7 +147,7 @@ def render(cam, stat_pc, dyn_pc, bg_color, get_static=False, get_dynamic=False, 
         s_img, _, _ = raster(s_means, s_quats, s_scales, s_opac, s_cols, bg[None], "RGB+ED")
         out["s_depth"] = rendered[..., -1]  # the reference slices the DECODED image here (:250) -> [3,H]
         out["s_render"] = decode(s_img)
-        s_a, _, _ = raster(s_means, s_quats, s_scales, s_opac, torch.ones(s_cols.shape[0], 1), bg[0:1][None], "RGB")
+        s_a, _, _ = raster(s_means, s_quats, s_scales, s_opac, _ones_colour(s_cols), bg[0:1][None], "RGB")
         out["s_alpha"] = s_a[..., 0]
 
     if delta_exposure is not None and get_flow:
@@ -175,7 +180,7 @@ def get_flow(cam, stat_pc, dyn_pc, bg_color, delta_exposure, rasterization=G.ras
                              backgrounds=bgs, viewmats=viewmat[None], Ks=K[None], width=W, height=H, packed=False,
                              render_mode=mode)
 
-    latent_alpha, _, _ = raster(exp_m, exp_q, d_scales, d_opac, torch.ones(exp_c.shape[0], 1), bg[0:1][None], "RGB")
+    latent_alpha, _, _ = raster(exp_m, exp_q, d_scales, d_opac, _ones_colour(exp_c), bg[0:1][None], "RGB")
     latent_alpha = latent_alpha[..., 0]
     mid_means = torch.cat((s_means, mid_m), 0)
     mid_quats = torch.cat((s_quats, mid_q), 0)

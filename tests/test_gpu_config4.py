@@ -39,16 +39,13 @@ def blce_mode(request):
     B.FUSED = old
 
 
-@pytest.mark.parametrize("blce_mode", ["fused", "graph"], indirect=True)
-def test_blurry_view_k9_blce_matches_reference_fixture(hip_device, blce_mode, kernel_selection):
-    """(also under the benchmark's kernel selection: conftest.kernel_selection)"""
-    from mobgs_amd import blce as B
+def blurry_view_run(dev, **batch_options):
+    """The blurry view of tests/golden/blurry_view.npz through render_blurry_batch (K = 9, BLCE), forward and backward, twice
+    -> (fx, cam, stat, dyn, kern, idx, pred, mid).  batch_options: further keyword arguments of render_blurry_batch."""
     from mobgs_amd.deblur import render_blurry_batch
     from mobgs_amd.distributed import SubframeShard
     from mobgs_amd.ops import LeafGradSink
-    assert B.GRAPH_CAPTURE
     fx = load("blurry_view")
-    dev = hip_device
     cam, stat, dyn, bg, w2c = scene_from_fixture(fx, dev)
     kern, idx = _kernel_from_fixture(fx, dev)
     cam.uid = idx
@@ -59,16 +56,16 @@ def test_blurry_view_k9_blce_matches_reference_fixture(hip_device, blce_mode, ke
             # second pass: zero gradients already in place (what distributed.FlatGradients.zero() leaves) -- every
             # backward kernel then ADDS into .grad itself (leaves, decoder weights, BLCE parameters)
             p.grad = None if rep == 0 else torch.zeros_like(p)
-        pred, mids = render_blurry_batch([cam], stat, dyn, bg, SubframeShard(1, 0), blce=kern, n_sub=9)
+        pred, mids = render_blurry_batch([cam], stat, dyn, bg, SubframeShard(1, 0), blce=kern, n_sub=9, **batch_options)
         mid = mids[0]
         with LeafGradSink(stat, dyn, extra=kern.model.get_params()):
             ((pred[0] * T("cot_v_pred")).sum() + (mid["depth"] * T("cot_v_depth")).sum()
              + (mid["d_alpha"] * T("cot_v_depth")).sum()).backward()
-    g = kern._graphed.get(idx)
-    if blce_mode == "graph":
-        assert g is not None and g is not False, "BLCE must run as a captured HIP graph here (no eager fallback)"
-    else:
-        assert g is None, "the fused kernels must have been used (no torch module call)"
+    return fx, cam, stat, dyn, kern, idx, pred, mid
+
+
+def check_blurry_view_fixture(fx, dev, cam, stat, dyn, kern, pred, mid):
+    """The prediction, the mid-frame outputs and every gradient of blurry_view_run against the reference's fixture."""
     # an alpha within an ulp of 1/255 is kept by one exp() and dropped by the other: such a pixel moves by ONE blend step
     # passed through the decoder -- derived from the decoder's weights and the splat colours' range
     # (helpers.decoded_flip_bound), not a flat 5e-3.  Observed: no flipped element (largest error 2.5e-5); allowed for 2e-4
@@ -100,6 +97,21 @@ def test_blurry_view_k9_blce_matches_reference_fixture(hip_device, blce_mode, ke
             close(p.grad, ref, 5e-3, 5e-4 * float(np.abs(ref).max()), f"BLCE grad {k}")
             n += 1
     assert n >= 20
+
+
+@pytest.mark.parametrize("blce_mode", ["fused", "graph"], indirect=True)
+def test_blurry_view_k9_blce_matches_reference_fixture(hip_device, blce_mode, kernel_selection):
+    """(also under the benchmark's kernel selection: conftest.kernel_selection)"""
+    from mobgs_amd import blce as B
+    assert B.GRAPH_CAPTURE
+    dev = hip_device
+    fx, cam, stat, dyn, kern, idx, pred, mid = blurry_view_run(dev)
+    g = kern._graphed.get(idx)
+    if blce_mode == "graph":
+        assert g is not None and g is not False, "BLCE must run as a captured HIP graph here (no eager fallback)"
+    else:
+        assert g is None, "the fused kernels must have been used (no torch module call)"
+    check_blurry_view_fixture(fx, dev, cam, stat, dyn, kern, pred, mid)
     kernel_selection.check()
 
 

@@ -6,6 +6,15 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
+def assert_grads_of_the_batch(got, ref, what):
+    """The yardstick of render_many()'s gradients against the accumulated gradients of the separate render() calls: equal to
+    the order of the sums over cameras (also imported by tests/test_gpu_reference_cameras.py for the ray-map arm)."""
+    sc = float(ref.abs().max())
+    assert got.shape == ref.shape, what
+    assert torch.allclose(got, ref, rtol=1e-4, atol=2e-5 * sc + 1e-12), \
+        f"{what}: max err {float((got - ref).abs().max()):.3e} of {sc:.3e}"
+
+
 @pytest.mark.parametrize("size,ns,nd", [((232, 120), 900, 500), ((512, 288), 20_000, 10_000),
                                         ((1352, 1014), 200_000, 100_000)])   # ... and BASELINE config #2's size
 def test_render_many_equals_separate_renders(hip_device, size, ns, nd):
@@ -46,16 +55,11 @@ def test_render_many_equals_separate_renders(hip_device, size, ns, nd):
         assert torch.equal(o["render"], r), f"image of sub-frame {k}"
         assert torch.equal(o["depth"], d), f"depth of sub-frame {k}"
     for i, (p, gr) in enumerate(zip(params, ref_g)):
-        sc = float(gr.abs().max())
-        assert torch.allclose(p.grad, gr, rtol=1e-4, atol=2e-5 * sc + 1e-12), \
-            f"leaf {i}: max err {float((p.grad - gr).abs().max()):.3e} of {sc:.3e}"
+        assert_grads_of_the_batch(p.grad, gr, f"leaf {i}")
     # the densification input of every sub-frame: the batch shares ONE [K,N,2] tensor, viewspace_grad() picks the row
     for k, (o, gr) in enumerate(zip(outs, ref_vs)):
         assert o["viewspace_points"].shape[0] == K and o["viewspace_index"] == k
-        got = viewspace_grad(o)
-        assert got.shape == gr.shape
-        sc = float(gr.abs().max())
-        assert torch.allclose(got, gr, rtol=1e-4, atol=2e-5 * sc + 1e-12), f"viewspace gradient of sub-frame {k}"
+        assert_grads_of_the_batch(viewspace_grad(o), gr, f"viewspace gradient of sub-frame {k}")
 
 
 def test_prep_of_k_instants_in_one_launch_equals_k_launches(hip_device):

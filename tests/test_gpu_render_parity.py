@@ -4,12 +4,11 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import close, leaf_map, load, psnr, render_loss, scene_from_fixture
+from helpers import (check_get_flow_fixture_outputs, check_get_flow_static_fixture_outputs,
+                     check_render_fixture_gradients, check_render_fixture_outputs, check_separate_calls_gradients, close,
+                     leaf_map, load, render_fixture_options, render_loss, scene_from_fixture)
 
 pytestmark = pytest.mark.gpu
-
-IMG_KEYS = ("render", "s_render", "d_render", "d_alpha", "s_alpha", "depth", "d_depth", "s_depth", "ori_flow",
-            "ori_coord_map")
 
 
 @pytest.mark.parametrize("name", ["render_lean", "render_train", "render_train_delta_flow"])
@@ -22,78 +21,13 @@ def test_render_matches_reference_fixture(hip_device, name, kernel_selection):
     fx = load(name)
     cam, stat, dyn, bg, w2c = scene_from_fixture(fx, device=hip_device)
     get_static, get_dynamic, has_delta, delta, get_flow, use_w2c = fx["opt"]
-    w2c_leaf = w2c.clone().requires_grad_(True) if use_w2c else None
-    out = render(cam, stat, dyn, None, bg, get_static=bool(get_static), get_dynamic=bool(get_dynamic), w2c=w2c_leaf,
-                 delta_exposure=torch.tensor(float(delta), device=hip_device) if has_delta else None,
-                 get_flow=bool(get_flow))
-    ref_keys = {k[4:] for k in fx if k.startswith("out_")}
-    assert {k for k, v in out.items() if isinstance(v, torch.Tensor)} == ref_keys
-    assert len(out) == 22
-    # What ONE flipped blend decision can do (two fp32 evaluations of alpha = o exp(-sigma) disagree in the last bit at the
-    # 1/255 threshold): the splat's weight is w = alpha T <= 1/255, so a composited feature / alpha moves by at most
-    # 2 w (|c| + |pixel|) (x 2: the flip also changes the next weights), an expected depth D / alpha by 2 w spread / alpha,
-    # and a decoded colour by the decoder's Lipschitz factor times the feature move: rgb = sigmoid(albedo + W2 relu(W1 .))
-    # -> 1/4 (1 + |W2|_inf |W1|_inf).  Derived, not a flat fraction of the range.
-    w = 1.001 / 255.0
-    cmax = float(np.abs(fx["out_colors_precomp_final"]).max())
-    w1, w2 = dyn.rgbdecoder.mlp1.weight.detach().reshape(6, 12).cpu(), dyn.rgbdecoder.mlp2.weight.detach().reshape(3, 6).cpu()
-    lip = 0.25 * (1.0 + float(w2.abs().sum(1).max()) * float(w1.abs().sum(1).max()))
-    feature_step = 2.0 * w * 2.0 * cmax
-    alpha_keys = {"d_depth": ("d_alpha",), "s_depth": ("s_alpha",), "depth": ("d_alpha", "s_alpha")}
-
-    def coverage_floor(k, ref):
-        """Lower bound of the coverage behind an expected-depth key (the combined pass covers at least what either
-        class covers); 1/255 where the fixture holds no matching map (s_depth's [3,H] quirk)."""
-        a = None
-        for name in alpha_keys[k]:
-            c = fx.get("out_" + name)
-            if c is not None and c.size == ref.size:
-                c = c.reshape(ref.shape)
-                a = c if a is None else np.maximum(a, c)
-        return np.maximum(a, 1.0 / 255.0) if a is not None else np.full(ref.shape, 1.0 / 255.0)
-
-    def flip_bound(k, ref):
-        if k in ("render", "s_render", "d_render"):
-            return lip * feature_step
-        if k in ("d_alpha", "s_alpha"):
-            return 2.0 * w
-        if k in alpha_keys:
-            return float((2.0 * w * float(ref.max() - ref.min()) / coverage_floor(k, ref)).max())
-        return 2.0 * w * 2.0 * max(1.0, float(np.abs(ref).max()))  # splatted flow / coordinate maps: w (|f| + |pixel f|)
-
-    for k in sorted(ref_keys):
-        ref = fx["out_" + k]
-        got = out[k].detach().cpu()
-        assert tuple(got.shape) == ref.shape, f"{k}: {tuple(got.shape)} vs {ref.shape}"
-        if ref.dtype in (np.bool_, np.int32):
-            assert np.array_equal(got.numpy(), ref), k
-        elif k in IMG_KEYS:
-            scale = max(1.0, float(np.abs(ref).max()))
-            # observed: no flip at all in the three fixtures; allowed for 2e-4 of the elements (<= 6 of them), each
-            # within the derived one-blend-step bound of its key
-            close(got, ref, 0, 3e-5 * scale, f"out[{k}]", flip_frac=2e-4, flip_atol=flip_bound(k, ref))
-        else:
-            close(got, ref, 2e-5, 1e-5 * max(1.0, float(np.abs(ref).max())), f"out[{k}]")
-    # north-star criterion: PSNR of the decoded image against a common target within 1e-4 dB
-    ref_img = torch.from_numpy(fx["out_render"])
-    target = (ref_img + 0.05 * torch.randn(ref_img.shape, generator=torch.Generator().manual_seed(2))).clamp(0, 1)
-    assert abs(psnr(out["render"].detach().cpu(), target) - psnr(ref_img, target)) <= 1e-4
-
+    kw, w2c_leaf = render_fixture_options(fx, hip_device)
+    out = render(cam, stat, dyn, None, bg, **kw)
+    # (the per-key comparison with its derived flip bounds, and the gradient loop: helpers, shared with the ray-map arm's
+    # tests in tests/test_gpu_reference_cameras.py)
+    check_render_fixture_outputs(out, fx, dyn)
     render_loss(out, fx, hip_device).backward()
-    for k, leaf in leaf_map(stat, dyn).items():
-        if "grad_" + k not in fx:
-            continue
-        ref = fx["grad_" + k]
-        scale = float(np.abs(ref).max())
-        # the full-size comparison's form (tests/test_gpu_fullsize.py): rtol 1e-3 + 1e-4 of the tensor's maximum, a 1e-5
-        # tail for entries next to a flipped blend decision (was a flat 5e-4 of the maximum: VERDICT r3 item 8)
-        close(leaf.grad, ref, 1e-3, 1e-4 * scale + 1e-7, f"grad[{k}]", flip_frac=1e-5, flip_atol=5e-3 * scale)
-    if use_w2c:
-        ref = fx["grad_w2c"]
-        close(w2c_leaf.grad, ref, 1e-3, 1e-4 * float(np.abs(ref).max()), "grad[w2c]")
-    ref = fx["grad_viewspace_points"]
-    sc = float(np.abs(ref).max())
-    close(out["viewspace_points"].grad, ref, 1e-3, 1e-4 * sc, "viewspace_points.grad", flip_frac=1e-5, flip_atol=5e-3 * sc)
+    check_render_fixture_gradients(out, fx, stat, dyn, w2c_leaf)
     ps = kernel_selection.check()
     from mobgs_amd import _fast, rendering
     if _fast.get() is not None and not (has_delta and get_flow):
@@ -113,22 +47,12 @@ def test_get_flow_matches_reference_fixture(hip_device, kernel_selection):
     with torch.no_grad():
         e2m, m2e, img, alpha = get_flow(cam, stat, dyn, None, bg,
                                         delta_exposure=torch.tensor(float(fx["opt"][0]), device=hip_device))
-    from helpers import flow_flip_bound
-    for got, key, atol in ((e2m, "out_exp2mid", 2e-4), (m2e, "out_mid2exp", 2e-4), (img, "out_latent_img", 3e-5),
-                           (alpha, "out_latent_alpha", 3e-5)):
-        assert tuple(got.shape) == fx[key].shape
-        # flow maps: one blend step of the splatted flow (derived, helpers.flow_flip_bound: ~0.05 px here, was a flat
-        # 1.0 px); decoded image / coverage: 2 / 255.  Observed: no flipped element; allowed for 2e-4 of them
-        fb = flow_flip_bound(fx[key]) if "2" in key.split("_")[1] else 2.0 / 255.0
-        close(got, fx[key], 1e-5, atol, key, flip_frac=2e-4, flip_atol=fb)
+    check_get_flow_fixture_outputs(fx, e2m, m2e, img, alpha)
     cam_b = PinholeCamera(cam.image_width, cam.image_height, cam.K, torch.from_numpy(fx["in_w2c_b"]), cam.time,
                           cam.max_time, device=hip_device)
     with torch.no_grad():
         f2d, fimg = get_flow_static(cam, cam_b, cam, stat, dyn, None, bg)
-    close(f2d, fx["out_static_flow_2d"], 1e-5, 2e-4, "static flow_2d")
-    fmax = float(np.abs(fx["out_static_flow_2d"]).max())
-    close(fimg, fx["out_static_flow_img"], 1e-5, 2e-4, "static flow image", flip_frac=2e-4,
-          flip_atol=2.0 * (1.001 / 255.0) * 2.0 * fmax)  # one blend step of a splatted per-splat flow <= fmax
+    check_get_flow_static_fixture_outputs(fx, f2d, fimg)
     kernel_selection.check(need_bwd=False)
 
 
@@ -294,8 +218,7 @@ def test_get_flow_many_equals_separate_calls(hip_device):
                      {k: t.grad.cpu() for k, t in leaf_map(stat, dyn).items() if t.grad is not None})
     for a, b in zip(res[True][0], res[False][0]):
         assert torch.equal(a, b)
-    for k, g in res[False][1].items():
-        close(res[True][1][k], g, 1e-4, 1e-5 * float(g.abs().max()) + 1e-8, f"grad[{k}]")
+    check_separate_calls_gradients(res[True][1], res[False][1])
 
 
 def test_leaf_grad_sink_equals_autograd_accumulation(hip_device):

@@ -166,6 +166,14 @@ def test_get_flow_gradients_with_and_without_the_gates(hip_device):
         assert torch.equal(x, y)
 
 
+def assert_grads_of_shared_mid_state(got, ref):
+    """The yardstick of leaf gradients computed through a SHARED mid-exposure state against the calls that each build their
+    own: one sum instead of one per call (also imported by tests/test_gpu_reference_cameras.py)."""
+    from helpers import close
+    for a, b in zip(ref, got):
+        close(b, a, 2e-5 * float(a.abs().max()), 1e-4, "shared mid state")
+
+
 def test_separate_get_flow_calls_share_the_mid_exposure_state(hip_device):
     """The unchanged caller's nine get_flow() calls per view (train.py:570-579): the mid-exposure state is built once
     (implicit cache), results equal the uncached calls' -- images bit for bit, gradients to summation order (the shared
@@ -185,8 +193,7 @@ def test_separate_get_flow_calls_share_the_mid_exposure_state(hip_device):
     h0, m0 = G.mid_cache_stats["hits"], G.mid_cache_stats["misses"]
     got = _flow_run(dev, W, H, deltas, ws, 1.0, True, True, separate=True)
     assert G.mid_cache_stats["hits"] - h0 == len(deltas) - 1 and G.mid_cache_stats["misses"] - m0 == 1
-    for a, b in zip(ref, got):
-        close(b, a, 2e-5 * float(a.abs().max()), 1e-4, "shared mid state")
+    assert_grads_of_shared_mid_state(got, ref)
     # forward values are bit-identical, and a parameter update invalidates the entry
     cam, stat, dyn = _scene(dev, W, H, 6_000, 3_000)
     bg = torch.zeros(9, device=dev)
