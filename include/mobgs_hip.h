@@ -1416,6 +1416,65 @@ int mobgs_rows_snapshot(int n_fields, const MobgsRowsField* fields_dev, int64_t 
 int mobgs_rows_restore(int n_fields, const MobgsRowsField* fields_dev, int64_t n, int64_t capacity,
                        int64_t longest_row_bytes, const void* block, void* stream);
 
+/* ---- K33: probes of the cross-lane primitives and the fixed-order sums (test support) ------------------------------------
+ * One launch of a thin kernel that loads per-thread values, calls ONE function of csrc/wave_shared.h or
+ * csrc/reduce_shared.h and stores what every thread holds afterwards (csrc/lane_probe.hip), so that lane coverage,
+ * placement and summation order of each primitive can be compared bit for bit with tests/lane_model.py.  Not part of the
+ * drop-in surface.  An entry point and constants only: MOBGS_ABI_VERSION stays as it is.  One launch on the caller's
+ * stream; it does not synchronise, allocate or read back.  in and out are device pointers.
+ *
+ * op selects the function and the instantiation (MOBGS_LANE_*, below).  A group is one full wave (T = 64 threads), for
+ *   BLOCK_SUM, ROWS_SUM and BLOCK_SUM4 one workgroup of T = 256 threads; the launch runs n_groups independent groups.
+ *   Thread t of group g reads in[(g T + t) KI + i], i < KI, and writes out[(g T + t) KO + j], j < KO; nothing else of out
+ *   is written.  Elements are 8 bytes (double) for WAVE_SUM_F64, BLOCK_SUM, ROWS_SUM and WAVE_ROWS_SUM, 4 bytes (float,
+ *   int32 or uint32 as the name says; the DPP moves and the fence carry uint32 payloads) for the others.
+ *   KI -> KO is 1 -> 1 except: REDUCE_COMPONENTS_<NVP> NVP -> NVP / 4 (the registers v[0 .. NVP / 4) the header
+ *   documents), REDUCE_PAIR 2 -> 1 (e0, e1), WAVE_FENCE 1 -> 2 (lane l writes LDS slot l; fence; reads slot 63 - l and
+ *   writes that value to slot (l + 17) & 63; fence; reads slot l: the two reads), BLOCK_SUM and BLOCK_SUM4 2 -> 2 (two
+ *   calls in a row on the same LDS array, value i to call i).
+ *   ROWS_SUM: group g sums the n values at stride `stride` from in + (2 g) n stride, then at once those from
+ *   in + (2 g + 1) n stride, with rows_sum<256>; KO = 2.  WAVE_ROWS_SUM: the n values from in + g n stride; KO = 1.
+ * n, stride: read by ROWS_SUM and WAVE_ROWS_SUM only (the others: pass 0 and 1).
+ * Refused with MOBGS_E_INVALID before any launch, under the entry point's name: an unknown op, a NULL pointer,
+ *   n_groups < 1, n < 0, stride < 1, a pointer that is not a multiple of the element size, n_groups n stride > 2^40. */
+#define MOBGS_LANE_WAVE_SUM_F32 0
+#define MOBGS_LANE_WAVE_SUM_I32 1
+#define MOBGS_LANE_WAVE_SUM_F64 2
+#define MOBGS_LANE_WAVE_MIN_F32 3
+#define MOBGS_LANE_WAVE_MIN_I32 4
+#define MOBGS_LANE_WAVE_MAX_F32 5
+#define MOBGS_LANE_WAVE_MAX_I32 6
+#define MOBGS_LANE_FOLD_MAX_I32 7            /* MOBGS_WAVE_FOLD(v, max)            */
+#define MOBGS_LANE_FOLD_ADD_I32 8            /* MOBGS_WAVE_FOLD(v, MOBGS_WAVE_ADD) */
+#define MOBGS_LANE_FOLD_ADD_F32 9
+#define MOBGS_LANE_DPP_MOV_XOR1 10           /* dpp_mov<0xB1>                      */
+#define MOBGS_LANE_DPP_MOV_XOR2 11           /* dpp_mov<0x4E>                      */
+#define MOBGS_LANE_DPP_MOV_QUAD_REVERSE 12   /* dpp_mov<0x1B>                      */
+#define MOBGS_LANE_DPP_MOV_HALF_MIRROR 13    /* dpp_mov<0x141>                     */
+#define MOBGS_LANE_DPP_MOV_ROR8 14           /* dpp_mov<0x128>                     */
+#define MOBGS_LANE_DPP_MOV_XOR4 15           /* dpp_mov<0x1B>(dpp_mov<0x141>(v))   */
+#define MOBGS_LANE_DPP_ADD_XOR1 16           /* dpp_add<0xB1>                      */
+#define MOBGS_LANE_DPP_ADD_XOR2 17           /* dpp_add<0x4E>                      */
+#define MOBGS_LANE_DPP_ADD_HALF_MIRROR 18    /* dpp_add<0x141>                     */
+#define MOBGS_LANE_DPP_ADD_ROR8 19           /* dpp_add<0x128>                     */
+#define MOBGS_LANE_DPP_ADD_ROR4 20           /* dpp_add<0x124>                     */
+#define MOBGS_LANE_DPP_ADD_XOR4 21           /* dpp_add_xor4                       */
+#define MOBGS_LANE_ROW_ALLREDUCE 22
+#define MOBGS_LANE_HALF_WAVE_SUM 23
+#define MOBGS_LANE_WAVE_ALLREDUCE 24
+#define MOBGS_LANE_REDUCE_COMPONENTS_8 25
+#define MOBGS_LANE_REDUCE_COMPONENTS_16 26
+#define MOBGS_LANE_REDUCE_COMPONENTS_32 27
+#define MOBGS_LANE_REDUCE_COMPONENTS_64 28
+#define MOBGS_LANE_REDUCE_PAIR 29
+#define MOBGS_LANE_WAVE_FENCE 30
+#define MOBGS_LANE_BLOCK_SUM 31              /* block_sum<4>, twice                */
+#define MOBGS_LANE_ROWS_SUM 32               /* rows_sum<256>, twice               */
+#define MOBGS_LANE_WAVE_ROWS_SUM 33
+#define MOBGS_LANE_BLOCK_SUM4 34             /* block_sum4, twice                  */
+#define MOBGS_LANE_OPS 35
+int mobgs_lane_probe(int op, int n_groups, int n, int stride, const void* in, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

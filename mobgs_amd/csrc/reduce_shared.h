@@ -17,6 +17,7 @@ namespace mobgs {
 
 // ---- float64: down the wave by shuffles, then the waves' values in wave order -----------------------------------------
 // s_wave: LDS [WAVES]; the workgroup has WAVES full waves
+// Lane 0's chain is the xor butterfly's tree: u[l] = v[l] + v[l + 32], then u[l] + u[l + 16], .. + u[l + 1]; then ((w0 + w1) + w2) + ..
 template <int WAVES>
 __device__ __forceinline__ double block_sum(double v, double* s_wave) {
 #pragma unroll

@@ -45,7 +45,8 @@ __device__ __forceinline__ T wave_max(T v) {
 
 // ---- DPP: one VALU instruction reads another lane of the same 16-lane row ------------------------------------------------
 // CTRL: 0xB1 = quad_perm:[1,0,3,2] (lane ^ 1), 0x4E = quad_perm:[2,3,0,1] (lane ^ 2), 0x1B = quad_perm:[3,2,1,0],
-// 0x141 = row_half_mirror (l -> 7 - l inside each 8 lanes), 0x128 = row_ror:8 (lane ^ 8)
+// 0x141 = row_half_mirror (l -> 7 - l inside each 8 lanes), 0x128 = row_ror:8 (lane ^ 8), 0x124 = row_ror:4 (lane l reads
+// lane l - 4 of its row, cyclically)
 template <int CTRL>
 __device__ __forceinline__ uint32_t dpp_mov(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false);
