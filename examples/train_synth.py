@@ -3,7 +3,10 @@
 MI355X path: render() of a static + a dynamic Gaussian set -> photometric loss (L1 + 0.2 D-SSIM) -> backward ->
 densification statistics -> Adam step; every `densify_every` iterations densify_pruneclone / prune / opacity reset.
 
-    python examples/train_synth.py [--iters 200] [--ns 20000] [--nd 10000] [--width 676 --height 507]
+    python examples/train_synth.py [--iters 200] [--ns 20000] [--nd 10000] [--width 676 --height 507] [--controller]
+
+Two densification paths: the default one is this example's own (statistics once per view, thresholds of its making);
+--controller / train(controller=True) is the reference's (train.py:809-820 through mobgs_amd.helper_train.densification_step).
 
 The "ground truth" is a render of the same scene with perturbed parameters, so the loss has somewhere to go.
 Returns (and prints) the loss / PSNR trajectory; used by tests/test_gpu_train_loop.py as an integration test.
@@ -45,6 +48,29 @@ class Opt:
     lambda_dssim = 0.2
 
 
+class ControlOpt(Opt):
+    """The controller's options at the reference's defaults (arguments/__init__.py:141-166), for train(controller=True)."""
+    opacity_reset_interval = 3000
+    densification_interval = 100
+    densify_from_iter = 500
+    densify_until_iter = 15000
+    desicnt = 6
+    densify_grad_threshold = 0.0001
+
+    @classmethod
+    def scaled(cls, iters, densify_every):
+        """The intervals for a run of `iters` iterations that resizes every `densify_every`: the interval is densify_every
+        (100 in the reference); the reference's 500 / 3000 / 15000 iterations (5, 30 and 150 intervals) would all lie
+        past the end of a run this short, so resizes start after half an interval, go on to the end of the run -- as the
+        example's own path does -- and the size-threshold switch keeps its 30 intervals."""
+        o = cls()
+        o.densification_interval = densify_every
+        o.densify_from_iter = densify_every // 2
+        o.densify_until_iter = iters
+        o.opacity_reset_interval = 30 * densify_every
+        return o
+
+
 def build(dev, ns, nd, width, height, seed=0):
     scam = SynthCamera().scaled(width, height)
     torch.manual_seed(seed)
@@ -58,7 +84,8 @@ def build(dev, ns, nd, width, height, seed=0):
     return stat, dyn, cams, (sp, dp, dx)
 
 
-def train(dev="cuda:0", iters=120, ns=6000, nd=3000, width=320, height=240, densify_every=40, seed=0, log=None):
+def train(dev="cuda:0", iters=120, ns=6000, nd=3000, width=320, height=240, densify_every=40, seed=0, log=None,
+          controller=False):
     stat, dyn, cams, (sp, dp, dx) = build(dev, ns, nd, width, height, seed)
     bg = torch.zeros(9, device=dev)
     # targets: the same scene with shifted colours / opacities, rendered once
@@ -70,7 +97,11 @@ def train(dev="cuda:0", iters=120, ns=6000, nd=3000, width=320, height=240, dens
         tstat = TrainableGaussians(tsp, None, stat.rgbdecoder, device=dev)
         tdyn = TrainableGaussians(tdp, dx, stat.rgbdecoder, device=dev)
         targets = [render(c, tstat, tdyn, None, bg)["render"].clamp(0, 1).detach() for c in cams]
-    opt = Opt()
+    opt = ControlOpt.scaled(iters, densify_every) if controller else Opt()
+    if controller:
+        import types
+        from mobgs_amd.helper_train import densification_step
+        scene, flags = types.SimpleNamespace(cameras_extent=4.0), (0, 0)
     stat.training_setup(opt)
     dyn.training_setup(opt)
     dyn.optimizer.param_groups = [gr for gr in dyn.optimizer.param_groups if gr["name"] != "decoder"]  # shared decoder
@@ -83,17 +114,20 @@ def train(dev="cuda:0", iters=120, ns=6000, nd=3000, width=320, height=240, dens
         loss.backward()
         with torch.no_grad():
             Ns = stat.get_xyz.shape[0]
-            vgrad = out["viewspace_points"].grad[0]          # [Ns+Nd, 2]
-            vis, radii = out["visibility_filter"], out["radii"]
-            stat.add_densification_stats(vgrad[:Ns], vis[:Ns], radii=radii[:Ns])
-            dyn.add_densification_stats(vgrad[Ns:], vis[Ns:], radii=radii[Ns:])
+            if not controller:
+                vgrad = out["viewspace_points"].grad[0]          # [Ns+Nd, 2]
+                vis, radii = out["visibility_filter"], out["radii"]
+                stat.add_densification_stats(vgrad[:Ns], vis[:Ns], radii=radii[:Ns])
+                dyn.add_densification_stats(vgrad[Ns:], vis[Ns:], radii=radii[Ns:])
             history.append((float(loss), float(psnr(image.detach().clamp(0, 1)[None], targets[k][None]).mean()),
                             Ns, dyn.get_xyz.shape[0]))
         stat.optimizer.step()
         dyn.optimizer.step()
         stat.optimizer.zero_grad(set_to_none=True)
         dyn.optimizer.zero_grad(set_to_none=True)
-        if it % densify_every == 0 and it < iters:
+        if controller:   # train.py:809-820: the batch (here: one view) statistics, then the schedule for both sets
+            flags = densification_step(opt, it, stat, dyn, [out], width, height, scene, flags)
+        elif it % densify_every == 0 and it < iters:
             extent = 4.0
             stat.densify_pruneclone(opt.densify_grad_threshold * 1e-2, opt.opthr, extent, 20)
             dyn.densify_pruneclone(opt.densify_grad_threshold, opt.opthr, extent, 2)
@@ -112,5 +146,6 @@ if __name__ == "__main__":
     ap.add_argument("--nd", type=int, default=10000)
     ap.add_argument("--width", type=int, default=676)
     ap.add_argument("--height", type=int, default=507)
+    ap.add_argument("--controller", action="store_true", help="the reference's densification schedule and statistics")
     a = ap.parse_args()
-    train(iters=a.iters, ns=a.ns, nd=a.nd, width=a.width, height=a.height, log=20)
+    train(iters=a.iters, ns=a.ns, nd=a.nd, width=a.width, height=a.height, log=20, controller=a.controller)

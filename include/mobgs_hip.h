@@ -1475,6 +1475,60 @@ int mobgs_rows_restore(int n_fields, const MobgsRowsField* fields_dev, int64_t n
 #define MOBGS_LANE_OPS 35
 int mobgs_lane_probe(int op, int n_groups, int n, int stride, const void* in, void* out, void* stream);
 
+/* ---- K34: densification controller (mobgs_amd/helper_train.py; csrc/densify_ctl.hip, built with -ffp-contract=off) -------
+ * The statistics of one training iteration over the views of its batch, and the row list of a resize as one plan.  Entry
+ * points and an enum only: MOBGS_ABI_VERSION stays as it is, and the five entry points of K13 keep their behaviour.  None
+ * of the calls synchronises, allocates or reads back.  The kernels validate neither row indices nor buffer sizes.
+ *
+ * mobgs_densify_stats_batch: train.py:634-648 and :813-817 for ONE set, in one launch.  grads_host / radii_host: HOST
+ *   arrays of n_views (1 .. MOBGS_STATS_MAX_VIEWS = 16) device pointers to [N_total, grad_stride] fp32 gradients and [N_total] int32 radii; row i
+ *   of the set (i < n) is row row0 + i of each.  All arithmetic fp32, in view order:
+ *     gx = (((0 + g_0.x) + g_1.x) + ...) sx,  gy likewise with sy   (sx = W * 0.5f, sy = H * 0.5f)
+ *     r = max_v radii_v,  vis = r > 0 (any view's radius is positive)
+ *     vis: max_radii2D[i] = max(max_radii2D[i], float(r)); xyz_gradient_accum[i] += sqrt(gx gx + gy gy), each operation
+ *          rounded (as mobgs_densify_stats); denom[i] += 1.  A row that is not visible is not written.
+ *   grad_sum [n,2] fp32 (8-byte aligned), radii_max [n] int32, visible [n] uint8: optional outputs (NULL: not written),
+ *   written for every row.  n = 0 launches nothing.  MOBGS_E_INVALID before any launch: n_views outside 1 .. 16, n < 0,
+ *   row0 < 0, grad_stride < 2, a NULL pointer among the views or the three statistics arrays.
+ *
+ * mobgs_densify_plan: ONE row list for mobgs_rows_gather (a negative entry -(row + 1) is a new copy of that row), in two
+ *   launches without atomics: per-block counts (1024 rows a block), then every block sums the counts before it and the
+ *   totals and writes its rows to their final places.  Meant for tables of up to a few million rows: every block of the
+ *   write pass reads all per-block counts (12 bytes per 1024 rows), so those reads grow with the square of n -- 1 MB in
+ *   all at 300 k rows, 1 GB at 10 M -- and nothing but the 2^31 - 1 bound on the list refuses a larger n.
+ *   op (MobgsDensifyPlanOp) selects the list and the inputs it reads;
+ *   the other input pointers may be NULL.  Every comparison is false on NaN, so a NaN row is kept.
+ *     PRUNECLONE     [rows not split, ascending | -(clone + 1), ascending | -(split + 1), ascending, the run n_split times]
+ *                    with clone / split the selection of mobgs_densify_select at n_grads = n on xyz_gradient_accum, denom
+ *                    [n], scaling [n,3], grad_threshold, size_threshold
+ *     PRUNE_OPACITY  rows with !(1 / (1 + expf(-opacity[i])) < min_opacity), ascending; opacity [n].  The quotient is this
+ *                    kernel's fp32 evaluation, not torch.sigmoid's: a row whose sigmoid lies within a few ulp of
+ *                    min_opacity may be decided differently from torch's (sigmoid(x) < t) mask
+ *     PRUNE_BOUNDS   rows with none of x > max.x, y > max.y, z > max.z, x < min.x, y < min.y, z < min.z (strict), ascending;
+ *                    xyz [n,3], bounds = {max.x, max.y, max.z, min.x, min.y, min.z} six fp32 ON THE DEVICE
+ *     PRUNE_MASK     rows with mask[i] == 0, ascending; mask [n] uint8
+ *   index [n max(2, n_split)] int32: the list; entries at and beyond counts[3] are not written.
+ *   counts [4] int32: kept rows, clones, split parents, n_out = kept + clones + n_split parents (the prunes: kept, 0, 0,
+ *   kept), written by the last block.  scratch: 3 int32 per block of 1024 rows, (n + 1023) / 1024 blocks.
+ *   n = 0: counts = 0 (a memset on the stream), no launch, no list.  MOBGS_E_INVALID before any launch: n_split outside
+ *   1 .. 8 (for every op), an unknown op, n < 0, n max(2, n_split) > 2^31 - 1, NULL counts, and for n > 0 a NULL list,
+ *   scratch or input of the op. */
+#define MOBGS_STATS_MAX_VIEWS 16
+typedef enum MobgsDensifyPlanOp {
+    MOBGS_PLAN_PRUNECLONE = 0,
+    MOBGS_PLAN_PRUNE_OPACITY = 1,
+    MOBGS_PLAN_PRUNE_BOUNDS = 2,
+    MOBGS_PLAN_PRUNE_MASK = 3
+} MobgsDensifyPlanOp;
+int mobgs_densify_stats_batch(int n_views, const float* const* grads_host, int grad_stride,
+                              const int32_t* const* radii_host, int row0, int n, float sx, float sy,
+                              float* xyz_gradient_accum, float* denom, float* max_radii2D, float* grad_sum,
+                              int32_t* radii_max, uint8_t* visible, void* stream);
+int mobgs_densify_plan(int op, int n, int n_split, const float* xyz_gradient_accum, const float* denom,
+                       const float* scaling, float grad_threshold, float size_threshold, const float* opacity,
+                       float min_opacity, const float* xyz, const float* bounds, const uint8_t* mask, int32_t* index,
+                       int32_t* counts, int32_t* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,7 +41,9 @@ def _parse_header(text: str):
         a scalar whose type must be in _SCALARS; `(void)` is an empty list;
       - structs are `typedef struct Name { ... } Name;` with plain fields, several declarators per type allowed
         (`const float *a, *b;`), no bit-fields, arrays or nested structs;
-      - every `#define` with a value is an integer constant (optionally parenthesised).
+      - every `#define` with a value is an integer constant (optionally parenthesised);
+      - enums are `typedef enum Name { A = 0, B = 1 } Name;` with every value written out: the enumerators join the
+        defines, and a function takes the value as a plain `int`.
     Anything else raises with the offending text; nothing is skipped."""
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     text = re.sub(r"//[^\n]*", " ", text)
@@ -68,6 +70,18 @@ def _parse_header(text: str):
         return " "
 
     text = re.sub(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*(\w+)\s*;", take_struct, text, flags=re.S)
+
+    def take_enum(m):
+        if m[1] != m[3]:
+            raise ValueError(f"mobgs_hip.h: enum {m[1]} is typedef'd as {m[3]}")
+        for item in filter(None, (e.strip() for e in m[2].split(","))):
+            e = re.fullmatch(r"(\w+)\s*=\s*(-?\d+)", item)   # every enumerator carries its value
+            if not e:
+                raise ValueError(f"mobgs_hip.h: cannot read the enumerator {item!r} of enum {m[1]}")
+            defines[e[1]] = int(e[2])
+        return " "
+
+    text = re.sub(r"typedef\s+enum\s+(\w+)\s*\{(.*?)\}\s*(\w+)\s*;", take_enum, text, flags=re.S)
     sigs = {}
     for decl in filter(None, (" ".join(d.split()) for d in text.split(";"))):
         m = re.fullmatch(r"(.*?)\s*\b(mobgs_\w+) ?\((.*)\)", decl)

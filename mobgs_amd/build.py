@@ -13,7 +13,7 @@ from pathlib import Path
 CSRC = Path(__file__).resolve().parent / "csrc"
 # MOBGS_LIB: load another build of the same library instead (A/B timing of kernel variants on one GPU box)
 LIB_PATH = Path(os.environ["MOBGS_LIB"]).resolve() if os.environ.get("MOBGS_LIB") else CSRC / "libmobgs_hip.so"
-SOURCES = ["project.hip", "isect.hip", "raster.hip", "raster_bwd_mfma.hip", "raster_layers.hip", "pipeline.hip", "prep.hip", "decoder.hip", "deform.hip", "deform_bwd.hip", "hexplane_bwd.hip", "blce.hip", "loss.hip", "flowloss.hip", "densify.hip", "adam_dev.hip", "normals.hip", "knn.hip", "control_prune.hip", "scene_seed.hip", "exposure.hip", "regterms.hip", "metrics.hip", "pose.hip", "lpips.hip", "tof.hip", "report.hip", "gridreg.hip", "snapshot.hip", "lane_probe.hip"]
+SOURCES = ["project.hip", "isect.hip", "raster.hip", "raster_bwd_mfma.hip", "raster_layers.hip", "pipeline.hip", "prep.hip", "decoder.hip", "deform.hip", "deform_bwd.hip", "hexplane_bwd.hip", "blce.hip", "loss.hip", "flowloss.hip", "densify.hip", "adam_dev.hip", "normals.hip", "knn.hip", "control_prune.hip", "scene_seed.hip", "exposure.hip", "regterms.hip", "metrics.hip", "pose.hip", "lpips.hip", "tof.hip", "report.hip", "gridreg.hip", "snapshot.hip", "lane_probe.hip", "densify_ctl.hip"]
 ARCH = "gfx950"
 # host fast path (csrc/fastpath.cpp): a plain C++ torch extension, no device code, no link against libmobgs_hip.so
 FAST_SRC = CSRC / "fastpath.cpp"
@@ -59,6 +59,10 @@ EXTRA_FLAGS["report.hip"] = EXTRA_FLAGS.get("report.hip", []) + ["-ffp-contract=
 # gridreg.hip: the same for the grid regularisers: a second difference is (t[k+2] - t[k+1]) - (t[k+1] - t[k]) with each of
 # the three subtractions rounded to fp32, as the reference's slice statements round them (csrc/gridreg.hip).  Memory-bound kernels: no cost.
 EXTRA_FLAGS["gridreg.hip"] = EXTRA_FLAGS.get("gridreg.hip", []) + ["-ffp-contract=off"]
+# densify_ctl.hip: the same for the batch statistics: the gradient of a row is ((0 + g_0) + g_1 + ...) s with every addition
+# and the scaling rounded to fp32 in view order, as the reference's `+=` over the views and `*= W * 0.5` round them, so
+# grad_sum is bit-equal with torch and the norm starts from the same two numbers (csrc/densify_ctl.hip).  HBM-bound: no cost.
+EXTRA_FLAGS["densify_ctl.hip"] = EXTRA_FLAGS.get("densify_ctl.hip", []) + ["-ffp-contract=off"]
 # normals.hip: the same for the back-projected differences d_r z_r - d_l z_l: fused into fma(d_r, z_r, -(d_l z_l)) the
 # difference of two equal products is one product's rounding error, not 0, and the normals of a flat patch or of a depth
 # hole get components of 1e-8 where the reference's are exactly 0 (tests/test_gpu_loss_kernels.py).  15 us kernels.

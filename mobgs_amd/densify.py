@@ -12,6 +12,8 @@ per-splat statistics arrays, and offers the reference's method names with the re
     prune_points(mask)                       :1066-1089
     onedown_control_pts(viewpoints)          :274-371 (scene_init.onedown_control_pts: csrc/control_prune.hip)
     reset_opacity()                          :897-903
+    pruneclone_planned / prune_opacity_below / prune_outside   the tables of densify_pruneclone / prune_points(opacity
+                                             mask) / helper_train.removeminmax from ONE plan (csrc/densify_ctl.hip, K34)
 
 Where the reference re-allocates every group with ~50 index / cat / repeat calls per operation, every field lives
 here in a capacity-sized buffer pair; a resize builds ONE row list and moves all fields (parameters, Adam moments,
@@ -376,6 +378,77 @@ class TrainableGaussians(GaussianParams):
         sel = self._indices_of(split, 1)
         cl = self._indices_of(clone, 1)
         self._split_into(keep, [-(cl + 1)], sel, splitN, samples)
+
+    # ---- planned resizes (include/mobgs_hip.h K34, csrc/densify_ctl.hip) ---------------------------------------------
+    # The row list of a resize from ONE plan: two launches and one read-back of four counts, where the methods above
+    # take a selection launch, up to three single-workgroup list launches with a read-back each, and arange / cat glue.
+    # Everything after the list (_rebuild, the children kernel) is shared with them, so the results are the same tables.
+    def _plan(self, op_name: str, n_split: int = 1, **inputs):
+        """-> (index int32 [n max(2, n_split)], kept, clones, split parents, n_out) of mobgs_densify_plan on the live
+        rows; the four counts come to the host in one copy."""
+        n, dev = self._n, self._xyz.device
+        arr = lambda k: ptr(inputs[k]) if k in inputs else None  # noqa: E731
+        index = torch.empty(n * max(2, n_split), dtype=torch.int32, device=dev)
+        counts = torch.empty(4, dtype=torch.int32, device=dev)
+        scratch = torch.empty(3 * ((n + 1023) // 1024), dtype=torch.int32, device=dev)
+        check(_lib.load().mobgs_densify_plan(
+            _lib._DEFINES["MOBGS_PLAN_" + op_name], n, n_split, arr("accum"), arr("denom"), arr("scaling"),
+            float(inputs.get("grad_threshold", 0.0)), float(inputs.get("size_threshold", 0.0)), arr("opacity"),
+            float(inputs.get("min_opacity", 0.0)), arr("xyz"), arr("bounds"), arr("mask"),
+            ptr(index) if n else None, ptr(counts), ptr(scratch) if n else None, stream()), "mobgs_densify_plan")
+        kept, clones, parents, n_out = counts.tolist()
+        return index, kept, clones, parents, n_out
+
+    def _prune_planned(self, op_name: str, **inputs):
+        index, _, _, _, n_out = self._plan(op_name, **inputs)
+        coherent = self.rows_coherent == self._n
+        self._rebuild(index[:n_out], reset_stats=False)
+        if coherent:  # a subsequence of ordered rows is ordered
+            self.rows_coherent = self._n
+
+    @torch.no_grad()
+    def pruneclone_planned(self, max_grad, extent, splitN=2, samples=None):
+        """The table densify_pruneclone(max_grad, ., extent, ., splitN, samples) leaves ([kept originals | clones | split
+        children]), with torch.normal consuming the generator as it does there."""
+        n = self._n
+        scaling = self._fields["scaling"].view(n)
+        index, kept, clones, parents, n_out = self._plan(
+            "PRUNECLONE", splitN, accum=self.xyz_gradient_accum.reshape(-1), denom=self.denom.reshape(-1),
+            scaling=scaling, grad_threshold=max_grad, size_threshold=self.percent_dense * extent)
+        n_children = splitN * parents
+        if samples is None and n_children:
+            sel = -(index[n_out - parents:n_out] + 1)   # the list's tail: the split parents, ascending
+            stds = torch.exp(scaling[sel.long()]).repeat(splitN, 1)
+            samples = torch.normal(mean=torch.zeros_like(stds), std=stds)
+        self._rebuild(index[:n_out], reset_stats=True)
+        if n_children:
+            samples = samples.to(torch.float32).contiguous()
+            check(_lib.load().mobgs_split_children(n_children, kept + clones, splitN, ptr(samples),
+                                                  ptr(self._fields["rotation"].view(self._n)),
+                                                  ptr(self._fields["xyz"].view(self._n)),
+                                                  ptr(self._fields["scaling"].view(self._n)), stream()),
+                  "mobgs_split_children")
+        if self.keep_sorted:
+            self.spatial_sort_()
+
+    @torch.no_grad()
+    def prune_opacity_below(self, min_opacity):
+        """The table prune_points((get_opacity < min_opacity).squeeze()) leaves, with the sigmoid and the comparison inside
+        the plan: 1 / (1 + expf(-x)) in fp32 there, torch.sigmoid here.  The two agree except for a row whose sigmoid lies
+        within a few ulp of min_opacity, which the two routes may decide differently; every other row, and every table
+        without such a row, comes out bit for bit the same."""
+        self._prune_planned("PRUNE_OPACITY", opacity=self._fields["opacity"].view(self._n).reshape(-1),
+                            min_opacity=min_opacity)
+
+    @torch.no_grad()
+    def prune_outside(self, minbounds, maxbounds):
+        """The table helper_train.removeminmax leaves: rows with a coordinate strictly above `maxbounds` or strictly
+        below `minbounds` go.  The bounds (three numbers or 0-dim tensors each) reach the kernel as six fp32 on the
+        device: no value is read back."""
+        dev = self._xyz.device
+        bounds = torch.stack([torch.as_tensor(b, dtype=torch.float32, device=dev).reshape(())
+                              for b in (*maxbounds, *minbounds)])
+        self._prune_planned("PRUNE_BOUNDS", xyz=self._fields["xyz"].view(self._n), bounds=bounds)
 
     @torch.no_grad()
     def onedown_control_pts(self, viewpoints):
