@@ -70,22 +70,32 @@ def warm_hints(t):
 
 def run(dev="cuda:0", iters=40, *, ns=4000, nd=2000, width=256, height=192, n_views=2, seed=0, lambda_flow=0.0, graph=False,
         path=None, save_every=0, save_at=(), resume=None, stop_at=None, densify_at=(), reset_opacity_at=(),
-        estimate_exposure_at=(), blocking=False, log=0):
-    """-> (loss history of the iterations run here, trainer, save handles, arenas_fit).  Runs iterations start + 1 .. stop_at
+        estimate_exposure_at=(), blocking=False, log=0, controller=False):
+    """controller (True, or a mapping of option overrides: DeblurTrainer): the reference's densification on its schedule
+    (helper_train.DensificationController) instead of densify_at; its flags, bounds and log travel in the checkpoint's
+    counters.  After one of its operations a --graph run makes the next iteration eagerly and records the one after it.
+    -> (loss history of the iterations run here, trainer, save handles, arenas_fit).  Runs iterations start + 1 .. stop_at
     (default iters) where start is the checkpoint's iteration (0 without --resume); `iters` is the run's planned length (the
     horizon of the schedules and of the blur kernel's rate) and must be what the interrupted run was given."""
-    t = DeblurTrainer(dev, ns, nd, width, height, n_views, seed, lambda_flow, None, iters, False, True)
-    start, fresh = 0, False
+    if controller:
+        t = DeblurTrainer(dev, ns, nd, width, height, n_views, seed, lambda_flow, None, iters, False, True,
+                          controller=controller)
+    else:
+        t = DeblurTrainer(dev, ns, nd, width, height, n_views, seed, lambda_flow, None, iters, False, True)
+    start, fresh, record_at = 0, False, 0
     if resume:
         state = load_training_state(resume, device=dev, training_args=t.opt)
         adopt(t, state)
         start, fresh = state.iteration, True
+        if t.controller is not None:
+            t.controller.load_state_dict(state.counters["controller"], device=dev)
+            record_at = int(state.counters.get("record_at", 0))
         if state.counters.get("blce_rate_pending"):   # saved under a DeviceAdam: the rate of iteration `start`, not yet
             t.blce.adjust_lr()                        # multiplied for the next one as the eager loop leaves it
     history, handles, adam, fb, arenas_fit = [], [], None, None, True
     for it in range(start + 1, (stop_at or iters) + 1):
-        if graph and fb is None and it >= 2:   # (iteration 1 of a new run is eager: arenas and hints exist afterwards)
-            if fresh:
+        if graph and fb is None and it >= 2 and it >= record_at:   # (iteration 1 of a new run is eager: arenas and hints
+            if fresh:                                              # exist afterwards; so is the one after the controller)
                 warm_hints(t)
             adam = t.device_adam(first_iteration=it, horizon=iters)
 
@@ -107,7 +117,8 @@ def run(dev="cuda:0", iters=40, *, ns=4000, nd=2000, width=256, height=192, n_vi
         else:
             history.append(float(t.iteration()))
             t.blce.adjust_lr()
-        surgery = it in densify_at or it in reset_opacity_at
+        due = t.controller is not None and t.controller.due(it)
+        surgery = it in densify_at or it in reset_opacity_at or due
         if surgery and adam is not None:   # back to the state the eager loop holds between iterations
             adam.sync_to_host()
             t.blce.adjust_lr()
@@ -118,9 +129,15 @@ def run(dev="cuda:0", iters=40, *, ns=4000, nd=2000, width=256, height=192, n_vi
             t.stat.reset_opacity()
             t.dyn.reset_opacity()
             rebind(t)
+        if due:
+            t.control(it)
+            record_at = it + 2
         if path and ((save_every and it % save_every == 0) or it in save_at):
             handles.append(save_training_state(path, stat=t.stat, dyn=t.dyn, blce=t.blce, device_adam=adam, iteration=it,
-                                               counters={"blce_rate_pending": adam is not None, "last_loss": history[-1]},
+                                               counters=dict({"blce_rate_pending": adam is not None,
+                                                              "last_loss": history[-1]},
+                                                             **({"controller": t.controller.state_dict(),
+                                                                 "record_at": record_at} if t.controller is not None else {})),
                                                blocking=blocking))
         if log and (it % log == 0 or it == start + 1):
             print(f"it {it:4d}  photometric {history[-1]:.5f}  rows {t.stat._n} + {t.dyn._n}")
@@ -148,11 +165,13 @@ if __name__ == "__main__":
     ap.add_argument("--export", default=None, metavar="DIR",
                     help="at the end also write the reference's layout (point_cloud*.ply, point_cloud.pt, blce.pth) there")
     ap.add_argument("--lambda-flow", type=float, default=0.0)
+    ap.add_argument("--controller", action="store_true",
+                    help="the reference's densification schedule (helper_train.DensificationController); saved and resumed")
     a = ap.parse_args()
     every = lambda k: tuple(range(k, a.iters + 1, k)) if k else ()  # noqa: E731
     history, trainer, _, fit = run(iters=a.iters, ns=a.ns, nd=a.nd, width=a.width, height=a.height, graph=a.graph,
                                    path=a.path, save_every=a.save_every, resume=a.resume, lambda_flow=a.lambda_flow,
-                                   stop_at=a.stop_at,
+                                   stop_at=a.stop_at, controller=a.controller,
                                    densify_at=every(a.densify_every), reset_opacity_at=every(a.reset_opacity_every), log=10)
     if a.export:
         print("exported", export_reference_layout(a.export, stat=trainer.stat, dyn=trainer.dyn, blce=trainer.blce))

@@ -12,6 +12,10 @@ MI355X path and, under torchrun, sharded over GPUs:
   backward                ops.LeafGradSink + distributed.FlatGradients, ONE in-place gradient all-reduce that also carries
                           the mid-frame densification statistics
   step                    Adam on both Gaussian sets, the decoder and the BLCE parameters; densification statistics
+  --controller            the reference's densification (train.py:809-820): the batch statistics in ONE launch inside the
+                          iteration -- from the mid renders, or from the gradient message when sharded -- and after the
+                          step helper_train.DensificationController.step(): clone + split / opacity prune / opacity reset
+                          on the reference's schedule, in every mode (eager, --graph, --graph-optimizer, torchrun)
 
     python examples/train_deblur_synth.py [--iters 60]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 examples/train_deblur_synth.py
@@ -39,7 +43,7 @@ from mobgs_amd.loss_utils import flow_warp_loss, l1_loss, photometric_loss  # no
 from mobgs_amd.ops import LeafGradSink  # noqa: E402
 from mobgs_amd.optim import DeviceAdam, MultiplicativeLR, fused_adam_step  # noqa: E402
 from mobgs_amd.synth import SynthCamera, dynamic_extras, gaussian_cloud  # noqa: E402
-from train_synth import Opt  # noqa: E402  (examples/ is on sys.path when run as a script or from the test)
+from train_synth import ControlOpt, Opt  # noqa: E402  (examples/ is on sys.path when run as a script or from the test)
 
 K = 9
 
@@ -121,7 +125,10 @@ class DeblurTrainer:
     Adam on both Gaussian sets (incl. the decoder) and the BLCE parameters.  bench.py times it at full size."""
 
     def __init__(self, dev="cuda:0", ns=4000, nd=2000, width=256, height=192, n_views=2, seed=0, lambda_flow=1e-2,
-                 shard=None, iters=40, from_views=False, lr_schedule=False):
+                 shard=None, iters=40, from_views=False, lr_schedule=False, *, controller=None):
+        """controller: None (no densification: the statistics are added once per view, as before), a
+        helper_train.DensificationController, True (one with the reference's options, train_synth.ControlOpt) or a mapping of
+        option overrides ("cameras_extent" among them)."""
         from mobgs_amd.main_utils import get_normals
         self.get_normals = get_normals
         self.shard = shard = shard or SubframeShard()
@@ -176,6 +183,63 @@ class DeblurTrainer:
         # N > 1: one gradient message per view, exchanged while the next view back-propagates (backward_by_view)
         self.view_buckets = ([FlatGradients(params, extra={f"view{v}": 3 * (ns + nd)}) for v in range(n_views)]
                              if shard.collective else None)
+        self.controller = self._make_controller(controller) if controller is not None and controller is not False else None
+
+    CAMERAS_EXTENT = 5.0   # scene.cameras_extent of the synthetic scene (the spatial_lr_scale sets_from_views passes)
+
+    def _make_controller(self, controller):
+        from mobgs_amd.helper_train import DensificationController
+        if isinstance(controller, DensificationController):
+            return controller
+        overrides = dict(controller) if isinstance(controller, dict) else {}
+        extent = overrides.pop("cameras_extent", self.CAMERAS_EXTENT)
+        for name in ("opacity_reset_interval", "densification_interval", "densify_from_iter", "densify_until_iter",
+                     "desicnt", "densify_grad_threshold"):
+            setattr(self.opt, name, getattr(ControlOpt, name))
+        for name, value in overrides.items():
+            setattr(self.opt, name, value)
+        return DensificationController(self.opt, extent, self.stat, self.dyn)
+
+    def parameters(self):
+        """The tensors the flat gradient buffers are laid over, as they are now."""
+        return [p for gr in self.stat.optimizer.param_groups + self.dyn.optimizer.param_groups for p in gr["params"]] \
+            + list(self.blce.model.get_params())
+
+    def rebind(self):
+        """After a resize, an opacity reset or a load the sets' Parameters are new objects and the row counts may have
+        changed: the trainer's sizes, the flat gradient buffers (the per-view ones of the sharded loop too) and the
+        renderer's caches follow.  The dynamic set's optimiser stays without the shared decoder's group: a resize re-keys
+        the groups it has and adds none."""
+        from mobgs_amd import gaussian_renderer
+        self.ns, self.nd = int(self.stat.get_xyz.shape[0]), int(self.dyn.get_xyz.shape[0])
+        assert all(gr["name"] != "decoder" for gr in self.dyn.optimizer.param_groups)
+        params, slot = self.parameters(), 3 * (self.ns + self.nd)
+        self.bucket.rebind(params, extra={f"view{v}": slot for v in range(self.n_views)})
+        for v, b in enumerate(self.view_buckets or []):
+            b.rebind(params, extra={f"view{v}": slot})
+        gaussian_renderer.parameters_changed()
+
+    def control(self, iteration) -> bool:
+        """After the optimiser step of `iteration`: the controller's schedule on both sets (train.py:819-820); -> whether
+        a table was resized or had its opacity reset (the buffers are then laid anew: rebind())."""
+        if self.controller is None or not self.controller.step(iteration, self.stat, self.dyn):
+            return False
+        self.rebind()
+        return True
+
+    def _batch_statistics(self, mids, buckets):
+        """With a controller: the statistics of the iteration over the views of its batch in ONE launch (train.py:634-648 +
+        :813-817: the norm of the gradient SUMMED over the views).  buckets: None -- from the mid renders' own gradients
+        and int32 radii -- or the FlatGradients whose slot "view<v>" holds view v's statistics after the all-reduce."""
+        from mobgs_amd.helper_train import batch_densification_stats, message_densification_stats
+        W, H = self.cams[0].image_width, self.cams[0].image_height
+        with torch.no_grad():
+            if buckets is None:
+                batch_densification_stats(self.stat, self.dyn, [mids[v] for v in range(self.n_views)], W, H,
+                                          one_launch=True)
+            else:
+                message_densification_stats(self.stat, self.dyn,
+                                            [buckets[v].extra(f"view{v}") for v in range(self.n_views)], W, H)
 
     def prune_viewpoints(self, n=8):
         """Cameras for TrainableGaussians.onedown_control_pts, with the attributes the reference's compute_prune_error
@@ -250,12 +314,15 @@ class DeblurTrainer:
                                               mids[v]["radii"])
 
         shard.backward_by_view(self.view_buckets, view_backward, after_view)
-        with torch.no_grad():
-            for v in range(V):
-                grad2d, radii = shard.get_densification_stats(self.view_buckets[v], f"view{v}")
-                vis = radii > 0
-                stat.add_densification_stats(grad2d[:ns], vis[:ns], radii=radii[:ns])
-                dyn.add_densification_stats(grad2d[ns:], vis[ns:], radii=radii[ns:])
+        if self.controller is not None:
+            self._batch_statistics(mids, self.view_buckets)
+        else:
+            with torch.no_grad():
+                for v in range(V):
+                    grad2d, radii = shard.get_densification_stats(self.view_buckets[v], f"view{v}")
+                    vis = radii > 0
+                    stat.add_densification_stats(grad2d[:ns], vis[:ns], radii=radii[:ns])
+                    dyn.add_densification_stats(grad2d[ns:], vis[ns:], radii=radii[ns:])
         fused_adam_step([stat.optimizer, dyn.optimizer, blce.optimizer])
         return torch.stack([p.detach() for p in photos]).mean()
 
@@ -324,9 +391,16 @@ class DeblurTrainer:
         loss = loss + shard.replicated_term(1e-4 * ((stat._scaling ** 2).mean() + (dyn._scaling ** 2).mean()))
         with LeafGradSink(stat, dyn, extra=blce.model.get_params()):
             loss.backward()
+        if self.controller is not None and not shard.collective:   # single process: straight from the mid renders
+            shard.all_reduce_gradients(bucket)
+            self._batch_statistics(mids, None)
+            return photo.detach()
         for v, pkg in mids.items():
             shard.put_densification_stats(bucket, f"view{v}", pkg["viewspace_points"].grad, pkg["radii"])
         shard.all_reduce_gradients(bucket)
+        if self.controller is not None:                            # sharded: from the message, where the sum left them
+            self._batch_statistics(mids, [bucket] * self.n_views)
+            return photo.detach()
         with torch.no_grad():
             for v in range(self.n_views):
                 grad2d, radii = shard.get_densification_stats(bucket, f"view{v}")
@@ -424,7 +498,8 @@ class DeblurTrainer:
 
 def train(dev="cuda:0", iters=40, ns=4000, nd=2000, width=256, height=192, n_views=2, seed=0, lambda_flow=1e-2,
           shard=None, log=None, graph=False, prune_control_every=0, from_views=False, estimate_exposure=0,
-          report_dir=None, report_every=0, lr_schedule=False, graph_optimizer=False):
+          report_dir=None, report_every=0, lr_schedule=False, graph_optimizer=False, *, controller=False,
+          first_iteration=1, keep_sorted=False, on_trainer=None):
     """graph=True (single process): forward + losses + backward of the iteration recorded ONCE as a HIP graph
     (mobgs_amd.graphed.GraphedCallable) and replayed, the Adam step outside -- for small images / few Gaussians, where an
     iteration is ~1400 launches and bound by the host (the reference's own 512x288 / 30 k operating point: 9.5 -> 7.5 ms).
@@ -445,20 +520,44 @@ def train(dev="cuda:0", iters=40, ns=4000, nd=2000, width=256, height=192, n_vie
     recorded iteration reads the new values.
     report_dir, report_every=K > 0: after every K-th iteration (and after the last) rank 0 writes the report sheets of the
     training views (DeblurTrainer.report: mobgs_amd.scene_utils.render_training_image, as train.py:776-790 does on its
-    testing iterations)."""
+    testing iterations).
+    controller=True (or a mapping of option overrides, see DeblurTrainer): the reference's densification, in every mode.
+    The statistics of an iteration are the batch's, one launch inside the iteration (recorded with it under graph=True);
+    after the optimiser step DensificationController.step(it, stat, dyn) runs the schedule of train.py:819-820.  When it
+    resized a table or reset its opacities, the flat gradient buffers are laid over the new Parameters
+    (DeblurTrainer.rebind) and, under graph=True, the recorded iteration is dropped: the optimisers' host state is brought
+    up to date (DeviceAdam.sync_to_host, blcekernel.adjust_lr), the next iteration runs eagerly -- arenas and hints learn
+    the grown scene, the reason iteration 1 is eager -- and the one after it is recorded again, with a DeviceAdam that
+    starts at that iteration.
+    first_iteration: the loop runs first_iteration .. iters with schedules, the blur kernel's rate and DeviceAdam at the
+    true iteration (a short run can then cross iteration 3000, the opacity reset controlgaussians hard-codes).
+    keep_sorted=True: TrainableGaussians.keep_sorted on both sets -- every densification ends with a spatial sort.
+    on_trainer: called with the DeblurTrainer once it exists (its controller's log and flags, its optimisers)."""
     import time
     started = time.time()
     lr_schedule = lr_schedule or graph_optimizer
-    t = DeblurTrainer(dev, ns, nd, width, height, n_views, seed, lambda_flow, shard, iters, from_views, lr_schedule)
+    if controller is not False and controller is not None:
+        t = DeblurTrainer(dev, ns, nd, width, height, n_views, seed, lambda_flow, shard, iters, from_views, lr_schedule,
+                          controller=controller)
+    else:
+        t = DeblurTrainer(dev, ns, nd, width, height, n_views, seed, lambda_flow, shard, iters, from_views, lr_schedule)
     if graph_optimizer and (not graph or t.shard.collective):
         raise ValueError("graph_optimizer=True needs graph=True and a single process")
+    if keep_sorted:
+        t.stat.keep_sorted = t.dyn.keep_sorted = True
+    if on_trainer is not None:
+        on_trainer(t)
+    if first_iteration > 1 and lr_schedule:   # the rate blcekernel.adjust_lr() has left after first_iteration - 1 calls
+        for g in t.blce.optimizer.param_groups:
+            g["lr"] *= t.blce.lr_factor ** (first_iteration - 1)
     history, adam = [], None
     prune_views = t.prune_viewpoints() if prune_control_every else None
     fb, pending = None, []
-    for it in range(1, iters + 1):
+    record_at = first_iteration + 1   # (the first iteration runs eagerly: arenas and hints exist afterwards)
+    for it in range(first_iteration, iters + 1):
         if estimate_exposure and it % estimate_exposure == 0:
             t.estimate_exposure()
-        if graph and it == 2 and not t.shard.collective:   # (iteration 1 ran eagerly: arenas and hints exist)
+        if graph and fb is None and it == record_at and not t.shard.collective:
             from mobgs_amd.graphed import GraphedCallable
             if graph_optimizer:
                 adam = t.device_adam(first_iteration=it, horizon=iters)
@@ -497,6 +596,14 @@ def train(dev="cuda:0", iters=40, ns=4000, nd=2000, width=256, height=192, n_vie
             history.append(float(t.iteration()))
         if lr_schedule and adam is None:
             t.blce.adjust_lr()
+        if t.controller is not None and t.controller.due(it):
+            if fb is not None:   # the tensors of the recorded iteration are about to be replaced: back to the state the
+                if adam is not None:   # eager loop holds between two iterations, and record again two iterations on
+                    adam.sync_to_host()
+                    t.blce.adjust_lr()
+                adam, fb, pending = None, None, []
+            t.control(it)
+            record_at = it + 2
         if prune_control_every and it % prune_control_every == 0:
             pruned = t.dyn.onedown_control_pts(prune_views)
             if t.shard.rank == 0:
@@ -504,7 +611,7 @@ def train(dev="cuda:0", iters=40, ns=4000, nd=2000, width=256, height=192, n_vie
         if report_dir and report_every and (it % report_every == 0 or it == iters) and t.shard.rank == 0:
             sheets = t.report(report_dir, it, time.time() - started)
             print(f"it {it:4d}  report sheets of {len(sheets)} views under {os.path.dirname(sheets[0])}")
-        if it == 2:   # everything long-lived exists now: keep Python's cyclic collector off it (66 ms per generation-2
+        if it == first_iteration + 1:   # everything long-lived exists now: keep Python's cyclic collector off it (66 ms per generation-2
             import gc  # pass over a torch process's objects on this host, in the middle of an iteration: DESIGN section 5)
             gc.collect()
             gc.freeze()
@@ -540,6 +647,11 @@ if __name__ == "__main__":
                     help="write the report sheets of the training views (render_training_image) under DIR")
     ap.add_argument("--report-every", type=int, default=0, metavar="K",
                     help="with --report-dir: after every K-th iteration and after the last (0 = never)")
+    ap.add_argument("--controller", action="store_true",
+                    help="the reference's densification schedule and batch statistics (helper_train.DensificationController)")
+    ap.add_argument("--first-iteration", type=int, default=1, metavar="IT",
+                    help="run iterations IT .. --iters, with every schedule at the true iteration")
+    ap.add_argument("--keep-sorted", action="store_true", help="end every densification with a spatial sort of the table")
     a = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -550,4 +662,5 @@ if __name__ == "__main__":
     train(dev=f"cuda:{local}", iters=a.iters, ns=a.ns, nd=a.nd, width=a.width, height=a.height, log=10, graph=a.graph,
           prune_control_every=a.prune_control_every, from_views=a.from_views, estimate_exposure=a.estimate_exposure,
           report_dir=a.report_dir, report_every=a.report_every, lr_schedule=a.lr_schedule,
-          graph_optimizer=a.graph_optimizer, lambda_flow=a.lambda_flow)
+          graph_optimizer=a.graph_optimizer, lambda_flow=a.lambda_flow, controller=a.controller,
+          first_iteration=a.first_iteration, keep_sorted=a.keep_sorted)

@@ -1491,6 +1491,17 @@ int mobgs_lane_probe(int op, int n_groups, int n, int stride, const void* in, vo
  *   written for every row.  n = 0 launches nothing.  MOBGS_E_INVALID before any launch: n_views outside 1 .. 16, n < 0,
  *   row0 < 0, grad_stride < 2, a NULL pointer among the views or the three statistics arrays.
  *
+ * mobgs_densify_stats_sets: the statistics of mobgs_densify_stats_batch for up to TWO sets in ONE launch (the static rows
+ *   and the dynamic rows of a render, or of a gradient message), bit-equal to one mobgs_densify_stats_batch call per set on
+ *   the same numbers.  Set a is rows [row0_a, row0_a + n_a) of every view's arrays with its own three statistics arrays, set
+ *   b likewise; either may have n = 0 (its pointers are then not read).  radii_host: HOST array of n_views device pointers
+ *   to [N_total] radii in the encoding radii_encoding names: MOBGS_RADII_INT32 (contiguous int32, what render() returns) or
+ *   MOBGS_RADII_FP32 (fp32-coded integers, the last N floats of a gradient message's slot whose first 2 N floats are the
+ *   [N, 2] gradient rows; |r| < 2^24, so the conversion is exact).  Both tables are copied into the kernel's arguments: the
+ *   call can be recorded in a graph.  No optional outputs.  MOBGS_E_INVALID before any launch: n_views outside 1 .. 16, an
+ *   unknown encoding, a negative n or row0, grad_stride < 2, a NULL table, a NULL pointer among the views (n_a + n_b > 0) or
+ *   among the statistics arrays of a set with n > 0.
+ *
  * mobgs_densify_plan: ONE row list for mobgs_rows_gather (a negative entry -(row + 1) is a new copy of that row), in two
  *   launches without atomics: per-block counts (1024 rows a block), then every block sums the counts before it and the
  *   totals and writes its rows to their final places.  Meant for tables of up to a few million rows: every block of the
@@ -1514,6 +1525,8 @@ int mobgs_lane_probe(int op, int n_groups, int n, int stride, const void* in, vo
  *   1 .. 8 (for every op), an unknown op, n < 0, n max(2, n_split) > 2^31 - 1, NULL counts, and for n > 0 a NULL list,
  *   scratch or input of the op. */
 #define MOBGS_STATS_MAX_VIEWS 16
+#define MOBGS_RADII_INT32 0
+#define MOBGS_RADII_FP32 1
 typedef enum MobgsDensifyPlanOp {
     MOBGS_PLAN_PRUNECLONE = 0,
     MOBGS_PLAN_PRUNE_OPACITY = 1,
@@ -1524,6 +1537,10 @@ int mobgs_densify_stats_batch(int n_views, const float* const* grads_host, int g
                               const int32_t* const* radii_host, int row0, int n, float sx, float sy,
                               float* xyz_gradient_accum, float* denom, float* max_radii2D, float* grad_sum,
                               int32_t* radii_max, uint8_t* visible, void* stream);
+int mobgs_densify_stats_sets(int n_views, const float* const* grads_host, int grad_stride, const void* const* radii_host,
+                             int radii_encoding, float sx, float sy, int row0_a, int n_a, float* xyz_gradient_accum_a,
+                             float* denom_a, float* max_radii2D_a, int row0_b, int n_b, float* xyz_gradient_accum_b,
+                             float* denom_b, float* max_radii2D_b, void* stream);
 int mobgs_densify_plan(int op, int n, int n_split, const float* xyz_gradient_accum, const float* denom,
                        const float* scaling, float grad_threshold, float size_threshold, const float* opacity,
                        float min_opacity, const float* xyz, const float* bounds, const uint8_t* mask, int32_t* index,

@@ -47,6 +47,53 @@ densify_stats_batch_kernel(BatchViews V, int n_views, int vstride, int row0, int
     denom[i] += 1.f;
 }
 
+// ---- statistics of a batch, both sets in one launch -----------------------------------------------------------------
+// The arithmetic of densify_stats_batch_kernel, row for row, over up to two sets whose rows are dealt to the threads one
+// after the other (a workgroup may hold the last rows of the first set and the first rows of the second).  The radii of a
+// view are either contiguous int32 or fp32-coded integers (the last third of a gradient message's slot: exact below 2^24,
+// converted with a round-to-nearest that has nothing to round).
+struct SetsViews {
+    const float* grad[MAX_VIEWS];
+    const void* radii[MAX_VIEWS];
+};
+struct StatsSet {
+    int row0, n;
+    float *accum, *denom, *max_radii;
+};
+
+template <bool CODED>
+__device__ __forceinline__ int radius_at(const void* radii, size_t row) {
+    if (CODED) return __float2int_rn(static_cast<const float*>(radii)[row]);
+    return static_cast<const int32_t*>(radii)[row];
+}
+
+template <bool CODED>
+__global__ void __launch_bounds__(256)
+densify_stats_sets_kernel(SetsViews V, int n_views, int vstride, StatsSet A, StatsSet B, float sx, float sy) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= A.n + B.n) return;
+    const bool second = t >= A.n;
+    const int i = second ? t - A.n : t;
+    const size_t row = (size_t)(second ? B.row0 : A.row0) + i;
+    float* __restrict__ accum = second ? B.accum : A.accum;
+    float* __restrict__ denom = second ? B.denom : A.denom;
+    float* __restrict__ max_radii = second ? B.max_radii : A.max_radii;
+    float gx = 0.f, gy = 0.f;
+    int r = radius_at<CODED>(V.radii[0], row);
+    for (int v = 0; v < n_views; ++v) {
+        const float* g = V.grad[v] + row * vstride;
+        gx = gx + g[0];
+        gy = gy + g[1];
+        r = max(r, radius_at<CODED>(V.radii[v], row));
+    }
+    gx = gx * sx;
+    gy = gy * sy;
+    if (!(r > 0)) return;  // visible in no view: not written
+    max_radii[i] = fmaxf(max_radii[i], (float)r);
+    accum[i] += __fsqrt_rn(__fadd_rn(__fmul_rn(gx, gx), __fmul_rn(gy, gy)));
+    denom[i] += 1.f;
+}
+
 // ---- the plan -----------------------------------------------------------------------------------------------------
 struct PlanArgs {
     int op, n, n_split;
@@ -194,6 +241,48 @@ int mobgs_densify_stats_batch(int n_views, const float* const* grads_host, int g
     hipLaunchKernelGGL(densify_stats_batch_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, V, n_views,
                        grad_stride, row0, n, sx, sy, xyz_gradient_accum, denom, max_radii2D, grad_sum, radii_max, visible);
     return check_launch("densify_stats_batch_kernel");
+}
+
+int mobgs_densify_stats_sets(int n_views, const float* const* grads_host, int grad_stride, const void* const* radii_host,
+                             int radii_encoding, float sx, float sy, int row0_a, int n_a, float* xyz_gradient_accum_a,
+                             float* denom_a, float* max_radii2D_a, int row0_b, int n_b, float* xyz_gradient_accum_b,
+                             float* denom_b, float* max_radii2D_b, void* stream) {
+    if (n_views < 1 || n_views > MAX_VIEWS) {
+        set_error("mobgs_densify_stats_sets: n_views = %d (1..%d)", n_views, MAX_VIEWS);
+        return MOBGS_E_INVALID;
+    }
+    if (radii_encoding != MOBGS_RADII_INT32 && radii_encoding != MOBGS_RADII_FP32) {
+        set_error("mobgs_densify_stats_sets: radii_encoding = %d (MOBGS_RADII_INT32 or MOBGS_RADII_FP32)", radii_encoding);
+        return MOBGS_E_INVALID;
+    }
+    if (n_a < 0 || n_b < 0 || row0_a < 0 || row0_b < 0 || grad_stride < 2 || !grads_host || !radii_host ||
+        (long long)n_a + n_b > 2147483647ll ||
+        (n_a > 0 && (!xyz_gradient_accum_a || !denom_a || !max_radii2D_a)) ||
+        (n_b > 0 && (!xyz_gradient_accum_b || !denom_b || !max_radii2D_b))) {
+        set_error("mobgs_densify_stats_sets: bad arguments n=%d+%d row0=%d,%d stride=%d or a NULL table", n_a, n_b, row0_a,
+                  row0_b, grad_stride);
+        return MOBGS_E_INVALID;
+    }
+    SetsViews V;
+    for (int v = 0; v < MAX_VIEWS; ++v) {
+        V.grad[v] = v < n_views ? grads_host[v] : nullptr;
+        V.radii[v] = v < n_views ? radii_host[v] : nullptr;
+        if (v < n_views && n_a + n_b > 0 && (!V.grad[v] || !V.radii[v])) {
+            set_error("mobgs_densify_stats_sets: view %d has a NULL pointer", v);
+            return MOBGS_E_INVALID;
+        }
+    }
+    if (n_a + n_b == 0) return MOBGS_OK;
+    const StatsSet A = {row0_a, n_a, xyz_gradient_accum_a, denom_a, max_radii2D_a};
+    const StatsSet B = {row0_b, n_b, xyz_gradient_accum_b, denom_b, max_radii2D_b};
+    const dim3 grid((n_a + n_b + 255) / 256), block(256);
+    if (radii_encoding == MOBGS_RADII_FP32)
+        hipLaunchKernelGGL(densify_stats_sets_kernel<true>, grid, block, 0, (hipStream_t)stream, V, n_views, grad_stride, A,
+                           B, sx, sy);
+    else
+        hipLaunchKernelGGL(densify_stats_sets_kernel<false>, grid, block, 0, (hipStream_t)stream, V, n_views, grad_stride, A,
+                           B, sx, sy);
+    return check_launch("densify_stats_sets_kernel");
 }
 
 int mobgs_densify_plan(int op, int n, int n_split, const float* xyz_gradient_accum, const float* denom,

@@ -213,11 +213,25 @@ class FlatGradients:
     all-reduce per buffer (no torch.cat, no copy back).  `extra` reserves named fp32 slots for per-step statistics
     that ride in the same message (name -> number of floats)."""
 
+    GROWTH = 1.5   # rebind(): a storage that no longer fits grows to this times the need (+ 1024), as the tables do
+
     def __init__(self, params: Sequence[torch.Tensor], extra: Optional[Dict[str, int]] = None):
-        self.params = [p for p in params if p.requires_grad]
-        if any(p.dtype not in (torch.float32, torch.float16) for p in self.params):
+        self.params: List[torch.Tensor] = []
+        self.views: List[torch.Tensor] = []
+        self._store: Dict[torch.dtype, Optional[torch.Tensor]] = {torch.float32: None, torch.float16: None}
+        self._device = torch.device("cpu")
+        self._lay(params, extra, grow=False)
+
+    def _lay(self, params, extra, grow: bool) -> None:
+        """The layout over `params` and `extra`: fp32 parameters in order, then the named slots, in `flat`; fp16
+        parameters in order in `flat_half`.  Both are prefixes of their storage, which is kept when it holds the layout
+        and otherwise allocated anew (grow: with GROWTH's headroom)."""
+        params = [p for p in params if p.requires_grad]
+        if any(p.dtype not in (torch.float32, torch.float16) for p in params):
             raise NotImplementedError("FlatGradients holds fp32 / fp16 parameters")
-        dev = self.params[0].device if self.params else torch.device("cpu")
+        self.params = params
+        if params:
+            self._device = params[0].device
         self.extra_slices: Dict[str, slice] = {}
         sizes = {torch.float32: 0, torch.float16: 0}
         for p in self.params:
@@ -227,14 +241,35 @@ class FlatGradients:
         for name, k in (extra or {}).items():
             self.extra_slices[name] = slice(off, off + int(k))
             off += int(k)
-        self.flat = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.flat_half = torch.zeros(sizes[torch.float16], dtype=torch.float16, device=dev)
-        self.views: List[torch.Tensor] = []
+        sizes[torch.float32] = off
+        for dtype, need in sizes.items():
+            st = self._store[dtype]
+            if st is None or st.numel() < need or st.device != self._device:
+                room = int(need * self.GROWTH) + 1024 if grow else need
+                self._store[dtype] = torch.zeros(room, dtype=dtype, device=self._device)
+        self.flat = self._store[torch.float32][:sizes[torch.float32]]
+        self.flat_half = self._store[torch.float16][:sizes[torch.float16]]
+        self.views = []
         o = {torch.float32: 0, torch.float16: 0}
         for p in self.params:
             buf = self.flat if p.dtype == torch.float32 else self.flat_half
             self.views.append(buf[o[p.dtype]:o[p.dtype] + p.numel()].view_as(p))
             o[p.dtype] += p.numel()
+
+    def rebind(self, params: Sequence[torch.Tensor], extra: Optional[Dict[str, int]] = None) -> "FlatGradients":
+        """Lay the views over `params` as they are NOW -- after a resize, an opacity reset or a load the sets' Parameters
+        are new objects and their row counts may differ -- and over new `extra` slot sizes (None: no slots).  The storage
+        is kept when the new layout fits in it (a smaller layout never shrinks it) and otherwise replaced by one of
+        GROWTH times the need, so a run that resizes every 100 iterations allocates a handful of times.  Afterwards every
+        parameter's .grad is its view, both buffers are zero, attached() / extra(name) / param_floats / buffers() describe
+        the new layout, and no parameter -- old or new -- holds an old view."""
+        stale = {v.data_ptr() for v in self.views}
+        for p in self.params:
+            if p.grad is not None and p.grad.data_ptr() in stale:
+                p.grad = None
+        self._lay(params, extra, grow=True)
+        self.zero()
+        return self
 
     def buffers(self) -> List[torch.Tensor]:
         return [b for b in (self.flat, self.flat_half) if b.numel()]
